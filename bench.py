@@ -16,9 +16,18 @@ GPU, created BEFORE this process imports torch or touches HIP (a process that ha
 initialised the GPU is never forked or re-exec'ed) -- and exits with their status.  This
 replaces the reference's fork-per-draw (parallel::mclapply, pendulum_fit.R:261-268).
 
-The line also carries a `c4` sub-record: BASELINE config c4 (the 64-point rho x sigma grid at
-N=8192) sharded over the same ranks, its wall time, and the speed-up over ONE rank evaluating
-all 64 points in the same run (strong scaling), with the sharded results compared bit for bit.
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`metric`, `value`,
+`unit`, `ms_per_step`, ...).  Everything else the benchmark measures runs only with --full, after the
+timed steps: the roofline pass (per-kernel HIP-event timing, one evaluation at a time) and the
+sequential figures, the host-buffer ABI call, the c1 sub-record (the reference's own sizes), the CPU
+baselines and a `c4` sub-record: BASELINE config c4 (the 64-point rho x sigma grid at N=8192)
+sharded over the same ranks, its wall time, and the speed-up over ONE rank evaluating all 64
+points in the same run (strong scaling), with the sharded results compared bit for bit.
+
+--dump-outputs DIR writes what the last timed step returned, as float64 arrays: DIR/out3.npy
+(points x 3: logml, sum log L_ii, z'z) and DIR/info.npy (points: 0, or the order of the first
+non-positive-definite minor): rank 0's point(s) of that step, for c4 the whole gathered grid.  The
+inputs are seeded (gp_amd.synth), so the same arguments give the same inputs in every run.
 """
 import argparse
 import glob
@@ -62,6 +71,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c4", action="store_true", help="skip the c4 strong-scaling sub-record")
     ap.add_argument("--no-c1", action="store_true", help="skip the c1 / small-N sub-record (PMC passes: keeps per-kernel averages clean)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline / sequential passes, the host-buffer call, and the "
+                         "c1, c4 and CPU-baseline sub-records (--no-c1 / --no-c4 / --no-cpu-baseline skip parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/out3.npy and DIR/info.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -119,11 +133,14 @@ def cpu_baseline(n_sample, D, cores=1):
 def cpu_lapack(n_sample, D, threads):
     """Best-effort CPU leg: the same evaluation with numpy + LAPACK
     dpotrf / dtrtrs (scipy, OpenBLAS) on `threads` host threads -- an upper bound for what a CPU
-    build of the reference's path could reach, next to the single-threaded restatement."""
+    build of the reference's path could reach, next to the single-threaded restatement.  The thread
+    count is capped at the pool OpenBLAS started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else
+    the host's cores): raising it past that pool crashes OpenBLAS.  Returns (seconds, logml, threads)."""
     import scipy.linalg as sla
-    from threadpoolctl import threadpool_limits
+    from threadpoolctl import threadpool_info, threadpool_limits
     from oracle import oracle as orc
     X, y = orc.synth(n_sample, D)
+    threads = min([threads] + [p["num_threads"] for p in threadpool_info() if p.get("internal_api") == "openblas"])
     with threadpool_limits(limits=threads):
         t0 = time.perf_counter()
         G = X @ X.T
@@ -140,7 +157,7 @@ def cpu_lapack(n_sample, D, threads):
         sld = float(np.sum(np.log(np.diag(L))))
         lm = -0.5 * float(z @ z) - sld - 0.5 * n_sample * np.log(2.0 * np.pi)
         dt = time.perf_counter() - t0
-    return dt, lm
+    return dt, lm, threads
 
 
 # ---- PMC summaries committed under profiles/ -----------------------------------------------------------
@@ -422,13 +439,27 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
 
-    # Roofline pass (same run, rank 0 only, after the timed region): the same evaluations one at
+    # the timed steps' results, copied before the --full passes below re-evaluate points into the same buffers
+    if args.workload == "c4":
+        f4 = full4.cpu().numpy()
+        res, info = f4[:, :3], f4[:, 3].astype(np.int32)
+        last_out3, last_info = res, info                      # the last step: the whole grid
+    else:
+        res = dout.cpu().numpy()[warm * per_step:]
+        info = dinfo.cpu().numpy()[warm * per_step:]
+        last_out3, last_info = res[(steps - 1) * per_step:], info[(steps - 1) * per_step:]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "out3.npy"), np.ascontiguousarray(last_out3, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "info.npy"), np.ascontiguousarray(last_info, dtype=np.float64))
+
+    # Roofline pass (--full; same run, rank 0 only, after the timed region): the same evaluations one at
     # a time with HIP-event pairs around every covariance-build, trailing-update and panel-phase
     # launch group on the launch stream.  Done separately because concurrent lanes overlap launches,
     # which makes per-launch durations meaningless inside the throughput region.
     kt = {"syrk": (0, 0.0, 0.0), "build": (0, 0.0, 0.0), "panel": (0, 0.0, 0.0), "syrk_multi_round": (0, 0.0, 0.0)}
     seq_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ctx.set_option("grid_lanes", 1)
         ctx.set_option("kernel_timing", 1)
         ctx.kernel_timing(reset=True)
@@ -459,17 +490,11 @@ def main():
     if distributed:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=coll_group)
     elapsed = float(tmax.item())
-    if args.workload == "c4":
-        f4 = full4.cpu().numpy()
-        res, info = f4[:, :3], f4[:, 3].astype(np.int32)
-    else:
-        res = dout.cpu().numpy()[warm * per_step:]
-        info = dinfo.cpu().numpy()[warm * per_step:]
     ok = bool(np.all(info == 0) and np.all(np.isfinite(res[:, 0])))
 
-    # ---- c4 sub-record: the 64-point grid at N=8192 over the same ranks (strong scaling) --------------
+    # ---- c4 sub-record (--full): the 64-point grid at N=8192 over the same ranks (strong scaling) -----
     c4 = None
-    if args.workload == "c3" and not args.no_c4:
+    if args.full and args.workload == "c3" and not args.no_c4:
         X4, y4 = synth(C4_N, C4_D)
         dX4 = torch.from_numpy(np.ascontiguousarray(X4.T)).to(dev)
         dy4 = torch.from_numpy(y4).to(dev)
@@ -521,16 +546,9 @@ def main():
         evals = steps * (C4_G if args.workload == "c4" else world * per_step)
         value = evals / elapsed
         order = 2 * n if args.workload == "c5" else n
-        syrk_n, syrk_ms, syrk_flops = kt["syrk"]
-        build_n, build_ms, build_bytes = kt["build"]
-        pan_n, pan_ms, pan_flops = kt["panel"]
-        mr_n, mr_ms, mr_flops = kt["syrk_multi_round"]
-        ach = syrk_flops / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
-        pach = pan_flops / (pan_ms * 1e-3) / 1e12 if pan_ms > 0 else 0.0
         chol_flops = order ** 3 / 3.0
         nbo_auto = (lambda nf: 1024 if nf >= 8192 else 512 if nf >= 4608 else 256 if nf >= 3584 else 128)(order)
         build_kernel = "k_joint_cov" if args.workload == "c5" else "k_se_cov<%d>" % D
-        syrk_traffic, syrk_util, syrk_src = pmc_lookup(args.workload, order, "k_gemm_nt<1>")
         line = {
             "metric": {"c3": "gp_logml_evals_per_sec_N%d_D%d" % (n, D),
                        "c4": "gp_logml_grid64_evals_per_sec_N%d_D%d" % (n, D),
@@ -566,111 +584,131 @@ def main():
             "launched_by": "bench.py launcher" if os.environ.get("GPMI_BENCH_LAUNCHED") else
                            ("torchrun / external" if distributed else "single process"),
             "grid_lanes": args.grid_lanes or "auto(4)",
-            "ms_per_eval_sequential": seq_ms,
-            "ms_per_eval_sequential_instrumented": seq_inst_ms,
             "logml_first": float(res[0, 0]),
             "cholesky_tflops_per_gpu_whole_eval": chol_flops * evals / world / elapsed / 1e12,
-            "roofline": {
-                "kernel": "k_gemm_nt<1> (trailing-update SYRK, v_mfma_f64_16x16x4_f64)",
-                "bound": "mfma",
-                "measured_in": "instrumented sequential pass of the same evaluations in this run "
-                               "(lanes=1: bracketed launches run alone on the chip)",
-                "achieved": ach,
-                "peak": FP64_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": ach / FP64_PEAK_TFLOPS,
-                "traffic": syrk_traffic,
-                "traffic_unit": "bytes/launch (PMC: 2*FETCH_SIZE + WRITE_SIZE, separate passes)",
-                "traffic_source": syrk_src,
-                "mfma_util_pmc": syrk_util,
-                "launches": int(syrk_n),
-                "avg_launch_ms": syrk_ms / max(syrk_n, 1),
-                "flops_per_launch_avg": syrk_flops / max(syrk_n, 1),
-                # subset of the above: launches of more than one round of tiles (throughput-bound; a single-round
-                # launch also factors the next diagonal block and is bounded by that ~27 us latency chain)
-                "multi_round_launches": {
-                    "launches": int(mr_n), "avg_launch_ms": mr_ms / max(mr_n, 1),
-                    "achieved": mr_flops / (mr_ms * 1e-3) / 1e12 if mr_ms > 0 else 0.0,
-                    "frac": (mr_flops / (mr_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS) if mr_ms > 0 else 0.0,
-                    "share_of_syrk_flops": mr_flops / syrk_flops if syrk_flops > 0 else 0.0},
-            },
-            "roofline_panel": {
-                "kernel": "panel phase of one outer block: k_potrf_diag4 + k_trsm_panel + k_gemm_nt<0> (in-block "
-                          "products with the fused diagonal blocks); latency chain, 128 sequential pivot blocks",
-                "bound": "mfma",
-                "achieved": pach,
-                "peak": FP64_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": pach / FP64_PEAK_TFLOPS,
-                "outer_blocks": int(pan_n),
-                "ms_per_eval": pan_ms / max(nprof, 1),
-                "mfma_util_pmc_gemm_nt0": pmc_lookup(args.workload, order, "k_gemm_nt<0>")[1],
-                "mfma_util_pmc_trsm_panel": pmc_lookup(args.workload, order, "k_trsm_panel")[1],
-                "traffic_gemm_nt0": pmc_lookup(args.workload, order, "k_gemm_nt<0>")[0],
-            },
-            "roofline_build": {
-                "kernel": "k_joint_cov (lower-triangular joint [y, y'] covariance build)" if args.workload == "c5"
-                else "%s (lower-triangular SE covariance build)" % build_kernel,
-                "bound": "hbm",
-                "achieved": build_bytes / (build_ms * 1e-3) / 1e9 if build_ms > 0 else 0.0,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": (build_bytes / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if build_ms > 0 else 0.0,
-                "traffic": pmc_lookup(args.workload, order, build_kernel)[0],
-                "algorithmic_bytes_per_launch": build_bytes / max(build_n, 1),
-                "avg_launch_ms": build_ms / max(build_n, 1),
-            },
         }
-        if c4 is not None:
-            line["c4"] = c4
-        if world == 1 and args.workload == "c3":
-            # the host-buffer entry point `.Call` binds (gpmi_logml): X, y over PCIe, 3 doubles back,
-            # blocking -- the PCIe-inclusive time of one evaluation, never `value`
-            ctx.set_stream(None)
-            ctx.logml(X, y, 1.0, [0.3], 0.1)
-            t1 = time.perf_counter()
-            ctx.logml(X, y, 1.0, [0.3], 0.1)
-            line["ms_per_eval_host_buffer_abi"] = 1e3 * (time.perf_counter() - t1)
-        if world == 1 and args.workload == "c3" and not args.no_c1:
-            line["c1"] = c1_record(ctx, dev, args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline and args.workload == "c3":
-            ns = args.cpu_sample_n
-            dt, lm_cpu = cpu_baseline(ns, D)
-            # parity of the sample size on the GPU, for the record
-            Xs, ys = synth(ns, D)
-            ctx.set_stream(None)
-            lm_gpu = ctx.logml(Xs, ys, 1.0, [0.3], 0.1)[0]
-            scale = (float(n) / ns) ** 3
-            line["cpu_baseline"] = {
-                "value": 1.0 / (dt * scale),
-                "unit": "evals/s",
-                "cores": 1,
-                "kind": "port",
-                "sample": "one full evaluation at N=%d, D=%d by the single-threaded oracle (%.2f s), "
-                          "scaled to N=%d by (N/Ns)^3" % (ns, D, dt, n),
-                "sample_seconds": dt,
-                "sample_rel_err_gpu_vs_cpu": abs(lm_gpu - lm_cpu) / abs(lm_cpu),
-                "host_cores_available": os.cpu_count(),
-            }
-            # best-effort legs: LAPACK on the CPU share of a one-GPU box (16 threads) and on ALL host cores
-            usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-            line["cpu_baseline"]["host_cores_usable"] = usable
-            for key, thr in (("lapack_16_threads", min(16, usable)), ("lapack_all_cores", usable)):
-                try:
-                    cpu_lapack(1024, D, thr)  # thread-pool warm-up
-                    dt2, lm2 = cpu_lapack(ns, D, thr)
-                    line["cpu_baseline"][key] = {
-                        "value": 1.0 / (dt2 * scale), "unit": "evals/s", "cores": thr,
-                        "sample": "numpy + LAPACK dpotrf/dtrtrs (scipy, OpenBLAS) at N=%d (%.2f s), scaled by "
-                                  "(N/Ns)^3; upper bound for a CPU build, not the reference's path" % (ns, dt2),
-                        "sample_rel_err_vs_oracle": abs(lm2 - lm_cpu) / abs(lm_cpu)}
-                except Exception as e:  # optional leg: never fails the bench line
-                    line["cpu_baseline"][key] = {"error": repr(e)}
-        print(json.dumps(line))
-        sys.stdout.flush()
+        if not args.full:
+            print(json.dumps(line))
+            sys.stdout.flush()
+        else:
+            full_records(args, line, ctx, dev, X, y, n, D, order, build_kernel, kt, nprof, seq_ms, seq_inst_ms, c4, world)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_records(args, line, ctx, dev, X, y, n, D, order, build_kernel, kt, nprof, seq_ms, seq_inst_ms, c4, world):
+    """--full, rank 0: the roofline / sequential figures of the pass after the timed region, the c4
+    sub-record, the host-buffer call, c1 and the CPU baselines are added to the line, which is printed."""
+    from gp_amd.synth import synth
+    syrk_n, syrk_ms, syrk_flops = kt["syrk"]
+    build_n, build_ms, build_bytes = kt["build"]
+    pan_n, pan_ms, pan_flops = kt["panel"]
+    mr_n, mr_ms, mr_flops = kt["syrk_multi_round"]
+    ach = syrk_flops / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
+    pach = pan_flops / (pan_ms * 1e-3) / 1e12 if pan_ms > 0 else 0.0
+    syrk_traffic, syrk_util, syrk_src = pmc_lookup(args.workload, order, "k_gemm_nt<1>")
+    line.update({
+        "ms_per_eval_sequential": seq_ms,
+        "ms_per_eval_sequential_instrumented": seq_inst_ms,
+        "roofline": {
+            "kernel": "k_gemm_nt<1> (trailing-update SYRK, v_mfma_f64_16x16x4_f64)",
+            "bound": "mfma",
+            "measured_in": "instrumented sequential pass of the same evaluations in this run "
+                           "(lanes=1: bracketed launches run alone on the chip)",
+            "achieved": ach,
+            "peak": FP64_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": ach / FP64_PEAK_TFLOPS,
+            "traffic": syrk_traffic,
+            "traffic_unit": "bytes/launch (PMC: 2*FETCH_SIZE + WRITE_SIZE, separate passes)",
+            "traffic_source": syrk_src,
+            "mfma_util_pmc": syrk_util,
+            "launches": int(syrk_n),
+            "avg_launch_ms": syrk_ms / max(syrk_n, 1),
+            "flops_per_launch_avg": syrk_flops / max(syrk_n, 1),
+            # subset of the above: launches of more than one round of tiles (throughput-bound; a single-round
+            # launch also factors the next diagonal block and is bounded by that ~27 us latency chain)
+            "multi_round_launches": {
+                "launches": int(mr_n), "avg_launch_ms": mr_ms / max(mr_n, 1),
+                "achieved": mr_flops / (mr_ms * 1e-3) / 1e12 if mr_ms > 0 else 0.0,
+                "frac": (mr_flops / (mr_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS) if mr_ms > 0 else 0.0,
+                "share_of_syrk_flops": mr_flops / syrk_flops if syrk_flops > 0 else 0.0},
+        },
+        "roofline_panel": {
+            "kernel": "panel phase of one outer block: k_potrf_diag4 + k_trsm_panel + k_gemm_nt<0> (in-block "
+                      "products with the fused diagonal blocks); latency chain, 128 sequential pivot blocks",
+            "bound": "mfma",
+            "achieved": pach,
+            "peak": FP64_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": pach / FP64_PEAK_TFLOPS,
+            "outer_blocks": int(pan_n),
+            "ms_per_eval": pan_ms / max(nprof, 1),
+            "mfma_util_pmc_gemm_nt0": pmc_lookup(args.workload, order, "k_gemm_nt<0>")[1],
+            "mfma_util_pmc_trsm_panel": pmc_lookup(args.workload, order, "k_trsm_panel")[1],
+            "traffic_gemm_nt0": pmc_lookup(args.workload, order, "k_gemm_nt<0>")[0],
+        },
+        "roofline_build": {
+            "kernel": "k_joint_cov (lower-triangular joint [y, y'] covariance build)" if args.workload == "c5"
+            else "%s (lower-triangular SE covariance build)" % build_kernel,
+            "bound": "hbm",
+            "achieved": build_bytes / (build_ms * 1e-3) / 1e9 if build_ms > 0 else 0.0,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": (build_bytes / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if build_ms > 0 else 0.0,
+            "traffic": pmc_lookup(args.workload, order, build_kernel)[0],
+            "algorithmic_bytes_per_launch": build_bytes / max(build_n, 1),
+            "avg_launch_ms": build_ms / max(build_n, 1),
+        },
+    })
+    if c4 is not None:
+        line["c4"] = c4
+    if world == 1 and args.workload == "c3":
+        # the host-buffer entry point `.Call` binds (gpmi_logml): X, y over PCIe, 3 doubles back,
+        # blocking -- the PCIe-inclusive time of one evaluation, never `value`
+        ctx.set_stream(None)
+        ctx.logml(X, y, 1.0, [0.3], 0.1)
+        t1 = time.perf_counter()
+        ctx.logml(X, y, 1.0, [0.3], 0.1)
+        line["ms_per_eval_host_buffer_abi"] = 1e3 * (time.perf_counter() - t1)
+    if world == 1 and args.workload == "c3" and not args.no_c1:
+        line["c1"] = c1_record(ctx, dev, args.no_cpu_baseline)
+    if world == 1 and not args.no_cpu_baseline and args.workload == "c3":
+        ns = args.cpu_sample_n
+        dt, lm_cpu = cpu_baseline(ns, D)
+        # parity of the sample size on the GPU, for the record
+        Xs, ys = synth(ns, D)
+        ctx.set_stream(None)
+        lm_gpu = ctx.logml(Xs, ys, 1.0, [0.3], 0.1)[0]
+        scale = (float(n) / ns) ** 3
+        line["cpu_baseline"] = {
+            "value": 1.0 / (dt * scale),
+            "unit": "evals/s",
+            "cores": 1,
+            "kind": "port",
+            "sample": "one full evaluation at N=%d, D=%d by the single-threaded oracle (%.2f s), "
+                      "scaled to N=%d by (N/Ns)^3" % (ns, D, dt, n),
+            "sample_seconds": dt,
+            "sample_rel_err_gpu_vs_cpu": abs(lm_gpu - lm_cpu) / abs(lm_cpu),
+            "host_cores_available": os.cpu_count(),
+        }
+        # best-effort legs: LAPACK on the CPU share of a one-GPU box (16 threads) and on ALL host cores
+        usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        line["cpu_baseline"]["host_cores_usable"] = usable
+        for key, thr in (("lapack_16_threads", min(16, usable)), ("lapack_all_cores", usable)):
+            try:
+                cpu_lapack(1024, D, thr)  # thread-pool warm-up
+                dt2, lm2, thr = cpu_lapack(ns, D, thr)
+                line["cpu_baseline"][key] = {
+                    "value": 1.0 / (dt2 * scale), "unit": "evals/s", "cores": thr,
+                    "sample": "numpy + LAPACK dpotrf/dtrtrs (scipy, OpenBLAS) at N=%d (%.2f s), scaled by "
+                              "(N/Ns)^3; upper bound for a CPU build, not the reference's path" % (ns, dt2),
+                    "sample_rel_err_vs_oracle": abs(lm2 - lm_cpu) / abs(lm_cpu)}
+            except Exception as e:  # optional leg: never fails the bench line
+                line["cpu_baseline"][key] = {"error": repr(e)}
+    print(json.dumps(line))
+    sys.stdout.flush()
 
 
 if __name__ == "__main__":

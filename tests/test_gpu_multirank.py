@@ -39,12 +39,12 @@ def test_sharded_dev_without_process_group_equals_grid_entry_point(ctx):
 
 
 def test_bench_two_rank_rehearsal_runs_the_products_sharded_grid():
-    """`python bench.py --gpus 2 --rehearse` as a fresh child process: the launcher starts two ranks, both on
+    """`python bench.py --gpus 2 --rehearse --full` as a fresh child process: the launcher starts two ranks, both on
     cuda:0, gloo rendezvous; the c3 line's c4 sub-record is produced by gp_amd.grid.logml_grid_sharded_dev
     and its sharded results equal rank 0's one-rank evaluation of all 64 points bit for bit."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -4,7 +4,7 @@ cp $R/gp_amd/csrc/libgpmi.so $R/gp_amd/csrc/new.so
 cd /tmp && export TMPDIR=/tmp
 for v in new old; do
   if [ $v = old ]; then cp $R/gp_amd/csrc/libgpmi_old.so $R/gp_amd/csrc/libgpmi.so; fi
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/t_$v -- python3 $R/bench.py --n $N --grid-lanes 1 --steps 2 --warmup 1 --no-cpu-baseline --no-c4 --no-c1 > $O/t_$v.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/t_$v -- python3 $R/bench.py --full --n $N --grid-lanes 1 --steps 2 --warmup 1 --no-cpu-baseline --no-c4 --no-c1 > $O/t_$v.log 2>&1
   python3 - $O/t_$v > $O/launches_${v}_n$N.txt <<'PY'
 import csv, glob, os, re, sys
 f = glob.glob(os.path.join(sys.argv[1], "**", "*kernel_trace.csv"), recursive=True)[0]

@@ -1,5 +1,5 @@
 """Timeline of ONE evaluation's launches from a rocprofv3 kernel trace of
-     rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --grid-lanes 1 --steps 1 --warmup 1 --no-cpu-baseline --no-c4
+     rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --grid-lanes 1 --steps 1 --warmup 1 --no-cpu-baseline --no-c4
    per outer block: duration of the panel phase (everything between two multi-round SYRK launches), its launches by kind,
    gaps between launches; then the first block's launches one by one."""
 import csv, glob, os, re, sys
