@@ -21,6 +21,7 @@ SYMBOLS = (
     "gpmi_set_stream", "gpmi_reset_stream", "gpmi_sync", "gpmi_reserve", "gpmi_set_option",
     "gpmi_se_cov", "gpmi_se_cov_dev", "gpmi_deriv_cov", "gpmi_deriv_cov_dev", "gpmi_deriv_elem",
     "gpmi_joint_cov", "gpmi_potrf", "gpmi_potrf_dev", "gpmi_trmv_lower", "gpmi_trsv_lower", "gpmi_exact_gp_f",
+    "gpmi_trmv_lower_t", "gpmi_exact_gp_f_vjp", "gpmi_exact_gp_f_vjp_dev",
     "gpmi_logml", "gpmi_logml_dev", "gpmi_logml_grid", "gpmi_logml_grid_dev", "gpmi_logml_grid_ard", "gpmi_logml_grid_ard_dev",
     "gpmi_joint_logml", "gpmi_joint_logml_dev", "gpmi_joint_logml_grid_dev", "gpmi_rbf_cov_chol", "gpmi_gp_condition", "gpmi_sample_derivs", "gpmi_sample_derivs_batch",
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
@@ -242,6 +243,14 @@ class Context:
         _chk(self._lib.gpmi_trmv_lower(self._h, _p(L), L.shape[0], max(L.shape[0], 1), _p(z), _p(f)))
         return f
 
+    def trmv_lower_t(self, L, u):
+        """w = L^T u for lower-triangular L (the transpose of trmv_lower)."""
+        L = _mat(L); u = _vec(u); w = np.empty_like(u)
+        if L.shape[0] != u.size:
+            raise GpmiError(-1, "L and u disagree on N")
+        _chk(self._lib.gpmi_trmv_lower_t(self._h, _p(L), L.shape[0], max(L.shape[0], 1), _p(u), _p(w)))
+        return w
+
     def trsv_lower(self, L, b):
         L = _mat(L); b = _vec(b); z = np.empty_like(b)
         _chk(self._lib.gpmi_trsv_lower(self._h, _p(L), L.shape[0], max(L.shape[0], 1), _p(b), _p(z)))
@@ -257,6 +266,25 @@ class Context:
         f = np.empty(n)
         _chk(self._lib.gpmi_exact_gp_f(self._h, _p(X), n, n, D, _d(alpha), _p(ell), int(ell.size), _d(jitter), _p(z), _p(f)))
         return f
+
+    def exact_gp_f_vjp(self, X, alpha, ell, Z, Fbar, jitter=1e-10):
+        """(F, Zbar, grad) of F = chol(cov_exp_quad(X, alpha, ell) + jitter I) Z with upstream adjoint Fbar:
+        Zbar = L^T Fbar, grad = (d/dalpha, d/dell...) of sum(Fbar * F).  Z and Fbar are 1-D (one column) or n x k;
+        F and Zbar come back in the same shape.  Raises NotPositiveDefinite."""
+        X = _mat(X); ell = _vec(ell)
+        n, D = X.shape
+        one = np.ndim(Z) == 1
+        Zm = _mat(Z); Fb = _mat(Fbar)
+        if Zm.shape[0] != n or Fb.shape != Zm.shape:
+            raise GpmiError(-1, "X, Z and Fbar disagree on the shape")
+        k = Zm.shape[1]
+        F = np.empty((n, k), order="F"); Zb = np.empty((n, k), order="F"); g = np.empty(1 + ell.size)
+        ld = max(n, 1)
+        _chk(self._lib.gpmi_exact_gp_f_vjp(self._h, _p(X), n, ld, D, _d(alpha), _p(ell), int(ell.size), _d(jitter), _p(Zm), k, ld,
+                                           _p(Fb), ld, _p(F), ld, _p(Zb), ld, _p(g)))
+        if one:
+            return F[:, 0], Zb[:, 0], g
+        return F, Zb, g
 
     # ---- marginal likelihood -------------------------------------------------
     def logml(self, X, y, alpha, ell, sigma, jitter=0.0):
@@ -430,6 +458,15 @@ class Context:
         _chk(self._lib.gpmi_logml_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), C.c_void_p(dy_ptr),
                                       _d(alpha), _p(ell), int(ell.size), _d(sigma), _d(jitter),
                                       C.c_void_p(dout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def exact_gp_f_vjp_dev(self, dX_ptr, n, ldx, D, alpha, ell, jitter, dZ_ptr, k, ldz, dFbar_ptr, ldfb, dF_ptr, ldf, dZbar_ptr,
+                           ldzb, dgrad_ptr, dinfo_ptr):
+        """gpmi_exact_gp_f_vjp_dev on device pointers (dF_ptr may be None); enqueued, not synchronised."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_exact_gp_f_vjp_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), _d(alpha), _p(ell),
+                                               int(ell.size), _d(jitter), C.c_void_p(dZ_ptr), int(k), int(ldz),
+                                               C.c_void_p(dFbar_ptr), int(ldfb), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
+                                               C.c_void_p(dZbar_ptr), int(ldzb), C.c_void_p(dgrad_ptr), C.c_void_p(dinfo_ptr)))
 
     def logml_grid_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, rho, sigma, jitter, dout_ptr, dinfo_ptr):
         a = _vec(alpha); r = _vec(rho); s = _vec(sigma)

@@ -2619,6 +2619,269 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_small(const double *__restr
     small_signal_done(done, seq);
 }
 
+// The vector-Jacobian product of the same transform for k <= GPMI_VJP_KMAX columns (F = L Z; adjoint Fbar), what NUTS asks of
+// models/exact_gp.stan:17-25 (and, k = 2, of models/heteroscedastic.stan:23-32) at every leapfrog step, by ONE workgroup for
+// n <= 256.  The chain of gpmi_api.hip (exact_gp_vjp_core) states the algebra; here:
+//   build, factorisation with U = L^-T riding along (small_potrf_partial<true>, as k_logml_grad_small);
+//   F column by column with the loop of k_exact_gp_small (bit-identical to the value call);
+//   Zbar = W = L^T Fbar, thread = column of L;
+//   V = U Phi(W Z^T) by the suffix sums along the rows of U o w_c, thread = row;
+//   2 Sbar = V U^T + U V^T = [V U] [U V]^T by gemm_tile<3> with K = 2n (V, U, V stored side by side, so that ONE product per
+//   tile forms it) and contracted in registers against dK/dtheta as logml_grad_small_body contracts K^-1.
+// R: 3 n columns of leading dimension ld, [V | U | V]; the gradient (1 + n_ell) is finished on the device.
+struct VjpSmallEll {
+    double ell[GPMI_MAXD];
+};
+constexpr int VJP_KMAX = GPMI_VJP_KMAX;
+__global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
+                                                            const double *__restrict__ Z, int k, int ldz, const double *__restrict__ Fb,
+                                                            int ldfb, double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
+                                                            double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
+                                                            VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                            int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
+{
+    GPMI_SMALL_LDS
+    const int tid = threadIdx.x;
+    if (stage) {   // host-mapped X, Z, Fbar: one coalesced pass into device memory
+        const int nx = n * p.D, nz = n * k;
+        for (int e = tid; e < nx + 2 * nz; e += 256) {
+            if (e < nx) {
+                const int d = e / n, i = e - d * n;
+                stage[e] = X[(size_t)i + (size_t)d * ldx];
+            } else {
+                const int e2 = e - nx, src = e2 < nz ? e2 : e2 - nz, c = src / n, i = src - c * n;
+                stage[e] = e2 < nz ? Z[(size_t)i + (size_t)c * ldz] : Fb[(size_t)i + (size_t)c * ldfb];
+            }
+        }
+        __syncthreads();
+        X = stage;
+        Z = stage + nx;
+        Fb = stage + nx + nz;
+        ldx = ldz = ldfb = n;
+    }
+    if (tid == 0) *info_w = 0;
+    SmallSe se;
+    se.a2 = p.a2;
+    se.D = p.D;
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
+    double *V = R, *U = R + (size_t)n * ld, *V2 = R + 2 * (size_t)n * ld;
+    {
+        double *xs = &smem[0][0][0][0];
+#pragma unroll
+        for (int d = 0; d < GPMI_MAXD; ++d)
+            if (d < se.D)
+                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
+        __syncthreads();
+        for (int row0 = 0; row0 < n; row0 += SE_TR)
+            for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
+                switch (se.D) {
+                case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                }
+            }
+    }
+    {   // U = I (as logml_grad_small_body)
+        const int rp = 2 * (tid & 127), cp = tid >> 7;
+        if (rp < n)
+            for (int j = cp; j < n; j += 2) *reinterpret_cast<double2 *>(U + (size_t)rp + (size_t)j * ld) = make_double2(0.0, 0.0);
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) U[(size_t)i * (ld + 1)] = 1.0;
+    }
+    __syncthreads();
+    small_potrf_partial<true>(smem, s_F, s_aux, W, ld, n, n, n, info_w, false, U);
+    __syncthreads();
+    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the packed factors are no longer needed: s_F holds the scaled coordinates, Fbar (then W) and Z, k n doubles each
+    double *xg = s_F, *s_w = s_F + 2048, *s_z = s_F + 4096;
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d)
+        if (d < se.D)
+            for (int i = tid; i < n; i += 256) xg[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
+    for (int e = tid; e < n * k; e += 256) {
+        const int c = e / n, i = e - c * n;
+        s_z[e] = Z[(size_t)i + (size_t)c * ldz];
+        s_w[e] = Fb[(size_t)i + (size_t)c * ldfb];
+    }
+    __syncthreads();
+    // F, one column at a time: the loop of k_exact_gp_small (row sums in column order)
+    if (F)
+        for (int c = 0; c < k; ++c) {
+            if (tid < n) {
+                const int i = tid;
+                const double *zc = s_z + c * n;
+                double acc = 0.0;
+                for (int j0 = 0; j0 <= i; j0 += 16) {
+                    double u[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int j = j0 + q <= i ? j0 + q : i;
+                        u[q] = W[(size_t)i + (size_t)j * ld];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if (j0 + q <= i) acc = fma(u[q], zc[j0 + q], acc);
+                }
+                F[(size_t)i + (size_t)c * ldf] = info ? __builtin_nan("") : acc;
+            }
+        }
+    // W = L^T Fbar: thread = column j of L, all k columns at once
+    double wj[VJP_KMAX];
+#pragma unroll
+    for (int c = 0; c < VJP_KMAX; ++c) wj[c] = 0.0;
+    if (tid < n) {
+        const int j = tid;
+        const double *col = W + (size_t)j * ld;
+        for (int i0 = j; i0 < n; i0 += 8) {
+            double l8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) l8[q] = col[i0 + q < n ? i0 + q : n - 1];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (i0 + q < n)
+#pragma unroll
+                    for (int c = 0; c < VJP_KMAX; ++c)
+                        if (c < k) wj[c] = fma(l8[q], s_w[c * n + i0 + q], wj[c]);
+        }
+    }
+    __syncthreads();   // every thread has read Fbar
+    if (tid < n)
+#pragma unroll
+        for (int c = 0; c < VJP_KMAX; ++c)
+            if (c < k) {
+                s_w[c * n + tid] = wj[c];
+                Zb[(size_t)tid + (size_t)c * ldzb] = info ? __builtin_nan("") : wj[c];
+            }
+    __syncthreads();
+    // V = U Phi(W Z^T): thread = row i, columns from the last to the first, one running suffix sum per column of Z
+    if (tid < n) {
+        const int i = tid;
+        double P[VJP_KMAX];
+#pragma unroll
+        for (int c = 0; c < VJP_KMAX; ++c) P[c] = 0.0;
+        for (int j1 = n; j1 > 0; j1 -= 16) {
+            double u[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int j = j1 - 1 - q;
+                u[q] = (j >= i) ? U[(size_t)i + (size_t)j * ld] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int j = j1 - 1 - q;
+                if (j < 0) break;
+                double v = 0.0;
+#pragma unroll
+                for (int c = 0; c < VJP_KMAX; ++c)
+                    if (c < k) {
+                        const double t = u[q] * s_w[c * n + j];
+                        v = fma(s_z[c * n + j], fma(0.5, t, P[c]), v);
+                        P[c] += t;
+                    }
+                V[(size_t)i + (size_t)j * ld] = v;
+                V2[(size_t)i + (size_t)j * ld] = v;
+            }
+        }
+    }
+    __syncthreads();
+    // [V U] [U V]^T tile by tile (lower tiles), contracted where it is produced; the columns of [V U] left of the tile's first
+    // column are skipped (U's rows there are zero in V U^T; U V^T needs them all)
+    double acc[1 + GPMI_MAXD];
+#pragma unroll
+    for (int q = 0; q < 1 + GPMI_MAXD; ++q) acc[q] = 0.0;
+    const double a2 = se.a2;
+    auto sbar_tiles = [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;   // compile-time dimension count (0: se.D at run time, <= GPMI_MAXD)
+        const int Dn = DT ? DT : se.D;
+        constexpr int DH = DT ? DT : 1;
+        double xm[4][DH], xn[DH];
+        int mm[4], ncur = 0;
+        bool okn = false;
+        auto contract = make_epi3(
+            [&](int tm, int m, bool ok) {
+                mm[tm] = ok ? m : -1;
+                if constexpr (DT != 0) {
+                    const int mc = ok ? m : 0;
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) xm[tm][d] = xg[mc + d * n];
+                }
+            },
+            [&](int nn, bool ok) {
+                ncur = ok ? nn : 0;
+                okn = ok;
+                if constexpr (DT != 0) {
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) xn[d] = xg[ncur + d * n];
+                }
+            },
+            [&](double s2, int tm) {
+                double e = 0.0, r2[GPMI_MAXD];
+                const int mc = mm[tm] < 0 ? 0 : mm[tm];
+#pragma unroll
+                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) {
+                    double r;
+                    if constexpr (DT != 0) r = xm[tm][d] - xn[d];
+                    else r = d < Dn ? xg[mc + d * n] - xg[ncur + d * n] : 0.0;
+                    r2[d] = r * r;
+                    e += r2[d];
+                }
+                const double kse = a2 * exp_nonpos(-0.5 * e, ec);
+                const bool lower = okn && ncur <= mm[tm];
+                const double c = lower ? ((ncur == mm[tm]) ? 0.5 : 1.0) * s2 * kse : 0.0;
+                acc[0] += c;
+#pragma unroll
+                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) acc[1 + d] += c * r2[d];
+            });
+        for (int ti = 0; ti * GT < n; ++ti)
+            for (int tj = 0; tj <= ti; ++tj) {
+                const int k0 = tj * GT;
+                gemm_tile<3>(smem, R + (size_t)k0 * ld, ld, U + (size_t)k0 * ld, ld, W, ld, n, n, 2 * n - k0, ti, tj, 0,
+                             (int)threadIdx.x, contract);
+                __syncthreads();
+            }
+    };
+    switch (se.D) {
+    case 1: sbar_tiles(ic<1>{}); break;
+    case 2: sbar_tiles(ic<2>{}); break;
+    case 3: sbar_tiles(ic<3>{}); break;
+    default: sbar_tiles(ic<0>{}); break;
+    }
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d)   // sums over UNSCALED squared differences (layout of k_grad_partial)
+        acc[1 + d] = (d < se.D) ? acc[1 + d] / (se.inv_ell[d] * se.inv_ell[d]) : 0.0;
+    // fixed-shape reduction: butterfly inside every wave, the four wave sums added in wave order
+    double *s_r = s_aux;
+#pragma unroll
+    for (int q = 0; q < 1 + GPMI_MAXD; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if ((tid & 63) == 0) s_r[(tid >> 6) * (1 + GPMI_MAXD) + q] = v;
+    }
+    __syncthreads();
+    if (tid < 1 + GPMI_MAXD) {
+        constexpr int S = 1 + GPMI_MAXD;
+        s_r[4 * S + tid] = ((s_r[tid] + s_r[S + tid]) + s_r[2 * S + tid]) + s_r[3 * S + tid];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double *hs = s_r + 4 * (1 + GPMI_MAXD);
+        const double nan = __builtin_nan("");
+        grad[0] = info ? nan : 2.0 * hs[0] / alpha;
+        if (n_ell == 1) {
+            double t = 0.0;
+            for (int d = 0; d < se.D; ++d) t += hs[1 + d];
+            grad[1] = info ? nan : t / (el.ell[0] * el.ell[0] * el.ell[0]);
+        } else {
+            for (int d = 0; d < se.D; ++d) grad[1 + d] = info ? nan : hs[1 + d] / (el.ell[d] * el.ell[d] * el.ell[d]);
+        }
+        *info_out = info;
+    }
+    small_signal_done(done, seq);
+}
+
 // rbf_cov_chol (covariance.cpp:9-47) by ONE workgroup for n <= 128 (test_interpolate.R:5 runs it at N = 100, P = 10 times):
 // Sigma_ij = exp(-(x_i - x_j)^2 / (2 l^2)) + 1e-10 [i == j], L = chol(Sigma), and the forward-mode tangent
 // dL/dl = L Phi(L^-1 Sdot L^-T), Sdot_ij = Sigma_ij (x_i - x_j)^2 / l^3, Phi = lower triangle with halved diagonal --
@@ -2998,6 +3261,28 @@ __global__ __launch_bounds__(256) void k_trmv_lower_sum(const double *__restrict
     f[i] = s;
 }
 
+// w = L^T u (column c of u / w: blockIdx.y): one wave per column of L, w_j = sum_{i >= j} L_ij u_i -- the column is
+// contiguous, lanes stride its rows with two accumulators, then a fixed butterfly: the order of every addition depends on
+// (n, j) only, repeated calls are bit-identical
+__global__ __launch_bounds__(256) void k_trmv_lower_t(const double *__restrict__ L, size_t ldl, int n, const double *__restrict__ u,
+                                                      size_t ldu, double *__restrict__ w, size_t ldw)
+{
+    const int j = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= n) return;  // wave-uniform
+    const double *col = L + (size_t)j * ldl, *uc = u + (size_t)blockIdx.y * ldu;
+    double a0 = 0.0, a1 = 0.0;
+    int i = j + lane;
+    for (; i + 64 < n; i += 128) {
+        a0 = fma(col[i], uc[i], a0);
+        a1 = fma(col[i + 64], uc[i + 64], a1);
+    }
+    if (i < n) a0 = fma(col[i], uc[i], a0);
+    double v = a0 + a1;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) w[(size_t)blockIdx.y * ldw + j] = v;
+}
+
 #ifdef GPMI_PROBES
 // D = A(16x4) * B(4x16) with the library's operand conventions (layout probe)
 __global__ void k_probe_mfma(const double *A, const double *B, double *D)
@@ -3053,6 +3338,7 @@ static void small_lds_attr()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sample_derivs_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gp_condition_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_vjp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_cov_chol_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     const int gbytes = SMALL_GRAD_LDS_DOUBLES * (int)sizeof(double);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_grad_small), hipFuncAttributeMaxDynamicSharedMemorySize, gbytes);
@@ -3085,6 +3371,7 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->small_ng = 256;
     t->grad_aug_n = 3072;
     t->grad_aug_ng = 2304;
+    t->small_vjp = 256;
     t->small_gc = 180;    // gpmi_gp_condition by one workgroup up to n + m + 1 rows (tools/cond_bench.py)
     t->small_sd = 640;
     t->small_sdb = 5;     // tools/sample_derivs_bench.py: one workgroup 0.21 / 0.56 / 0.73 ms at n = m = 79 / 199 / 256, the lanes 95 / 136 / 129 us per draw
@@ -3761,6 +4048,21 @@ void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const
                        d_info_work, h_exp, stage, done, seq);
 }
 
+// one workgroup; W: 4 slices of small_ws_layout(n) -- the covariance / factor, then [V | U | V] (3 n columns of the same ld)
+void launch_exact_gp_vjp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *Z, int k,
+                               int ldz, const double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb, double *W, double alpha,
+                               const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage, int *done,
+                               int seq)
+{
+    size_t ld, stride;
+    small_ws_layout(n, &ld, &stride);
+    small_lds_attr();
+    VjpSmallEll el;
+    for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
+    hipLaunchKernelGGL(k_exact_gp_vjp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, Fb,
+                       ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
+}
+
 // P <= 64 length-scales, one workgroup each (n <= 128); Wall: 3 P slices of small_ws_layout(n)
 void launch_rbf_cov_chol_small(hipStream_t s, const double *x, int n, const double *ls, int P, double *Wall, double *Lout, double *dLout,
                                size_t ostride, size_t ldo, int *info_out, int *d_info_work, double *stage)
@@ -3807,6 +4109,12 @@ void launch_trmv_lower(hipStream_t s, const double *L, size_t ldl, int n, const 
     const int nchunk = trmv_lower_chunks(n);
     hipLaunchKernelGGL(k_trmv_lower_part, dim3((n + 255) / 256, nchunk), 256, 0, s, L, ldl, n, z, part);
     hipLaunchKernelGGL(k_trmv_lower_sum, dim3((n + 255) / 256), 256, 0, s, part, n, nchunk, f);
+}
+
+void launch_trmv_lower_t(hipStream_t s, const double *L, size_t ldl, int n, const double *u, size_t ldu, double *w, size_t ldw, int k)
+{
+    if (n <= 0 || k <= 0) return;
+    hipLaunchKernelGGL(k_trmv_lower_t, dim3((n + 3) / 4, k), 256, 0, s, L, ldl, n, u, ldu, w, ldw);
 }
 
 #ifdef GPMI_PROBES

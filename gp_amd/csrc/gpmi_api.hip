@@ -416,6 +416,11 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         (name[10] == 'g' ? c->tune.grad_aug_ng : c->tune.grad_aug_n) = value;
         return 0;
     }
+    if (!strcmp(name, "small_vjp")) {  // gpmi_exact_gp_f_vjp by one workgroup up to this n (<= 256; 0: off)
+        if (value < 0 || value > 256) return gpmi_fail(GPMI_EARG, "small_vjp must be 0 .. 256");
+        c->tune.small_vjp = value;
+        return 0;
+    }
     if (!strcmp(name, "small_gc")) {  // gp_condition by one workgroup up to this many rows n + m + 1 (0: off)
         if (value < 0 || value > 1024) return gpmi_fail(GPMI_EARG, "small_gc must be 0 .. 1024");
         c->tune.small_gc = value;
@@ -803,6 +808,27 @@ extern "C" int gpmi_trmv_lower(gpmi_ctx *c, const double *L, int n, int ldl, con
     launch_trmv_lower(c->stream, dL, (size_t)n, n, dz, df, df + n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(f, df, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// w = L^T u: the transpose twin of gpmi_trmv_lower (one wave per column of L, fixed-order reductions)
+extern "C" int gpmi_trmv_lower_t(gpmi_ctx *c, const double *L, int n, int ldl, const double *u, double *w)
+{
+    ENTER(c);
+    if (n < 0) return gpmi_fail(GPMI_EARG, "negative size");
+    if (n == 0) return 0;
+    if (!L || !u || !w || ldl < n) return gpmi_fail(GPMI_EARG, "bad argument");
+    double *dL, *du, *dw;
+    int rc;
+    if ((rc = stage_buf(c, 2, (size_t)n * n * sizeof(double), &dL))) return rc;
+    if ((rc = stage_buf(c, 0, (size_t)n * sizeof(double), &du))) return rc;
+    if ((rc = stage_buf(c, 1, (size_t)n * sizeof(double), &dw))) return rc;
+    if ((rc = h2d_matrix(c, L, n, n, ldl, dL))) return rc;
+    HIPCHK(hipMemcpyAsync(du, u, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    launch_trmv_lower_t(c->stream, dL, (size_t)n, n, du, (size_t)n, dw, (size_t)n, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w, dw, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2097,6 +2123,248 @@ extern "C" int gpmi_logml_grad(gpmi_ctx *c, const double *X, int n, int ldx, int
     }
     logml_grad_finish(hr + 3, D, alpha, ell, n_ell, sigma, grad);
     return 0;
+}
+
+// ---- vector-Jacobian product of the latent exact GP's transform ---------------------------------------------------
+// F = L Z, L = chol(K), K = alpha^2 K0(ell) + jitter I (models/exact_gp.stan:17-25, k = 2 columns in
+// models/heteroscedastic.stan:23-32).  Given the adjoint Fbar: Zbar = W = L^T Fbar, and with U = L^-T,
+// B = Phi(W Z^T) (lower triangle, halved diagonal), Sbar = sym(U B U^T), theta_bar = <Sbar, dK/dtheta>.
+// V = U B costs O(n^2 k) because B is a triangle-masked rank-k matrix (U upper triangular):
+//     V_ij = sum_c z_cj ( sum_{m >= max(i, j + 1)} U_im w_cm + 1/2 U_ij w_cj ),
+// a suffix sum along each row of U o w_c.  2 Sbar = V U^T + U V^T is contracted against dK/dtheta by the kernels of the
+// log-likelihood gradient (k_grad_partial[_big] with a = 0: g = 1/2 (2 Sbar)_ij).
+namespace {
+constexpr int VJP_SCOLS = 256;   // columns per chunk of the suffix sums
+// T[(c nchunk + q) n + i] = sum_{m in chunk q, m >= i} U_im w_cm
+__global__ __launch_bounds__(256) void k_vjp_suffix_part(const double *__restrict__ U, size_t ldu, int n, const double *__restrict__ Wv,
+                                                         size_t ldw, double *__restrict__ T)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y, c = blockIdx.z, nchunk = gridDim.y;
+    if (i >= n) return;
+    const int c0 = q * VJP_SCOLS, c1 = (c0 + VJP_SCOLS < n) ? c0 + VJP_SCOLS : n;
+    const double *w = Wv + (size_t)c * ldw;
+    double s = 0.0;
+    for (int m = c0 > i ? c0 : i; m < c1; ++m) s = fma(U[(size_t)i + (size_t)m * ldu], w[m], s);
+    T[((size_t)c * nchunk + q) * n + i] = s;
+}
+
+// V (and its copy V2) for the columns of chunk q: the carry from the chunks to the right added in a fixed order, then the
+// running suffix sum walks the chunk from its last column to its first; thread = row (coalesced across the wave)
+__global__ __launch_bounds__(256) void k_vjp_suffix(const double *__restrict__ U, size_t ldu, int n, const double *__restrict__ Wv,
+                                                    size_t ldw, const double *__restrict__ Z, size_t ldz, int k,
+                                                    const double *__restrict__ T, double *__restrict__ V, double *__restrict__ V2,
+                                                    size_t ldv)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y, nchunk = gridDim.y;
+    if (i >= n) return;
+    const int c0 = q * VJP_SCOLS, c1 = (c0 + VJP_SCOLS < n) ? c0 + VJP_SCOLS : n;
+    for (int c = 0; c < k; ++c) {
+        const double *w = Wv + (size_t)c * ldw, *z = Z + (size_t)c * ldz;
+        double P = 0.0;
+        for (int qq = nchunk - 1; qq > q; --qq) P += T[((size_t)c * nchunk + qq) * n + i];
+        for (int j = c1 - 1; j >= c0; --j) {
+            const double u = (j >= i) ? U[(size_t)i + (size_t)j * ldu] * w[j] : 0.0;
+            const double val = z[j] * fma(0.5, u, P);
+            P += u;
+            double *v = V + (size_t)i + (size_t)j * ldv;
+            const double acc = c ? *v + val : val;
+            *v = acc;
+            if (c == k - 1) V2[(size_t)i + (size_t)j * ldv] = acc;
+        }
+    }
+}
+
+struct VjpEll {
+    double ell[GPMI_MAXD_BIG];
+};
+// (d/dalpha, d/dell...) from the contraction sums (logml_grad_finish without the noise term); NaN when not PD
+__global__ void k_vjp_finish(const double *__restrict__ hs, int D, double alpha, VjpEll e, int n_ell, const int *__restrict__ info,
+                             double *__restrict__ grad)
+{
+    if (threadIdx.x != 0) return;
+    const bool bad = *info != 0;
+    grad[0] = bad ? __builtin_nan("") : 2.0 * hs[0] / alpha;
+    if (n_ell == 1) {
+        double t = 0.0;
+        for (int d = 0; d < D; ++d) t += hs[1 + d];
+        grad[1] = bad ? __builtin_nan("") : t / (e.ell[0] * e.ell[0] * e.ell[0]);
+    } else {
+        for (int d = 0; d < D; ++d) grad[1 + d] = bad ? __builtin_nan("") : hs[1 + d] / (e.ell[d] * e.ell[d] * e.ell[d]);
+    }
+}
+
+// A (rows x cols, ld) = NaN when *info != 0
+__global__ __launch_bounds__(256) void k_nan_on_info(double *__restrict__ A, size_t ld, int rows, int cols, const int *__restrict__ info)
+{
+    if (*info == 0) return;
+    const size_t total = (size_t)rows * cols;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t j = e / (size_t)rows, i = e - j * (size_t)rows;
+        A[i + j * ld] = __builtin_nan("");
+    }
+}
+void launch_nan_on_info(hipStream_t s, double *A, size_t ld, int rows, int cols, const int *info)
+{
+    const size_t total = (size_t)rows * cols;
+    const unsigned blocks = (unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_nan_on_info, dim3(blocks), 256, 0, s, A, ld, rows, cols, info);
+}
+}  // namespace
+
+// every buffer of the chain at its final size: c->W (K, L, then 2 Sbar), stage[2] = [V | U | V] (ldu), stage[1] = vectors,
+// scratch = the packed factors
+static int exact_gp_vjp_reserve(gpmi_ctx *c, int n, int D, int k)
+{
+    int rc;
+    if ((rc = reserve_ws(c, n, n))) return rc;
+    const size_t ldu = (size_t)(((n + 15) / 16) * 16 + 16);
+    const int npan = (n + GPMI_NB - 1) / GPMI_NB, nsch = (n + VJP_SCOLS - 1) / VJP_SCOLS;
+    const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
+    double *b;
+    if ((rc = stage_buf(c, 2, ldu * (3 * (size_t)n + 1) * sizeof(double), &b))) return rc;
+    const size_t vec = (size_t)n + GRAD_NS_MAX + ntiles * grad_ns(D) + (size_t)trmv_lower_chunks(n) * n + (size_t)k * nsch * n;
+    if ((rc = stage_buf(c, 1, vec * sizeof(double), &b))) return rc;
+    return scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &b);
+}
+
+// The chain, enqueued on c->stream: device X (ldx), Z (ldz), Fbar (ldfb); F (nullable, ldf), Zbar (ldzb), grad (1 + n_ell)
+// and *d_info written.  F is formed exactly as gpmi_exact_gp_f's blocked path forms it (same factorisation, same mat-vec).
+static int exact_gp_vjp_core(gpmi_ctx *c, const double *dX, int n, int ldx, const SeParams &p, double alpha, const double *ell,
+                             int n_ell, double jitter, const double *dZ, int k, int ldz, const double *dFb, int ldfb, double *dF,
+                             int ldf, double *dZb, int ldzb, double *d_grad, int *d_info)
+{
+    int rc;
+    if ((rc = exact_gp_vjp_reserve(c, n, p.D, k))) return rc;
+    const size_t ld = (size_t)c->ld, ldu = (size_t)(((n + 15) / 16) * 16 + 16);
+    const int nsch = (n + VJP_SCOLS - 1) / VJP_SCOLS, ns = grad_ns(p.D);
+    const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
+    double *G = c->stage[2], *V = G, *U = G + (size_t)n * ldu, *V2 = G + 2 * (size_t)n * ldu;
+    double *zero = c->stage[1], *sums = zero + n, *part = sums + GRAD_NS_MAX, *trpart = part + ntiles * ns;
+    double *spart = trpart + (size_t)trmv_lower_chunks(n) * n, *Fall = c->scratch;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
+    // K and L exactly as gpmi_exact_gp_f (the packed factors for the solve are taken from L afterwards)
+    launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, jitter, 1, c->W, ld);
+    if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, c->d_info, nullptr))) return rc;
+    if (dF)
+        for (int q = 0; q < k; ++q) launch_trmv_lower(s, c->W, ld, n, dZ + (size_t)q * ldz, dF + (size_t)q * ldf, trpart);
+    launch_trmv_lower_t(s, c->W, ld, n, dFb, (size_t)ldfb, dZb, (size_t)ldzb, k);   // Zbar = W = L^T Fbar
+    // U = L^-T
+    launch_pack_factors(s, c->W, ld, n, Fall);
+    hipLaunchKernelGGL(k_set_identity, dim3((n + 63) / 64, (n + 15) / 16), 256, 0, s, U, ldu, n);
+    if ((rc = launch_trsm_right(c, c->W, ld, n, U, ldu, n, Fall, 1))) return rc;
+    // V = U Phi(W Z^T) by suffix sums, then c->W = V U^T + U V^T = [V U] [U V]^T (L is no longer needed)
+    hipLaunchKernelGGL(k_vjp_suffix_part, dim3((n + 255) / 256, nsch, k), 256, 0, s, U, ldu, n, dZb, (size_t)ldzb, spart);
+    hipLaunchKernelGGL(k_vjp_suffix, dim3((n + 255) / 256, nsch), 256, 0, s, U, ldu, n, dZb, (size_t)ldzb, dZ, (size_t)ldz, k, spart,
+                       V, V2, ldu);
+    launch_gemm_nt(c, s, G, ldu, U, ldu, c->W, ld, n, n, 2 * n, 0);
+    // <Sbar, dK/dtheta>: the gradient contraction with a = 0
+    HIPCHK(hipMemsetAsync(zero, 0, (size_t)n * sizeof(double), s));
+    if (p.D <= GPMI_MAXD)
+        hipLaunchKernelGGL(k_grad_partial, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part);
+    else
+        hipLaunchKernelGGL(k_grad_partial_big, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part, ns);
+    hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, sums, ns);
+    VjpEll e;
+    for (int d = 0; d < GPMI_MAXD_BIG; ++d) e.ell[d] = d < n_ell ? ell[d] : 0.0;
+    hipLaunchKernelGGL(k_vjp_finish, dim3(1), 64, 0, s, sums, p.D, alpha, e, n_ell, c->d_info, d_grad);
+    if (dF) launch_nan_on_info(s, dF, (size_t)ldf, n, k, c->d_info);
+    launch_nan_on_info(s, dZb, (size_t)ldzb, n, k, c->d_info);
+    HIPCHK(hipMemcpyAsync(d_info, c->d_info, sizeof(int), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int exact_gp_vjp_check(int n, int ldx, int D, double alpha, int k, int ldz, int ldfb, bool hasF, int ldf, int ldzb)
+{
+    if (n <= 0 || D < 1 || ldx < n || k < 1 || ldz < n || ldfb < n || ldzb < n || (hasF && ldf < n))
+        return gpmi_fail(GPMI_EARG, "bad size or leading dimension");
+    if (!(alpha > 0.0) || !isfinite(alpha)) return gpmi_fail(GPMI_EARG, "alpha must be positive and finite");
+    return 0;
+}
+
+// one workgroup (k_exact_gp_vjp_small) up to n <= tune.small_vjp
+static bool small_vjp(const gpmi_ctx *c, int n, int D, int k)
+{
+    return c->tune.small_vjp > 0 && n <= c->tune.small_vjp && n <= 256 && D <= GPMI_MAXD && k <= GPMI_VJP_KMAX;
+}
+
+extern "C" int gpmi_exact_gp_f_vjp_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
+                                       double jitter, const double *dZ, int k, int ldz, const double *dFbar, int ldfb, double *dF, int ldf,
+                                       double *dZbar, int ldzb, double *d_grad, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = exact_gp_vjp_check(n, ldx, D, alpha, k, ldz, ldfb, dF != nullptr, ldf, ldzb))) return rc;
+    if (!dX || !dZ || !dFbar || !dZbar || !d_grad || !d_info) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    if (small_vjp(c, n, D, k)) {
+        if ((rc = reserve_ws_small(c, n, 4))) return rc;
+        launch_exact_gp_vjp_small(c->stream, dX, n, ldx, p, jitter, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, c->W, alpha, ell,
+                                  n_ell, d_grad, d_info, c->d_info, nullptr);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    return exact_gp_vjp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_grad, d_info);
+}
+
+extern "C" int gpmi_exact_gp_f_vjp(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
+                                   double jitter, const double *Z, int k, int ldz, const double *Fbar, int ldfb, double *F, int ldf,
+                                   double *Zbar, int ldzb, double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = exact_gp_vjp_check(n, ldx, D, alpha, k, ldz, ldfb, F != nullptr, ldf, ldzb))) return rc;
+    if (!X || !Z || !Fbar || !Zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    hipStream_t s = c->stream;
+    const size_t nk = (size_t)n * k;
+    if (small_vjp(c, n, D, k)) {
+        // one launch of one workgroup; inputs in and results out through the pinned, device-mapped buffer:
+        // [info, flag | grad (1 + D) | F | Zbar | X | Z | Fbar]
+        const size_t o_g = 8, o_f = 16, o_zb = o_f + nk, o_x = o_zb + nk, o_z = o_x + (size_t)n * D, o_fb = o_z + nk;
+        if ((rc = pin_reserve(c, (o_fb + nk) * sizeof(double)))) return rc;
+        double *h = c->h_pin, *stage;
+        for (int d = 0; d < D; ++d) memcpy(h + o_x + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
+        for (int q = 0; q < k; ++q) {
+            memcpy(h + o_z + (size_t)q * n, Z + (size_t)q * ldz, (size_t)n * sizeof(double));
+            memcpy(h + o_fb + (size_t)q * n, Fbar + (size_t)q * ldfb, (size_t)n * sizeof(double));
+        }
+        if ((rc = scratch_buf(c, (size_t)n * (D + 2 * k) * sizeof(double), &stage))) return rc;
+        if ((rc = reserve_ws_small(c, n, 4))) return rc;
+        const int seq = ++c->pin_seq;
+        __atomic_store_n((int *)(h + 7), 0, __ATOMIC_RELEASE);   // armed before the launch: a stale word never reads as done
+        double *pd = c->h_pin_dev;
+        launch_exact_gp_vjp_small(s, pd + o_x, n, n, p, jitter, pd + o_z, k, n, pd + o_fb, n, F ? pd + o_f : nullptr, n, pd + o_zb, n, c->W,
+                                  alpha, ell, n_ell, pd + o_g, (int *)pd, c->d_info, stage, (int *)(pd + 7), seq);
+        HIPCHK(hipGetLastError());
+        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
+        for (int q = 0; q < k; ++q) {
+            if (F) memcpy(F + (size_t)q * ldf, h + o_f + (size_t)q * n, (size_t)n * sizeof(double));
+            memcpy(Zbar + (size_t)q * ldzb, h + o_zb + (size_t)q * n, (size_t)n * sizeof(double));
+        }
+        memcpy(grad, h + o_g, (size_t)(1 + n_ell) * sizeof(double));
+        return *(const int *)h;
+    }
+    // blocked chain: [X | Z | Fbar | F | Zbar | grad (65) | info] staged in device memory
+    double *d;
+    const size_t o_z = (size_t)n * D, o_fb = o_z + nk, o_f = o_fb + nk, o_zb = o_f + nk, o_g = o_zb + nk, o_i = o_g + 1 + GPMI_MAXD_BIG;
+    if ((rc = stage_buf(c, 0, (o_i + 1) * sizeof(double), &d))) return rc;
+    if ((rc = h2d_matrix(c, X, n, D, ldx, d))) return rc;
+    if ((rc = h2d_matrix(c, Z, n, k, ldz, d + o_z))) return rc;
+    if ((rc = h2d_matrix(c, Fbar, n, k, ldfb, d + o_fb))) return rc;
+    if ((rc = exact_gp_vjp_core(c, d, n, n, p, alpha, ell, n_ell, jitter, d + o_z, k, n, d + o_fb, n, F ? d + o_f : nullptr, n, d + o_zb,
+                                n, d + o_g, (int *)(d + o_i))))
+        return rc;
+    int info = 0;
+    if (F && (rc = d2h_matrix(c, d + o_f, (size_t)n, n, k, F, ldf))) return rc;
+    if ((rc = d2h_matrix(c, d + o_zb, (size_t)n, n, k, Zbar, ldzb))) return rc;
+    HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return info;
 }
 
 // G independent (alpha[g], rho[g], sigma[g]) points: value AND gradient of each, concurrently on the lanes -- what

@@ -38,6 +38,7 @@ struct gpmi_tuning {
     int small_m;          // partial factorisation of <= small_m rows: one workgroup, one launch (0: off)
     int small_ng1, small_ng; // value + gradient by one workgroup: one evaluation up to n <= small_ng1, several (a sampler's chains) up to small_ng (<= 256; 0: off)
     int grad_aug_n, grad_aug_ng;  // gpmi_logml_grad / _grid: K^-1 and K^-1 y from one augmented partial factorisation up to this n (0: off)
+    int small_vjp;           // gpmi_exact_gp_f_vjp[_dev]: one workgroup, one launch, up to n <= small_vjp (<= 256, D <= GPMI_MAXD, k <= GPMI_VJP_KMAX; 0: off)
     int small_gc;            // gpmi_gp_condition: one workgroup, one launch, up to n + m + 1 <= small_gc rows (0: off)
     int small_sd, small_sdb; // sample_derivs_batch: one workgroup per draw when n + m + 1 <= small_sd rows and at least small_sdb (n + m + 1)^2 / 400^2 draws (0: off)
     int small_n2, small_g2;  // grids of >= small_g2 (n / 1024)^2 + 2 points: one workgroup per point up to n <= small_n2 (every CU a problem of its own)
@@ -196,6 +197,14 @@ void launch_gp_condition_small(hipStream_t s, const double *t, int n, const doub
 // f = chol(K + diag_add I) z by one workgroup (n <= 256, D <= GPMI_MAXD); X, z / f, info_out may be host-mapped (stage != null)
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,
                            double *W, double *f, int *info_out, int *d_info_work, double *stage, int *done = nullptr, int seq = 0);
+// the vector-Jacobian product of f = chol(K + diag_add I) z for k <= GPMI_VJP_KMAX columns by one workgroup (n <= 256,
+// D <= GPMI_MAXD; workspace: 4 slices of small_ws_layout(n)).  Z, Fbar (inputs) and F (nullable), Zbar, grad (1 + n_ell), info_out
+// may be host-mapped (stage != null: n (D + 2 k) doubles of device scratch)
+#define GPMI_VJP_KMAX 8
+void launch_exact_gp_vjp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *Z, int k,
+                               int ldz, const double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb, double *W, double alpha,
+                               const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage,
+                               int *done = nullptr, int seq = 0);
 // rbf_cov_chol (L and dL/dl) for P <= 64 length-scales, one workgroup each, n <= 128 (workspace: 3 P slices of small_ws_layout(n));
 // x / Lout, dLout, info_out may be host-mapped (stage != null: P n doubles of device scratch)
 void launch_rbf_cov_chol_small(hipStream_t s, const double *x, int n, const double *ls, int P, double *Wall, double *Lout, double *dLout,
@@ -218,6 +227,8 @@ void launch_logml_finalize(hipStream_t s, const double *W, size_t ld, int n, int
 int trmv_lower_chunks(int n);
 void launch_trmv_lower(hipStream_t s, const double *L, size_t ldl, int n, const double *z, double *f,
                        double *part /* trmv_lower_chunks(n) * n doubles */);
+// w = L^T u for k columns (u: n x k, ldu; w: n x k, ldw), fixed-order reductions (k_trmv_lower_t)
+void launch_trmv_lower_t(hipStream_t s, const double *L, size_t ldl, int n, const double *u, size_t ldu, double *w, size_t ldw, int k);
 #ifdef GPMI_PROBES
 void launch_syrk_probe(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int m, int k);
 void launch_probe_mfma(hipStream_t s, const double *A, const double *B, double *D);

@@ -88,3 +88,33 @@ def exact_gp_f(x, l, z, ctx=None):
     c = ctx or default_context()
     x = np.asarray(x, float).reshape(len(z), -1)
     return c.exact_gp_f(x, 1.0, [l], z, 1e-10)   # covariance, factor and product stay on the device (gpmi_exact_gp_f)
+
+
+def exact_gp_log_prob_grad(x, y, l, sigma, z, ctx=None):
+    """(lp__, d lp__/d(l, sigma, z)) of models/exact_gp.stan -- the value/gradient pair NUTS asks for at every leapfrog step
+    of test_interpolate.R:31-36.  Conventions of fit_hyperparameters_log_prob_grad: `~` drops constants, the <lower=0>
+    Jacobians log l + log sigma are included:
+        lp = -z'z / 2 + 3 log l - 4 l - N log sigma - |y - f|^2 / (2 sigma^2) + log l + log sigma.
+    With ubar = (y - f) / sigma^2 the gradient is (ubar' (dL/dl) z + 4/l - 4, -N/sigma + |y - f|^2 / sigma^3 + 1/sigma,
+    L' ubar - z); ubar' (dL/dl) z and L' ubar come from the vector-Jacobian product of the transform
+    (gpmi_exact_gp_f_vjp).  A non-positive-definite proposal returns (-inf, NaN)."""
+    c = ctx or default_context()
+    z = np.asarray(z, float).ravel()
+    y = np.asarray(y, float).ravel()
+    n = z.size
+    x = np.asarray(x, float).reshape(n, -1)
+    try:
+        f = c.exact_gp_f(x, 1.0, [l], z, 1e-10)
+        r = y - f
+        ubar = r / (sigma * sigma)
+        _, zbar, g = c.exact_gp_f_vjp(x, 1.0, [l], z, ubar, 1e-10)
+    except NotPositiveDefinite:
+        return -math.inf, np.full(2 + n, math.nan)
+    rr = float(r @ r)
+    lp = (-0.5 * float(z @ z) + 3.0 * math.log(l) - 4.0 * l - n * math.log(sigma) - 0.5 * rr / (sigma * sigma)
+          + math.log(l) + math.log(sigma))
+    grad = np.empty(2 + n)
+    grad[0] = g[1] + 4.0 / l - 4.0
+    grad[1] = -n / sigma + rr / sigma ** 3 + 1.0 / sigma
+    grad[2:] = zbar - z
+    return lp, grad

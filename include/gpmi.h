@@ -88,7 +88,8 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * "nb_thr1024", "nb_thr512", "nb_thr256", "small_n", "small_n1", "small_m" (one-workgroup kernels for small
  * problems), "small_ng1", "small_ng" (value + gradient by one workgroup: one evaluation up to n <= small_ng1, several at once
  * up to n <= small_ng <= 256), "grad_aug_n", "grad_aug_ng" (value + gradient through ONE augmented partial factorisation up
- * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
+ * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_vjp" (gpmi_exact_gp_f_vjp[_dev] by
+ * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
  * n + m + 1 <= small_sd rows for at least small_sdb ((n + m + 1) / 400)^2 draws), "small_n2", "small_g2" (grids of at least small_g2 (n / 1024)^2 + 2 points run one workgroup per point up
  * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing"; unknown names return GPMI_EARG.  Switches of variants that
  * were measured and rejected ("lookahead", "syrk_order", "diag_waves", "gemm_variant", ...) exist in the probe
@@ -140,12 +141,30 @@ GPMI_API int gpmi_potrf_dev(gpmi_ctx *ctx, double *dA, int n, int lda, int *d_in
  * multi_normal_cholesky, models/fit_hyperparameters.stan:31). */
 GPMI_API int gpmi_trmv_lower(gpmi_ctx *ctx, const double *L, int n, int ldl, const double *z, double *f);
 GPMI_API int gpmi_trsv_lower(gpmi_ctx *ctx, const double *L, int n, int ldl, const double *b, double *z);
+/* w = L^T u: the transpose of gpmi_trmv_lower (z-adjoint of f = L z). */
+GPMI_API int gpmi_trmv_lower_t(gpmi_ctx *ctx, const double *L, int n, int ldl, const double *u, double *w);
 /* The latent exact GP's transform in ONE call, models/exact_gp.stan:17-25 (test_interpolate.R:31-36 runs it at N = 100):
  * f = cholesky_decompose(cov_exp_quad(X, alpha, ell) + jitter I) z -- covariance, factor and product stay on the
  * device, only z goes in and f comes out (n <= 256: one launch of one workgroup).  Returns 0, or the order of the first
  * non-positive leading minor (f is NaN then). */
 GPMI_API int gpmi_exact_gp_f(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
                     double jitter, const double *z, double *f);
+/* Vector-Jacobian product of that transform: what reverse-mode autodiff needs of models/exact_gp.stan:17-25 (z and l are
+ * parameters) and of models/heteroscedastic.stan:23-32 (one factor applied to two vectors, sigmaf = alpha a parameter) at every
+ * leapfrog step.  F = L Z for k columns (Z n x k, ldz), upstream adjoint Fbar (n x k, ldfb):
+ *   Zbar = L^T Fbar  (n x k, ldzb);
+ *   grad[0] = d/dalpha, grad[1 .. n_ell] = d/dell of sum(Fbar o F)  (1 + n_ell doubles);
+ *   F (nullable, ldf) = L Z, each column bit-identical to gpmi_exact_gp_f.
+ * With U = L^-T, B = Phi(Zbar Z^T) (lower triangle, halved diagonal): Sbar = sym(U B U^T), theta_bar = <Sbar, dK/dtheta>;
+ * about 4/3 n^3 flops on top of the value whatever the number of hyper-parameters.  D <= 64, any k (n <= 256, D <= 8, k <= 8:
+ * one launch of one workgroup), alpha > 0.  Returns 0, or the order of the first non-positive leading minor (every output NaN). */
+GPMI_API int gpmi_exact_gp_f_vjp(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
+                        double jitter, const double *Z, int k, int ldz, const double *Fbar, int ldfb, double *F /* nullable */,
+                        int ldf, double *Zbar, int ldzb, double *grad);
+/* the same with device-resident X, Z, Fbar, F, Zbar, grad and d_info (1 int), enqueued on the context's stream (ell: host) */
+GPMI_API int gpmi_exact_gp_f_vjp_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
+                            int n_ell, double jitter, const double *dZ, int k, int ldz, const double *dFbar, int ldfb,
+                            double *dF /* nullable */, int ldf, double *dZbar, int ldzb, double *d_grad, int *d_info);
 
 /* ---- marginal likelihood ---------------------------------------------- */
 

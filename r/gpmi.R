@@ -82,6 +82,11 @@ gp_interp_Lz <- function(l, z) {
 gp_exact_f <- function(X, alpha, rho, z, jitter = 1e-10)
   .Call("gpmi_R_exact_gp_f", as.matrix(X), alpha, as.double(rho), jitter, as.double(z))
 
+# its vector-Jacobian product (models/exact_gp.stan:17-25, models/heteroscedastic.stan:23-32): list(f, zbar = t(L) fbar,
+# grad = c(d/dalpha, d/drho...)) of sum(fbar * f); z and fbar are vectors or n x k matrices
+exact_gp_f_vjp <- function(X, alpha, rho, z, fbar, jitter = 1e-10)
+  .Call("gpmi_R_exact_gp_f_vjp", as.matrix(X), alpha, as.double(rho), jitter, z + 0.0, fbar + 0.0)
+
 # models/fit_hyperparameters.stan:18-32 as plain functions
 gp_log_marginal <- function(X, y, alpha, rho, sigma, jitter = 0)
   .Call("gpmi_R_logml", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)[1]

@@ -223,6 +223,29 @@ SEXP gpmi_R_exact_gp_f(SEXP X, SEXP alpha, SEXP ell, SEXP jitter, SEXP z)
     return out;
 }
 
+/* list(f, zbar, grad): the vector-Jacobian product of that transform -- what reverse-mode autodiff needs of
+ * models/exact_gp.stan:17-25 and models/heteroscedastic.stan:23-32 per leapfrog step.  z, fbar: n-vectors or n x k
+ * matrices (f, zbar come back with z's shape); grad = c(d/dalpha, d/dell...) of sum(fbar * f). */
+SEXP gpmi_R_exact_gp_f_vjp(SEXP X, SEXP alpha, SEXP ell, SEXP jitter, SEXP z, SEXP fbar)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), ne = Rf_length(ell);
+    need(is_real(X) && is_real(z) && is_real(fbar) && is_real(ell), "X, z, fbar and the length-scales must be double");
+    need(n > 0 && Rf_length(z) % n == 0 && Rf_length(z) > 0, "length(z) must be a multiple of nrow(X)");
+    need(Rf_length(fbar) == Rf_length(z), "fbar must have the shape of z");
+    need(ne == 1 || ne == D, "length-scale must have length 1 or ncol(X)");
+    int k = Rf_length(z) / n;
+    SEXP f = PROTECT(Rf_duplicate(z)), zb = PROTECT(Rf_duplicate(z)), g = PROTECT(Rf_allocVector(REALSXP, 1 + ne));
+    int rc = gpmi_exact_gp_f_vjp(ctx(), REAL(X), n, n, D, Rf_asReal(alpha), REAL(ell), ne, Rf_asReal(jitter), REAL(z), k, n,
+                                 REAL(fbar), n, REAL(f), n, REAL(zb), n, REAL(g));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3)), names = PROTECT(Rf_allocVector(STRSXP, 3));
+    SET_VECTOR_ELT(out, 0, f); SET_VECTOR_ELT(out, 1, zb); SET_VECTOR_ELT(out, 2, g);
+    SET_STRING_ELT(names, 0, Rf_mkChar("f")); SET_STRING_ELT(names, 1, Rf_mkChar("zbar")); SET_STRING_ELT(names, 2, Rf_mkChar("grad"));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(5);
+    check(rc);
+    return out;
+}
+
 /* list(value = c(logml, sum log L_ii, z'z), grad = c(d/dalpha, d/dell..., d/dsigma)): what Stan's
  * autodiff computes per leapfrog step for models/fit_hyperparameters.stan:18-32 */
 SEXP gpmi_R_logml_grad(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter)
