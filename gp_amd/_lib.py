@@ -26,6 +26,8 @@ SYMBOLS = (
     "gpmi_joint_logml", "gpmi_joint_logml_dev", "gpmi_joint_logml_grid_dev", "gpmi_rbf_cov_chol", "gpmi_gp_condition", "gpmi_sample_derivs", "gpmi_sample_derivs_batch",
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
     "gpmi_interp_free", "gpmi_logml_grad", "gpmi_logml_grad_grid",
+    "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
+    "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
     "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy",
     "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex",
 )
@@ -412,6 +414,82 @@ class Context:
     def interp_free(self):
         _chk(self._lib.gpmi_interp_free(self._h))
         self._itp_n = 0
+
+    # ---- reverse mode of the interpolated models ------------------------------
+    def _tri_vjp(self, fn, n, l, Z, Fbar, want_f):
+        one = np.ndim(Z) == 1
+        Zm = _mat(Z); Fb = _mat(Fbar)
+        if Zm.shape[0] != n or Fb.shape != Zm.shape:
+            raise GpmiError(-1, "Z and Fbar must be n x k with the table's n")
+        k = Zm.shape[1]; ld = max(n, 1)
+        F = np.empty((n, k), order="F") if want_f else None
+        Zb = np.empty((n, k), order="F"); lb = np.empty(1)
+        _chk(fn(self._h, _d(l), _p(Zm), k, ld, _p(Fb), ld, _p(F) if want_f else None, ld, _p(Zb), ld, _p(lb)))
+        if one:
+            F = F[:, 0] if want_f else None
+            Zb = Zb[:, 0]
+        return F, Zb, float(lb[0])
+
+    def approx_Lz_vjp(self, l, Z, Fbar, want_f=True):
+        """(F, Zbar, lbar) of F = approx_L(l) Z with upstream adjoint Fbar (models/cubic_interpolated_gp.hpp:6-32,38-73 under
+        reverse mode): Zbar = approx_L(l)^T Fbar, lbar = sum(Fbar * (dv/dl) Z).  Z and Fbar are 1-D (one column) or n x k;
+        F (None when want_f is False) and Zbar come back in the same shape.  F is approx_Lz's, bit for bit."""
+        return self._tri_vjp(self._lib.gpmi_approx_Lz_vjp, getattr(self, "_itp_n", 0), l, Z, Fbar, want_f)
+
+    def approx_Lz_vjp_dev(self, l, dZ_ptr, k, ldz, dFbar_ptr, ldfb, dF_ptr, ldf, dZbar_ptr, ldzb, dlbar_ptr):
+        """gpmi_approx_Lz_vjp_dev on device pointers (dF_ptr may be None); enqueued, not synchronised."""
+        _chk(self._lib.gpmi_approx_Lz_vjp_dev(self._h, _d(l), C.c_void_p(dZ_ptr), int(k), int(ldz), C.c_void_p(dFbar_ptr),
+                                              int(ldfb), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
+                                              C.c_void_p(dZbar_ptr), int(ldzb), C.c_void_p(dlbar_ptr)))
+
+    def interp_gp_build(self, x, lp, rho=1.0, jitter=1e-10):
+        """lookup = (Sigma_P \\ exact)^T of models/interpolated_gp.stan:9-27, the P exact factors of x built on the device."""
+        x = _vec(x); lp = _vec(lp)
+        _chk(self._lib.gpmi_interp_gp_build(self._h, _p(x), x.size, _p(lp), lp.size, _d(rho), _d(jitter)))
+        self._igp_n = x.size
+
+    def interp_gp_load(self, lp, Ls, rho=1.0, jitter=1e-10):
+        """The same table from caller-supplied exact factors (a sequence of P n x n matrices)."""
+        lp = _vec(lp)
+        n = np.asarray(Ls[0]).shape[0]
+        A = np.ascontiguousarray(np.stack([np.asfortranarray(np.asarray(a, dtype=np.float64)).ravel(order="F") for a in Ls]))
+        if A.shape != (lp.size, n * n):
+            raise GpmiError(-1, "lp and Ls disagree on the table shape")
+        _chk(self._lib.gpmi_interp_gp_load(self._h, _p(lp), lp.size, _d(rho), _d(jitter), _p(A), n, n))
+        self._igp_n = n
+
+    def interp_gp_L(self, l):
+        """L(l) = to_matrix(lookup * Kp(l), N, N) (interpolated_gp.stan:40-42), lower triangular."""
+        n = getattr(self, "_igp_n", 0)
+        out = np.empty((n, n), order="F")
+        _chk(self._lib.gpmi_interp_gp_L(self._h, _d(l), _p(out), max(n, 1)))
+        return out
+
+    def interp_gp_Lz(self, l, Z):
+        """F = L(l) Z (interpolated_gp.stan:44); Z 1-D or n x k."""
+        n = getattr(self, "_igp_n", 0)
+        one = np.ndim(Z) == 1
+        Zm = _mat(Z)
+        if Zm.shape[0] != n:
+            raise GpmiError(-1, "Z must have the table's n rows")
+        k = Zm.shape[1]; ld = max(n, 1)
+        F = np.empty((n, k), order="F")
+        _chk(self._lib.gpmi_interp_gp_Lz(self._h, _d(l), _p(Zm), k, ld, _p(F), ld))
+        return F[:, 0] if one else F
+
+    def interp_gp_Lz_vjp(self, l, Z, Fbar, want_f=True):
+        """(F, Zbar, lbar) of F = L(l) Z with upstream adjoint Fbar: Zbar = L(l)^T Fbar, lbar = sum(Fbar * (dL/dl) Z)."""
+        return self._tri_vjp(self._lib.gpmi_interp_gp_Lz_vjp, getattr(self, "_igp_n", 0), l, Z, Fbar, want_f)
+
+    def interp_gp_Lz_vjp_dev(self, l, dZ_ptr, k, ldz, dFbar_ptr, ldfb, dF_ptr, ldf, dZbar_ptr, ldzb, dlbar_ptr):
+        """gpmi_interp_gp_Lz_vjp_dev on device pointers (dF_ptr may be None); enqueued, not synchronised."""
+        _chk(self._lib.gpmi_interp_gp_Lz_vjp_dev(self._h, _d(l), C.c_void_p(dZ_ptr), int(k), int(ldz), C.c_void_p(dFbar_ptr),
+                                                 int(ldfb), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
+                                                 C.c_void_p(dZbar_ptr), int(ldzb), C.c_void_p(dlbar_ptr)))
+
+    def interp_gp_free(self):
+        _chk(self._lib.gpmi_interp_gp_free(self._h))
+        self._igp_n = 0
 
     def gp_condition(self, t, ts, y, alpha, l, s2, jitter, kindK, kindS, kindSS, flags=FULL):
         t = _vec(t); ts = _vec(ts); y = _vec(y)

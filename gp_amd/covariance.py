@@ -1,5 +1,6 @@
-"""Mirror of the Rcpp exports in covariance.cpp (rbf_cov_chol :9-47, approx_L :49-96) and of the Stan
-external function approx_Lz (models/cubic_interpolated_gp.hpp:38-73)."""
+"""Mirror of the Rcpp exports in covariance.cpp (rbf_cov_chol :9-47, approx_L :49-96), of the Stan
+external function approx_Lz (models/cubic_interpolated_gp.hpp:38-73) and of the GP-regression interpolation of
+models/interpolated_gp.stan:9-47."""
 import numpy as np
 
 from ._lib import default_context
@@ -47,6 +48,16 @@ def approx_Lz_grad(l, lp, Ls, dLdls, z, ctx=None):
     return c.approx_Lz_grad(l, z)
 
 
+def approx_Lz_vjp(l, lp, Ls, dLdls, z, fbar, ctx=None):
+    """(f, zbar, lbar): approx_Lz and its vector-Jacobian product under Stan's reverse mode
+    (models/cubic_interpolated_gp.hpp:6-32,38-73): zbar = approx_L(l)^T fbar, lbar = sum(fbar * (dv/dl) z).
+    z and fbar are vectors or n x k matrices."""
+    c = ctx or default_context()
+    k = _neighbours(l, lp)
+    c.interp_load([lp[k], lp[k + 1]], [Ls[k], Ls[k + 1]], [dLdls[k], dLdls[k + 1]])
+    return c.approx_Lz_vjp(l, z, fbar)
+
+
 class FactorInterpolator:
     """Device-resident table for repeated queries: what test_interpolate.R:9-19 builds with P calls of
     rbf_cov_chol and cubic_interpolated_gp.stan consumes once per leapfrog step."""
@@ -64,3 +75,31 @@ class FactorInterpolator:
 
     def Lz_grad(self, l, z):
         return self.ctx.approx_Lz_grad(l, z)
+
+    def Lz_vjp(self, l, z, fbar):
+        """(f, zbar, lbar) of f = L(l) z with upstream adjoint fbar (see approx_Lz_vjp)."""
+        return self.ctx.approx_Lz_vjp(l, z, fbar)
+
+
+class GPFactorInterpolator:
+    """The transformed data of models/interpolated_gp.stan:9-28 on the device: lookup = (Sigma_P \\ exact)^T with
+    Sigma_P = cov_exp_quad(lp, 1, rho) + jitter I and exact the P factors chol(cov_exp_quad(x, 1, lp[p]) + 1e-10 I),
+    kept as P lower triangles; L(l) = sum_p exp(-(l - lp_p)^2 / (2 rho^2)) M_p (:39-42).  Lives beside the Hermite
+    table of FactorInterpolator in the same context."""
+
+    def __init__(self, x, lp, rho=1.0, jitter=1e-10, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lp = np.asarray(lp, dtype=np.float64)
+        self.rho = float(rho)
+        self.jitter = float(jitter)
+        self.ctx.interp_gp_build(x, self.lp, self.rho, self.jitter)
+
+    def L(self, l):
+        return self.ctx.interp_gp_L(l)
+
+    def Lz(self, l, z):
+        return self.ctx.interp_gp_Lz(l, z)
+
+    def Lz_vjp(self, l, z, fbar):
+        """(f, zbar, lbar): f = L(l) z, zbar = L(l)^T fbar, lbar = sum(fbar * (dL/dl) z)."""
+        return self.ctx.interp_gp_Lz_vjp(l, z, fbar)

@@ -10,7 +10,9 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <vector>
 
 static thread_local char g_err[512] = "";
@@ -298,7 +300,7 @@ extern "C" int gpmi_destroy(gpmi_ctx *c)
         for (int l = 0; l < 7; ++l)
             if (c->lane[l]) gpmi_destroy(c->lane[l]);
         double *dev_bufs[] = {c->W, c->Fpack, c->itp_L, c->itp_dL, c->itp_part, c->d_out, c->d_fin, c->scratch,
-                              c->stage[0], c->stage[1], c->stage[2], c->stage[3]};
+                              c->stage[0], c->stage[1], c->stage[2], c->stage[3], c->igp_M, c->igp_aux};
         for (double *b : dev_bufs)
             if (b) (void)hipFree(b);
         if (c->d_info) (void)hipFree(c->d_info);
@@ -307,6 +309,7 @@ extern "C" int gpmi_destroy(gpmi_ctx *c)
         if (c->d_spar) (void)hipFree(c->d_spar);
         if (c->d_sinfo) (void)hipFree(c->d_sinfo);
         free(c->itp_lp);
+        free(c->igp_lp);
         if (c->ktimer) {  // per-kernel timing events (gpmi_set_option "kernel_timing")
             KTimer *k = (KTimer *)c->ktimer;
             for (int cat = 0; cat < 3; ++cat) {
@@ -1528,14 +1531,11 @@ static int interp_alloc(gpmi_ctx *c, const double *lp, int P, int n)
     return 0;
 }
 
-extern "C" int gpmi_interp_build(gpmi_ctx *c, const double *x, int n, const double *lp, int P)
+// the P factors L(lp[p]) and tangents dL/dl(lp[p]) of x (test_interpolate.R:9-19: P calls of rbf_cov_chol) into Lt / dLt
+// (P stacked ld x n matrices); 0 or the first non-zero factorisation status
+static int interp_factors(gpmi_ctx *c, const double *x, int n, const double *lp, int P, double *Lt, double *dLt, size_t ld)
 {
-    ENTER(c);
-    if (!x) return gpmi_fail(GPMI_EARG, "bad argument");
     int rc;
-    if ((rc = interp_alloc(c, lp, P, n))) return rc;
-    for (int p = 0; p < P; ++p)
-        if (!(lp[p] > 0.0)) return gpmi_fail(GPMI_EARG, "length-scales must be positive");
     double *dx;
     int *dinfo;
     if ((rc = stage_buf(c, 0, (size_t)n * sizeof(double) + (size_t)P * sizeof(int) + 64, &dx))) return rc;
@@ -1548,11 +1548,11 @@ extern "C" int gpmi_interp_build(gpmi_ctx *c, const double *x, int n, const doub
         const int per = P < 64 ? P : 64;
         if ((rc = reserve_ws_small(c, n, 3 * per))) return rc;
         if ((rc = reserve_small_par(c, per))) return rc;
-        const size_t msz = c->itp_ld * (size_t)n;
+        const size_t msz = ld * (size_t)n;
         for (int p0 = 0; p0 < P; p0 += per) {
             const int pc = (P - p0 < per) ? P - p0 : per;
-            launch_rbf_cov_chol_small(s, dx, n, lp + p0, pc, c->W, c->itp_L + (size_t)p0 * msz, c->itp_dL + (size_t)p0 * msz, msz,
-                                      c->itp_ld, dinfo + p0, c->d_sinfo, nullptr);
+            launch_rbf_cov_chol_small(s, dx, n, lp + p0, pc, c->W, Lt + (size_t)p0 * msz, dLt + (size_t)p0 * msz, msz,
+                                      ld, dinfo + p0, c->d_sinfo, nullptr);
         }
         std::vector<int> info(P, 0);
         HIPCHK(hipMemcpyAsync(info.data(), dinfo, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1586,8 +1586,8 @@ extern "C" int gpmi_interp_build(gpmi_ctx *c, const double *x, int n, const doub
         rc = rbf_cov_chol_core(lc, dx, n, lp[p], &Lc, &S, &ldd);
         if (rc) break;
         hipStream_t s = lc->stream;
-        launch_copy_matrix(s, Lc, (size_t)ldd, c->itp_L + (size_t)p * c->itp_ld * n, c->itp_ld, n, n, 0);
-        launch_copy_matrix(s, S, (size_t)ldd, c->itp_dL + (size_t)p * c->itp_ld * n, c->itp_ld, n, n, 0);
+        launch_copy_matrix(s, Lc, (size_t)ldd, Lt + (size_t)p * ld * n, ld, n, n, 0);
+        launch_copy_matrix(s, S, (size_t)ldd, dLt + (size_t)p * ld * n, ld, n, n, 0);
         if (hipMemcpyAsync(dinfo + p, lc->d_info, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
             rc = gpmi_fail(GPMI_EHIP, "info copy failed");
     }
@@ -1600,6 +1600,17 @@ extern "C" int gpmi_interp_build(gpmi_ctx *c, const double *x, int n, const doub
     for (int p = 0; p < P; ++p)
         if (info[p]) return info[p];
     return 0;
+}
+
+extern "C" int gpmi_interp_build(gpmi_ctx *c, const double *x, int n, const double *lp, int P)
+{
+    ENTER(c);
+    if (!x) return gpmi_fail(GPMI_EARG, "bad argument");
+    int rc;
+    if ((rc = interp_alloc(c, lp, P, n))) return rc;
+    for (int p = 0; p < P; ++p)
+        if (!(lp[p] > 0.0)) return gpmi_fail(GPMI_EARG, "length-scales must be positive");
+    return interp_factors(c, x, n, lp, P, c->itp_L, c->itp_dL, c->itp_ld);
 }
 
 extern "C" int gpmi_interp_load(gpmi_ctx *c, const double *lp, int P, const double *Ls, const double *dLdls,
@@ -1722,6 +1733,276 @@ extern "C" int gpmi_approx_Lz_grad(gpmi_ctx *c, double l, const double *z, doubl
     ENTER(c);
     if (!dfdl) return gpmi_fail(GPMI_EARG, "bad argument");
     return approx_Lz_host(c, l, z, f, dfdl);
+}
+
+// ---- reverse mode of the interpolated models (interp_kernels.hip) ----------------------------
+// models/cubic_interpolated_gp.hpp:6-32,38-73 (the Hermite table above) and models/interpolated_gp.stan:9-47 (the
+// GP-regression lookup below): F = A(l) Z (nullable), Zbar = A(l)^T Fbar, lbar = sum(Fbar o (dA/dl) Z) in one pass over
+// the stored triangles.
+enum { TRI_HERMITE = 0, TRI_GP = 1 };
+
+static int tri_check(gpmi_ctx *c, int model, double l, const double *Z, int k, int ldz, const double *Fb, int ldfb,
+                     const double *F, int ldf, const double *Zb, int ldzb, const double *lbar, int vjp)
+{
+    const int n = model == TRI_GP ? c->igp_n : c->itp_n;
+    if (model == TRI_GP ? !c->igp_M : !c->itp_L)
+        return gpmi_fail(GPMI_EARG, model == TRI_GP ? "no GP-regression table (gpmi_interp_gp_build / gpmi_interp_gp_load first)"
+                                                    : "no interpolation table (gpmi_interp_build / gpmi_interp_load first)");
+    if (!std::isfinite(l)) return gpmi_fail(GPMI_EARG, "l must be finite");
+    if (k < 1) return gpmi_fail(GPMI_EARG, "k must be >= 1 (got %d)", k);
+    if (!Z || ldz < n) return gpmi_fail(GPMI_EARG, "bad Z");
+    if (F && ldf < n) return gpmi_fail(GPMI_EARG, "bad F");
+    if (vjp && (!Fb || ldfb < n || !Zb || ldzb < n || !lbar)) return gpmi_fail(GPMI_EARG, "bad Fbar, Zbar or lbar");
+    if (!vjp && !F) return gpmi_fail(GPMI_EARG, "bad F");
+    return 0;
+}
+
+// enqueue the pass on device (or, one-launch sizes only, host-mapped) pointers
+static int tri_core(gpmi_ctx *c, int model, double l, const double *dZ, int k, int ldz, const double *dFb, int ldfb, double *dF,
+                    int ldf, double *dZb, int ldzb, double *dlbar)
+{
+    const int n = model == TRI_GP ? c->igp_n : c->itp_n;
+    int rc;
+    double *ws = nullptr;
+    if (!tri_vjp_one_launch(n, k) && (rc = scratch_buf(c, tri_vjp_ws_doubles(n, k) * sizeof(double), &ws))) return rc;
+    if (model == TRI_GP) {
+        launch_gp_vjp(c->stream, c->igp_M, c->igp_ld, n, c->igp_P, c->igp_aux, c->igp_rho, l, dZ, ldz, dFb, ldfb, k, dF, ldf,
+                      dZb, ldzb, dlbar, ws);
+    } else {
+        const int t = interp_interval(c, l);
+        const size_t msz = c->itp_ld * n;
+        launch_hermite_vjp(c->stream, c->itp_L + t * msz, c->itp_L + (t + 1) * msz, c->itp_dL + t * msz, c->itp_dL + (t + 1) * msz,
+                           c->itp_ld, n, c->itp_lp[t], c->itp_lp[t + 1], l, dZ, ldz, dFb, ldfb, k, dF, ldf, dZb, ldzb, dlbar, ws);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// host buffers: n <= GPMI_TRI_SMALL_N and k <= GPMI_TRI_KG (the reference's N = 100) is one launch with Z, Fbar in and
+// F, Zbar, lbar out through the pinned, device-mapped buffer; larger problems are staged in device memory
+static int tri_host(gpmi_ctx *c, int model, double l, const double *Z, int k, int ldz, const double *Fb, int ldfb, double *F,
+                    int ldf, double *Zb, int ldzb, double *lbar)
+{
+    const int vjp = Fb != nullptr;
+    int rc;
+    if ((rc = tri_check(c, model, l, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, lbar, vjp))) return rc;
+    const int n = model == TRI_GP ? c->igp_n : c->itp_n;
+    const size_t nk = (size_t)n * k;
+    // [Z | Fbar | F | Zbar | lbar], n x k each, leading dimension n
+    const size_t oZ = 0, oFb = nk, oF = 2 * nk, oZb = 3 * nk, oL = 4 * nk, need = (4 * nk + 8) * sizeof(double);
+    double *base;
+    bool pinned = tri_vjp_one_launch(n, k);
+    if (pinned) {
+        if ((rc = pin_reserve(c, need))) return rc;
+        base = c->h_pin;
+        for (int j = 0; j < k; ++j) {
+            memcpy(base + oZ + (size_t)j * n, Z + (size_t)j * ldz, (size_t)n * sizeof(double));
+            if (vjp) memcpy(base + oFb + (size_t)j * n, Fb + (size_t)j * ldfb, (size_t)n * sizeof(double));
+        }
+    } else {
+        if ((rc = stage_buf(c, 0, need, &base))) return rc;
+        HIPCHK(hipMemcpy2DAsync(base + oZ, (size_t)n * sizeof(double), Z, (size_t)ldz * sizeof(double), (size_t)n * sizeof(double),
+                                k, hipMemcpyHostToDevice, c->stream));
+        if (vjp)
+            HIPCHK(hipMemcpy2DAsync(base + oFb, (size_t)n * sizeof(double), Fb, (size_t)ldfb * sizeof(double),
+                                    (size_t)n * sizeof(double), k, hipMemcpyHostToDevice, c->stream));
+    }
+    double *d = pinned ? c->h_pin_dev : base;
+    if ((rc = tri_core(c, model, l, d + oZ, k, n, vjp ? d + oFb : nullptr, n, F ? d + oF : nullptr, n, vjp ? d + oZb : nullptr, n,
+                       vjp ? d + oL : nullptr)))
+        return rc;
+    if (pinned) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+    } else {
+        double *h = nullptr;
+        if ((rc = pin_reserve(c, need))) return rc;
+        h = c->h_pin;
+        HIPCHK(hipMemcpyAsync(h + oF, base + oF, (2 * nk + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    const double *h = c->h_pin;
+    for (int j = 0; j < k; ++j) {
+        if (F) memcpy(F + (size_t)j * ldf, h + oF + (size_t)j * n, (size_t)n * sizeof(double));
+        if (vjp) memcpy(Zb + (size_t)j * ldzb, h + oZb + (size_t)j * n, (size_t)n * sizeof(double));
+    }
+    if (vjp) *lbar = h[oL];
+    return 0;
+}
+
+extern "C" int gpmi_approx_Lz_vjp(gpmi_ctx *c, double l, const double *Z, int k, int ldz, const double *Fbar, int ldfb,
+                                  double *F, int ldf, double *Zbar, int ldzb, double *lbar)
+{
+    ENTER(c);
+    if (!Fbar) return gpmi_fail(GPMI_EARG, "bad Fbar");
+    return tri_host(c, TRI_HERMITE, l, Z, k, ldz, Fbar, ldfb, F, ldf, Zbar, ldzb, lbar);
+}
+
+extern "C" int gpmi_approx_Lz_vjp_dev(gpmi_ctx *c, double l, const double *dZ, int k, int ldz, const double *dFbar, int ldfb,
+                                      double *dF, int ldf, double *dZbar, int ldzb, double *d_lbar)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = tri_check(c, TRI_HERMITE, l, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_lbar, 1))) return rc;
+    return tri_core(c, TRI_HERMITE, l, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_lbar);
+}
+
+// ---- GP-regression lookup table (interpolated_gp.stan:9-27) ----
+extern "C" int gpmi_interp_gp_free(gpmi_ctx *c)
+{
+    ENTER(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->igp_M) (void)hipFree(c->igp_M);
+    if (c->igp_aux) (void)hipFree(c->igp_aux);
+    free(c->igp_lp);
+    c->igp_M = c->igp_aux = c->igp_lp = nullptr;
+    c->igp_P = c->igp_n = 0;
+    return 0;
+}
+
+// Sigma_P = cov_exp_quad(lp, 1, rho) + jitter I, factored on the host by partial-pivot LU (Stan's mdivide_left); the
+// table (P stacked ld x n matrices) and the device copies of lp, LU and the pivot order allocated
+static int interp_gp_alloc(gpmi_ctx *c, const double *lp, int P, int n, double rho, double jitter)
+{
+    if (!lp || n <= 0) return gpmi_fail(GPMI_EARG, "bad argument");
+    if (P < 1 || P > GPMI_GP_PMAX) return gpmi_fail(GPMI_EARG, "the GP-regression table takes 1 ... %d knots (got P = %d)", GPMI_GP_PMAX, P);
+    if (!(rho > 0.0) || !std::isfinite(rho) || !std::isfinite(jitter)) return gpmi_fail(GPMI_EARG, "rho must be positive and jitter finite");
+    for (int p = 0; p < P; ++p)
+        if (!std::isfinite(lp[p])) return gpmi_fail(GPMI_EARG, "knots must be finite");
+    std::vector<double> lu((size_t)P * P);
+    std::vector<int> perm(P);
+    for (int p = 0; p < P; ++p) {
+        perm[p] = p;
+        for (int q = 0; q < P; ++q) {
+            const double d = lp[p] - lp[q];
+            lu[(size_t)p * P + q] = exp(-(d * d) / (2 * rho * rho)) + (p == q ? jitter : 0.0);
+        }
+    }
+    for (int col = 0; col < P; ++col) {  // Doolittle with row interchanges: the largest |pivot| of the column
+        int piv = col;
+        for (int r = col + 1; r < P; ++r)
+            if (fabs(lu[(size_t)r * P + col]) > fabs(lu[(size_t)piv * P + col])) piv = r;
+        if (!(lu[(size_t)piv * P + col] != 0.0) || !std::isfinite(lu[(size_t)piv * P + col]))
+            return gpmi_fail(GPMI_EARG, "Sigma_P is singular (pivot %d)", col);
+        if (piv != col) {
+            for (int q = 0; q < P; ++q) std::swap(lu[(size_t)piv * P + q], lu[(size_t)col * P + q]);
+            std::swap(perm[piv], perm[col]);
+        }
+        for (int r = col + 1; r < P; ++r) {
+            const double m = lu[(size_t)r * P + col] / lu[(size_t)col * P + col];
+            lu[(size_t)r * P + col] = m;
+            for (int q = col + 1; q < P; ++q) lu[(size_t)r * P + q] -= m * lu[(size_t)col * P + q];
+        }
+    }
+    int rc = gpmi_interp_gp_free(c);
+    if (rc) return rc;
+    c->igp_ld = (size_t)((n + 1) & ~1);
+    const size_t aux = (size_t)P + (size_t)P * P + (size_t)P;  // perm: one double slot per int is more than enough
+    if (hipMalloc((void **)&c->igp_M, (size_t)P * c->igp_ld * n * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&c->igp_aux, aux * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        gpmi_interp_gp_free(c);
+        return gpmi_fail(GPMI_ENOMEM, "GP-regression table of %d x %d x %d does not fit", P, n, n);
+    }
+    c->igp_lp = (double *)malloc(sizeof(double) * P);
+    if (!c->igp_lp) return gpmi_fail(GPMI_ENOMEM, "host allocation failed");
+    memcpy(c->igp_lp, lp, sizeof(double) * P);
+    HIPCHK(hipMemcpy(c->igp_aux, lp, (size_t)P * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->igp_aux + P, lu.data(), (size_t)P * P * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->igp_aux + P + (size_t)P * P, perm.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice));
+    c->igp_P = P;
+    c->igp_n = n;
+    c->igp_rho = rho;
+    return 0;
+}
+
+// the exact factors in c->igp_M become the lookup triangles, in place
+static int interp_gp_finish(gpmi_ctx *c)
+{
+    const int P = c->igp_P;
+    launch_gp_lookup(c->stream, c->igp_M, c->igp_ld, c->igp_n, P, c->igp_aux + P, (const int *)(c->igp_aux + P + (size_t)P * P));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int gpmi_interp_gp_build(gpmi_ctx *c, const double *x, int n, const double *lp, int P, double rho, double jitter)
+{
+    ENTER(c);
+    if (!x) return gpmi_fail(GPMI_EARG, "bad argument");
+    int rc;
+    if ((rc = interp_gp_alloc(c, lp, P, n, rho, jitter))) return rc;
+    for (int p = 0; p < P; ++p)
+        if (!(lp[p] > 0.0)) {
+            gpmi_interp_gp_free(c);
+            return gpmi_fail(GPMI_EARG, "length-scales must be positive");
+        }
+    double *dL;  // the tangents the factor builds produce are not needed here
+    if (hipMalloc((void **)&dL, (size_t)P * c->igp_ld * n * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        gpmi_interp_gp_free(c);
+        return gpmi_fail(GPMI_ENOMEM, "GP-regression table build of %d x %d x %d does not fit", P, n, n);
+    }
+    rc = interp_factors(c, x, n, lp, P, c->igp_M, dL, c->igp_ld);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(dL);
+    if (rc) {
+        gpmi_interp_gp_free(c);
+        return rc;
+    }
+    return interp_gp_finish(c);
+}
+
+extern "C" int gpmi_interp_gp_load(gpmi_ctx *c, const double *lp, int P, double rho, double jitter, const double *Ls, int n, int ld)
+{
+    ENTER(c);
+    if (!Ls || ld < n) return gpmi_fail(GPMI_EARG, "bad argument");
+    int rc;
+    if ((rc = interp_gp_alloc(c, lp, P, n, rho, jitter))) return rc;
+    for (int p = 0; p < P; ++p)
+        HIPCHK(hipMemcpy2DAsync(c->igp_M + (size_t)p * c->igp_ld * n, c->igp_ld * sizeof(double), Ls + (size_t)p * ld * n,
+                                (size_t)ld * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, c->stream));
+    return interp_gp_finish(c);
+}
+
+extern "C" int gpmi_interp_gp_L(gpmi_ctx *c, double l, double *out, int ldo)
+{
+    ENTER(c);
+    if (!c->igp_M) return gpmi_fail(GPMI_EARG, "no GP-regression table (gpmi_interp_gp_build / gpmi_interp_gp_load first)");
+    const int n = c->igp_n;
+    if (!out || ldo < n) return gpmi_fail(GPMI_EARG, "bad argument");
+    if (!std::isfinite(l)) return gpmi_fail(GPMI_EARG, "l must be finite");
+    int rc;
+    double *dout;
+    const size_t ldd = (size_t)((n + 1) & ~1);
+    if ((rc = stage_buf(c, 1, ldd * n * sizeof(double), &dout))) return rc;
+    launch_gp_blend(c->stream, c->igp_M, c->igp_ld, n, c->igp_P, c->igp_aux, c->igp_rho, l, dout, ldd);
+    HIPCHK(hipGetLastError());
+    if ((rc = d2h_matrix(c, dout, ldd, n, n, out, ldo))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int gpmi_interp_gp_Lz(gpmi_ctx *c, double l, const double *Z, int k, int ldz, double *F, int ldf)
+{
+    ENTER(c);
+    return tri_host(c, TRI_GP, l, Z, k, ldz, nullptr, 0, F, ldf, nullptr, 0, nullptr);
+}
+
+extern "C" int gpmi_interp_gp_Lz_vjp(gpmi_ctx *c, double l, const double *Z, int k, int ldz, const double *Fbar, int ldfb,
+                                     double *F, int ldf, double *Zbar, int ldzb, double *lbar)
+{
+    ENTER(c);
+    if (!Fbar) return gpmi_fail(GPMI_EARG, "bad Fbar");
+    return tri_host(c, TRI_GP, l, Z, k, ldz, Fbar, ldfb, F, ldf, Zbar, ldzb, lbar);
+}
+
+extern "C" int gpmi_interp_gp_Lz_vjp_dev(gpmi_ctx *c, double l, const double *dZ, int k, int ldz, const double *dFbar, int ldfb,
+                                         double *dF, int ldf, double *dZbar, int ldzb, double *d_lbar)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = tri_check(c, TRI_GP, l, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_lbar, 1))) return rc;
+    return tri_core(c, TRI_GP, l, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_lbar);
 }
 
 // ---- gradient of the log marginal likelihood ---------------------------

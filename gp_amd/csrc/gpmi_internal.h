@@ -95,6 +95,13 @@ struct gpmi_ctx {
     double *itp_lp;          // host copy of the P length-scales
     int itp_P, itp_n;
     size_t itp_ld;
+    // GP-regression lookup table (gpmi_interp_gp_*): P stacked lower triangles, ld itp-style, beside the Hermite table
+    double *igp_M;
+    double *igp_aux;         // device: lp (P) | LU of Sigma_P (P x P) | perm (P ints)
+    double *igp_lp;          // host copy of the P knots
+    int igp_P, igp_n;
+    size_t igp_ld;
+    double igp_rho;
     gpmi_ctx *lane[7];
     hipEvent_t evFork, evJoin;
     // Dispatch streams on distinct command-processor pipes (root context), found by probing:
@@ -146,6 +153,29 @@ void launch_hermite_mv(hipStream_t s, const double *L1, const double *L2, const 
                        double *dfdl /* nullable: (dv/dl) z, the reverse-mode partial of approx_Lz */);
 int hermite_mv_chunks(int n);
 #define GPMI_HMV_SMALL_N 256    // approx_Lz up to this n: one launch, z read straight from (possibly host-mapped) memory
+// ---- reverse mode of the interpolated models (interp_kernels.hip) ----
+// One pass over T stored lower triangles M_t (A = sum a_t M_t, B = sum b_t M_t): F = A Z (nullable), Zbar = A^T Fbar,
+// lbar = sum_c Fbar[:,c]^T (B Z[:,c]); Fbar == nullptr: F alone.  k columns in groups of GPMI_TRI_KG; n <= GPMI_TRI_SMALL_N
+// with k <= GPMI_TRI_KG is one launch of one workgroup (Z, Fbar, F, Zbar, lbar may be host-mapped), otherwise ws holds
+// tri_vjp_ws_doubles(n, k) doubles.  Every reduction has a fixed order.
+#define GPMI_TRI_KG 8
+#define GPMI_TRI_SMALL_N 256
+#define GPMI_GP_PMAX 64          // knots of the GP-regression lookup
+bool tri_vjp_one_launch(int n, int k);
+size_t tri_vjp_ws_doubles(int n, int k);
+// Hermite model: the four triangles of the interval [x1, x2]; F bit-identical to launch_hermite_mv
+void launch_hermite_vjp(hipStream_t s, const double *L1, const double *L2, const double *D1, const double *D2, size_t ld, int n,
+                        double x1, double x2, double l, const double *Z, int ldz, const double *Fb, int ldfb, int k, double *F,
+                        int ldf, double *Zb, int ldzb, double *lbar, double *ws);
+// GP-regression model: P lookup triangles (stride ld * n), weights exp(-(l - lp_p)^2 / (2 rho^2)); lp on the device
+void launch_gp_vjp(hipStream_t s, const double *M, size_t ld, int n, int P, const double *lp, double rho, double l,
+                   const double *Z, int ldz, const double *Fb, int ldfb, int k, double *F, int ldf, double *Zb, int ldzb,
+                   double *lbar, double *ws);
+void launch_gp_blend(hipStream_t s, const double *M, size_t ld, int n, int P, const double *lp, double rho, double l,
+                     double *out, size_t ldo);
+// in place: the P stacked exact factors become lookup = (Sigma_P \ exact)^T; lu: row-major P x P partial-pivot LU
+// factors, perm: the row taken at each step (device)
+void launch_gp_lookup(hipStream_t s, double *M, size_t ld, int n, int P, const double *lu, const int *perm);
 void launch_phi_mask(hipStream_t s, double *B, size_t ld, int n); // keep upper, halve diag, zero strict lower
 
 // ---- kernel launchers (chol_kernels.hip) -----------------------------------

@@ -15,6 +15,7 @@
 
 namespace {
 #include "se_device.h"
+#include "interp_device.h"
 
 constexpr int TILE = 64;
 
@@ -259,15 +260,8 @@ inline bool vec_ok(const void *p, size_t ld) { return ((uintptr_t)p % 16 == 0) &
 // ---------------------------------------------------------------------------
 // Cholesky-factor interpolation (covariance.cpp:49-96, cubic_interpolated_gp.hpp:38-73):
 // cubic Hermite blend of two factors and their length-scale tangents, element by element, in
-// the reference's operation order.  HBM-bound: 4 matrices read (lower triangles).
+// the reference's operation order (hermite(): interp_device.h).  HBM-bound: 4 matrices read (lower triangles).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double hermite(double y1, double y2, double k1, double k2, double dx, double t)
-{
-    const double a = k1 * dx - (y2 - y1);
-    const double b = -k2 * dx + (y2 - y1);
-    return (1 - t) * y1 + t * y2 + t * (1 - t) * (a * (1 - t) + b * t);
-}
-
 __global__ __launch_bounds__(256) void k_hermite_blend(const double *__restrict__ L1, const double *__restrict__ L2,
                                                        const double *__restrict__ D1, const double *__restrict__ D2,
                                                        size_t ld, int n, double dx, double t,

@@ -118,3 +118,43 @@ def exact_gp_log_prob_grad(x, y, l, sigma, z, ctx=None):
     grad[1] = -n / sigma + rr / sigma ** 3 + 1.0 / sigma
     grad[2:] = zbar - z
     return lp, grad
+
+
+def _interpolated_log_prob_grad(value, vjp, lo, hi, y, l, sigma, z):
+    """lp__ and its gradient in (l, sigma, z) for a latent f = L(l) z with l <lower=lo, upper=hi>: the conventions of
+    exact_gp_log_prob_grad with the Jacobian of the bounded transform, log(l - lo) + log(hi - l) - log(hi - lo)."""
+    z = np.asarray(z, float).ravel()
+    y = np.asarray(y, float).ravel()
+    n = z.size
+    if not (lo < l < hi) or not sigma > 0:
+        return -math.inf, np.full(2 + n, math.nan)
+    f = value(l, z)
+    r = y - f
+    ubar = r / (sigma * sigma)
+    _, zbar, lbar = vjp(l, z, ubar, False)
+    rr = float(r @ r)
+    lp = (-0.5 * float(z @ z) + 3.0 * math.log(l) - 4.0 * l - n * math.log(sigma) - 0.5 * rr / (sigma * sigma)
+          + math.log(l - lo) + math.log(hi - l) - math.log(hi - lo) + math.log(sigma))
+    grad = np.empty(2 + n)
+    grad[0] = lbar + 3.0 / l - 4.0 + 1.0 / (l - lo) - 1.0 / (hi - l)
+    grad[1] = -n / sigma + rr / sigma ** 3 + 1.0 / sigma
+    grad[2:] = zbar - z
+    return lp, grad
+
+
+def cubic_interpolated_gp_log_prob_grad(interp, y, l, sigma, z):
+    """(lp__, d lp__/d(l, sigma, z)) of models/cubic_interpolated_gp.stan (f = approx_Lz(l, lp, Ls, dLdls, z), l in
+    [min(lp), max(lp)], :17) for a FactorInterpolator `interp`:
+        lp = -z'z/2 + 3 log l - 4 l - N log sigma - |y - f|^2 / (2 sigma^2) + log(l - lo) + log(hi - l) - log(hi - lo) + log sigma.
+    With ubar = (y - f) / sigma^2 the gradient is (lbar(ubar) + 3/l - 4 + 1/(l - lo) - 1/(hi - l),
+    -N/sigma + |y - f|^2/sigma^3 + 1/sigma, Zbar(ubar) - z), lbar and Zbar from gpmi_approx_Lz_vjp.  l outside the open
+    interval returns (-inf, NaN)."""
+    lp_ = np.asarray(interp.lp, float)
+    return _interpolated_log_prob_grad(interp.ctx.approx_Lz, interp.ctx.approx_Lz_vjp, float(lp_.min()), float(lp_.max()), y, l, sigma, z)
+
+
+def interpolated_gp_log_prob_grad(interp, y, l, sigma, z):
+    """The same for models/interpolated_gp.stan (f = L(l) z with L(l) = to_matrix(lookup * Kp(l)), l in
+    [min(lp), max(lp)], :32) for a GPFactorInterpolator `interp`; lbar and Zbar from gpmi_interp_gp_Lz_vjp."""
+    lp_ = np.asarray(interp.lp, float)
+    return _interpolated_log_prob_grad(interp.ctx.interp_gp_Lz, interp.ctx.interp_gp_Lz_vjp, float(lp_.min()), float(lp_.max()), y, l, sigma, z)

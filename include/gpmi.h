@@ -264,6 +264,33 @@ GPMI_API int gpmi_approx_Lz_dev(gpmi_ctx *ctx, double l, const double *dz, doubl
 GPMI_API int gpmi_approx_Lz_grad(gpmi_ctx *ctx, double l, const double *z, double *f, double *dfdl);
 GPMI_API int gpmi_approx_Lz_grad_dev(gpmi_ctx *ctx, double l, const double *dz, double *df, double *ddfdl);
 GPMI_API int gpmi_interp_free(gpmi_ctx *ctx);
+/* cubic_interpolated_gp.hpp:6-32,38-73 under reverse mode: F = v(l) Z, Zbar = v(l)^T Fbar,
+ * lbar = sum(Fbar o (dv/dl) Z); table from gpmi_interp_build / gpmi_interp_load.  Z, Fbar, F, Zbar: n x k, column-major.
+ * One pass over the interval's four triangles (k <= 8 columns per pass; n <= 256, k <= 8: one launch); every column of F
+ * is bit-identical to gpmi_approx_Lz.  Errors (GPMI_EARG): no table, k < 1, non-finite l. */
+GPMI_API int gpmi_approx_Lz_vjp(gpmi_ctx *ctx, double l, const double *Z, int k, int ldz, const double *Fbar, int ldfb,
+                       double *F /* nullable */, int ldf, double *Zbar, int ldzb, double *lbar);
+/* the same on device pointers (d_lbar: 1 double), enqueued on the context's stream */
+GPMI_API int gpmi_approx_Lz_vjp_dev(gpmi_ctx *ctx, double l, const double *dZ, int k, int ldz, const double *dFbar, int ldfb,
+                           double *dF /* nullable */, int ldf, double *dZbar, int ldzb, double *d_lbar);
+/* The GP-regression interpolation of models/interpolated_gp.stan:9-47 (rho = 1, jitter = 1e-10 in the reference):
+ * transformed data lookup = (Sigma_P \ exact)^T with Sigma_P = cov_exp_quad(lp, 1, rho) + jitter I (partial-pivot LU, P <= 64)
+ * and exact the P factors chol(cov_exp_quad(x, 1, lp[p]) + 1e-10 I), kept on the device as P lower triangles M_p beside
+ * (not in place of) the Hermite table; L(l) = sum_p w_p M_p with w_p = exp(-(l - lp_p)^2 / (2 rho^2)).
+ * gpmi_interp_gp_build factors x as gpmi_interp_build does and returns its status codes; gpmi_interp_gp_load takes the P
+ * stacked n x n factors.  The Lz calls follow gpmi_approx_Lz_vjp (lbar from w'_p = -(l - lp_p) / rho^2 w_p); F of
+ * gpmi_interp_gp_Lz and of gpmi_interp_gp_Lz_vjp are bit-identical.  Errors (GPMI_EARG): no table, P > 64, singular
+ * Sigma_P, k < 1, non-finite l. */
+GPMI_API int gpmi_interp_gp_build(gpmi_ctx *ctx, const double *x, int n, const double *lp, int P, double rho, double jitter);
+GPMI_API int gpmi_interp_gp_load(gpmi_ctx *ctx, const double *lp, int P, double rho, double jitter,
+                        const double *Ls /* P stacked n x n exact factors */, int n, int ld);
+GPMI_API int gpmi_interp_gp_L(gpmi_ctx *ctx, double l, double *out, int ldo);
+GPMI_API int gpmi_interp_gp_Lz(gpmi_ctx *ctx, double l, const double *Z, int k, int ldz, double *F, int ldf);
+GPMI_API int gpmi_interp_gp_Lz_vjp(gpmi_ctx *ctx, double l, const double *Z, int k, int ldz, const double *Fbar, int ldfb,
+                          double *F /* nullable */, int ldf, double *Zbar, int ldzb, double *lbar);
+GPMI_API int gpmi_interp_gp_Lz_vjp_dev(gpmi_ctx *ctx, double l, const double *dZ, int k, int ldz, const double *dFbar, int ldfb,
+                              double *dF /* nullable */, int ldf, double *dZbar, int ldzb, double *d_lbar);
+GPMI_API int gpmi_interp_gp_free(gpmi_ctx *ctx);
 
 /* ---- GP posterior (value / derivative) -------------------------------- */
 

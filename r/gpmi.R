@@ -77,6 +77,30 @@ gp_interp_Lz <- function(l, z) {
   stopifnot(!is.null(.gpmi_interp_n), length(z) == .gpmi_interp_n)
   .Call("gpmi_R_approx_Lz", l, numeric(0), NULL, NULL, as.double(z))
 }
+# reverse mode of approx_Lz (models/cubic_interpolated_gp.hpp:6-32,38-73): list(f, zbar = t(approx_L(l)) fbar,
+# lbar = sum(fbar * (dv/dl) z)); z and fbar are vectors or n x k matrices
+approx_Lz_vjp <- function(l, lp, Ls, dLdls, z, fbar)
+  .Call("gpmi_R_approx_Lz_vjp", l, as.double(lp), Ls, dLdls, z + 0.0, fbar + 0.0, 0L)
+gp_interp_Lz_vjp <- function(l, z, fbar) {
+  stopifnot(!is.null(.gpmi_interp_n))
+  .Call("gpmi_R_approx_Lz_vjp", l, numeric(0), NULL, NULL, z + 0.0, fbar + 0.0, as.integer(.gpmi_interp_n))
+}
+# the GP-regression interpolation of models/interpolated_gp.stan:9-47: lookup = (Sigma_P \ exact)^T built on the device,
+# f = L(l) z with L(l) = to_matrix(lookup * Kp(l), N, N), and its reverse mode list(f, zbar, lbar)
+.gpmi_interp_gp_n <- NULL
+gp_interp_gp_build <- function(x, lp, rho = 1, jitter = 1e-10) {
+  .Call("gpmi_R_interp_gp_build", as.double(x), as.double(lp), rho, jitter)
+  .gpmi_interp_gp_n <<- length(x)
+  invisible(NULL)
+}
+gp_interp_gp_Lz <- function(l, z) {
+  stopifnot(!is.null(.gpmi_interp_gp_n))
+  .Call("gpmi_R_interp_gp_Lz", l, z + 0.0, as.integer(.gpmi_interp_gp_n))
+}
+gp_interp_gp_Lz_vjp <- function(l, z, fbar) {
+  stopifnot(!is.null(.gpmi_interp_gp_n))
+  .Call("gpmi_R_interp_gp_Lz_vjp", l, z + 0.0, fbar + 0.0, as.integer(.gpmi_interp_gp_n))
+}
 
 # models/exact_gp.stan:17-25: f = cholesky_decompose(cov_exp_quad(x, alpha, rho) + 1e-10 I) * z, fused on the device
 gp_exact_f <- function(X, alpha, rho, z, jitter = 1e-10)

@@ -193,6 +193,60 @@ SEXP gpmi_R_approx_Lz_grad(SEXP l, SEXP lp, SEXP Ls, SEXP dLdls, SEXP z)
     return out;
 }
 
+/* list(f, zbar, lbar) of F = A(l) Z with upstream adjoint Fbar (z, fbar: n-vectors or n x k matrices; f and zbar come
+ * back with z's shape) for the Hermite table (model 0) or the GP-regression table (model 1) */
+static SEXP tri_vjp(int model, double l, SEXP z, SEXP fbar, int n)
+{
+    need(is_real(z) && is_real(fbar) && Rf_length(fbar) == Rf_length(z), "z and fbar must be double and of one shape");
+    need(n > 0 && Rf_length(z) % n == 0 && Rf_length(z) > 0, "length(z) must be a multiple of the table's order");
+    int k = Rf_length(z) / n;
+    SEXP f = PROTECT(Rf_duplicate(z)), zb = PROTECT(Rf_duplicate(z)), lb = PROTECT(Rf_allocVector(REALSXP, 1));
+    int rc = (model ? gpmi_interp_gp_Lz_vjp : gpmi_approx_Lz_vjp)(ctx(), l, REAL(z), k, n, REAL(fbar), n, REAL(f), n, REAL(zb),
+                                                                  n, REAL(lb));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3)), names = PROTECT(Rf_allocVector(STRSXP, 3));
+    SET_VECTOR_ELT(out, 0, f); SET_VECTOR_ELT(out, 1, zb); SET_VECTOR_ELT(out, 2, lb);
+    SET_STRING_ELT(names, 0, Rf_mkChar("f")); SET_STRING_ELT(names, 1, Rf_mkChar("zbar")); SET_STRING_ELT(names, 2, Rf_mkChar("lbar"));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(5);
+    check(rc);
+    return out;
+}
+
+/* list(f, zbar = t(approx_L(l)) fbar, lbar = sum(fbar * (dv/dl) z)): models/cubic_interpolated_gp.hpp:6-32,38-73 under
+ * reverse mode; with Ls = NULL the table of gpmi_R_interp_build is used (n: its order) */
+SEXP gpmi_R_approx_Lz_vjp(SEXP l, SEXP lp, SEXP Ls, SEXP dLdls, SEXP z, SEXP fbar, SEXP n_table)
+{
+    int n = Rf_asInteger(n_table);
+    if (!Rf_isNull(Ls)) check(load_pair(Rf_asReal(l), lp, Ls, dLdls, &n));
+    return tri_vjp(0, Rf_asReal(l), z, fbar, n);
+}
+
+/* the GP-regression table of models/interpolated_gp.stan:9-27: lookup = (Sigma_P \ exact)^T on the device */
+SEXP gpmi_R_interp_gp_build(SEXP x, SEXP lp, SEXP rho, SEXP jitter)
+{
+    need(is_real(x) && is_real(lp), "x and lp must be double");
+    check(gpmi_interp_gp_build(ctx(), REAL(x), Rf_length(x), REAL(lp), Rf_length(lp), Rf_asReal(rho), Rf_asReal(jitter)));
+    return R_NilValue;
+}
+
+/* f = L(l) z, L(l) = to_matrix(lookup * Kp(l), N, N) (models/interpolated_gp.stan:39-44) */
+SEXP gpmi_R_interp_gp_Lz(SEXP l, SEXP z, SEXP n_table)
+{
+    int n = Rf_asInteger(n_table);
+    need(is_real(z) && n > 0 && Rf_length(z) % n == 0 && Rf_length(z) > 0, "z must be double with a multiple of n entries");
+    SEXP f = PROTECT(Rf_duplicate(z));
+    int rc = gpmi_interp_gp_Lz(ctx(), Rf_asReal(l), REAL(z), Rf_length(z) / n, n, REAL(f), n);
+    UNPROTECT(1);
+    check(rc);
+    return f;
+}
+
+/* list(f, zbar = t(L(l)) fbar, lbar = sum(fbar * (dL/dl) z)) of the same */
+SEXP gpmi_R_interp_gp_Lz_vjp(SEXP l, SEXP z, SEXP fbar, SEXP n_table)
+{
+    return tri_vjp(1, Rf_asReal(l), z, fbar, Rf_asInteger(n_table));
+}
+
 /* c(logml, sum log L_ii, z'z): one evaluation of models/fit_hyperparameters.stan:18-32 */
 SEXP gpmi_R_logml(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter)
 {
