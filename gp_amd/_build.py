@@ -6,7 +6,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["se_kernels.hip", "chol_kernels.hip", "interp_kernels.hip", "gpmi_api.hip"]
+SOURCES = ["se_kernels.hip", "chol_kernels.hip", "interp_kernels.hip", "latent_kernels.hip", "gpmi_api.hip"]
 LIB = os.path.join(CSRC, "libgpmi.so")
 PROBES_LIB = os.path.join(CSRC, "libgpmi_probes.so")  # -DGPMI_PROBES: tools/ only, never loaded by the product
 
@@ -27,6 +27,7 @@ def needs_build(lib=LIB):
         os.path.join(CSRC, "factor16.h"),
         os.path.join(CSRC, "se_device.h"),
         os.path.join(CSRC, "interp_device.h"),
+        os.path.join(CSRC, "latent_device.h"),
         os.path.join(HERE, "..", "include", "gpmi.h"),
     ]
     return any(os.path.getmtime(d) > t for d in deps)

@@ -21,7 +21,7 @@ SYMBOLS = (
     "gpmi_set_stream", "gpmi_reset_stream", "gpmi_sync", "gpmi_reserve", "gpmi_set_option",
     "gpmi_se_cov", "gpmi_se_cov_dev", "gpmi_deriv_cov", "gpmi_deriv_cov_dev", "gpmi_deriv_elem",
     "gpmi_joint_cov", "gpmi_potrf", "gpmi_potrf_dev", "gpmi_trmv_lower", "gpmi_trsv_lower", "gpmi_exact_gp_f",
-    "gpmi_trmv_lower_t", "gpmi_exact_gp_f_vjp", "gpmi_exact_gp_f_vjp_dev",
+    "gpmi_trmv_lower_t", "gpmi_exact_gp_f_vjp", "gpmi_exact_gp_f_vjp_dev", "gpmi_latent_gp_lp_grad", "gpmi_latent_gp_lp_grad_dev",
     "gpmi_logml", "gpmi_logml_dev", "gpmi_logml_grid", "gpmi_logml_grid_dev", "gpmi_logml_grid_ard", "gpmi_logml_grid_ard_dev",
     "gpmi_joint_logml", "gpmi_joint_logml_dev", "gpmi_joint_logml_grid_dev", "gpmi_rbf_cov_chol", "gpmi_gp_condition", "gpmi_sample_derivs", "gpmi_sample_derivs_batch",
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
@@ -127,6 +127,18 @@ def _mat(X):
     if X.ndim == 1:
         X = X.reshape(-1, 1)
     return np.asfortranarray(X)
+
+
+LIK_FAMILIES = {"normal": 0, "bernoulli_logit": 1, "normal_logsd": 2}   # GPMI_LIK_*
+
+
+def lik_family(family):
+    """GPMI_LIK_* of a family name; integers pass through (the library rejects unknown ones)."""
+    if isinstance(family, str):
+        if family not in LIK_FAMILIES:
+            raise GpmiError(-1, "unknown likelihood family %r" % (family,))
+        return LIK_FAMILIES[family]
+    return int(family)
 
 
 def _kind(k):
@@ -287,6 +299,37 @@ class Context:
         if one:
             return F[:, 0], Zb[:, 0], g
         return F, Zb, g
+
+    def latent_gp_lp_grad(self, X, alpha, ell, Z, family, Y, sigma=None, jitter=1e-10, want_f=True, want_fbar=False,
+                          raise_not_pd=True):
+        """The likelihood part of a latent exact-GP model's lp__ and its gradient with one factorisation
+        (gpmi_latent_gp_lp_grad): F = chol(cov_exp_quad(X, alpha, ell) + jitter I) Z, the head `family` ("normal",
+        "bernoulli_logit", "normal_logsd") on F against the columns of Y (n or n x m), Fbar = d lik / d F, Zbar = L^T Fbar and
+        grad = (d/dalpha, d/dell...) of lik.  Returns a dict: lik, dlik_dsigma, F, Fbar (None unless asked for), Zbar, grad,
+        info.  Z is 1-D or n x 1 (n x 2 for "normal_logsd"); F, Fbar and Zbar come back in Z's shape.  sigma is required by
+        "normal" alone.  Not positive definite: raises NotPositiveDefinite, or with raise_not_pd=False returns the NaN outputs
+        and info = the minor's order."""
+        X = _mat(X); ell = _vec(ell)
+        n, D = X.shape
+        one = np.ndim(Z) == 1
+        Zm = _mat(Z); Ym = _mat(Y)
+        if Zm.shape[0] != n or Ym.shape[0] != n:
+            raise GpmiError(-1, "X, Z and Y disagree on N")
+        k = Zm.shape[1]; m = Ym.shape[1]
+        fam = lik_family(family)
+        if fam == LIK_FAMILIES["normal"] and sigma is None:
+            raise GpmiError(-1, "the normal head needs sigma")
+        F = np.empty((n, k), order="F") if want_f else None
+        Fb = np.empty((n, k), order="F") if want_fbar else None
+        Zb = np.empty((n, k), order="F"); g = np.empty(1 + ell.size); out = np.empty(2)
+        ld = max(n, 1)
+        info = _chk(self._lib.gpmi_latent_gp_lp_grad(self._h, _p(X), n, ld, D, _d(alpha), _p(ell), int(ell.size), _d(jitter), _p(Zm), k,
+                                                     ld, fam, _p(Ym), m, ld, _d(0.0 if sigma is None else sigma), _p(out),
+                                                     _p(F) if want_f else None, ld, _p(Fb) if want_fbar else None, ld, _p(Zb), ld,
+                                                     _p(g)), allow_info=not raise_not_pd)
+        sq = (lambda A: None if A is None else (A[:, 0] if one else A))
+        return {"lik": float(out[0]), "dlik_dsigma": float(out[1]), "F": sq(F), "Fbar": sq(Fb), "Zbar": sq(Zb), "grad": g,
+                "info": int(info)}
 
     # ---- marginal likelihood -------------------------------------------------
     def logml(self, X, y, alpha, ell, sigma, jitter=0.0):
@@ -545,6 +588,17 @@ class Context:
                                                int(ell.size), _d(jitter), C.c_void_p(dZ_ptr), int(k), int(ldz),
                                                C.c_void_p(dFbar_ptr), int(ldfb), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
                                                C.c_void_p(dZbar_ptr), int(ldzb), C.c_void_p(dgrad_ptr), C.c_void_p(dinfo_ptr)))
+
+    def latent_gp_lp_grad_dev(self, dX_ptr, n, ldx, D, alpha, ell, jitter, dZ_ptr, k, ldz, family, dY_ptr, m, ldy, sigma, dout_ptr,
+                              dF_ptr, ldf, dFbar_ptr, ldfb, dZbar_ptr, ldzb, dgrad_ptr, dinfo_ptr):
+        """gpmi_latent_gp_lp_grad_dev on device pointers (dF_ptr and dFbar_ptr may be None); enqueued, not synchronised."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_latent_gp_lp_grad_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), _d(alpha), _p(ell),
+                                                  int(ell.size), _d(jitter), C.c_void_p(dZ_ptr), int(k), int(ldz), lik_family(family),
+                                                  C.c_void_p(dY_ptr), int(m), int(ldy), _d(0.0 if sigma is None else sigma),
+                                                  C.c_void_p(dout_ptr), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
+                                                  C.c_void_p(dFbar_ptr) if dFbar_ptr else None, int(ldfb), C.c_void_p(dZbar_ptr),
+                                                  int(ldzb), C.c_void_p(dgrad_ptr), C.c_void_p(dinfo_ptr)))
 
     def logml_grid_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, rho, sigma, jitter, dout_ptr, dinfo_ptr):
         a = _vec(alpha); r = _vec(rho); s = _vec(sigma)

@@ -24,6 +24,7 @@
 // multi_normal_cholesky (:31), L*z (models/exact_gp.stan:25).
 #include "gpmi_internal.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -56,6 +57,7 @@ __device__ __host__ constexpr int fp_inv(int jb) { return 28 + jb; }
 
 #include "factor16.h"
 #include "se_device.h"
+#include "latent_device.h"
 
 #ifdef GPMI_PROBES  // the 5-wave / 3-barrier diagonal-block kernel of round 1 (diag_waves = 5): A/B material only
 // ---------------------------------------------------------------------------
@@ -2633,31 +2635,59 @@ struct VjpSmallEll {
     double ell[GPMI_MAXD];
 };
 constexpr int VJP_KMAX = GPMI_VJP_KMAX;
-__global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
-                                                            const double *__restrict__ Z, int k, int ldz, const double *__restrict__ Fb,
-                                                            int ldfb, double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
-                                                            double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                            VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out,
-                                                            int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
+// HEAD: Fbar is not an input but the adjoint of a likelihood head evaluated on F (gpmi_latent_gp_lp_grad): F is formed
+// unconditionally, thread = row evaluates latent_head_row (k <= 2), lik and d lik / d sigma are reduced in a fixed order into
+// out[0..1], and Fb (nullable) receives the Fbar the sweep then uses.  Everything else is the same statement for both instances.
+template <bool HEAD>
+__device__ __forceinline__ void exact_gp_vjp_small_body(const double *__restrict__ X, int n, int ldx, const SeParams &p,
+                                                        double diag_add, const double *__restrict__ Z, int k, int ldz,
+                                                        std::conditional_t<HEAD, double, const double> *__restrict__ Fb, int ldfb,
+                                                        double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
+                                                        double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
+                                                        const VjpSmallEll &el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                        int *info_w, const ExpC &ec, double *__restrict__ stage, int *done, int seq,
+                                                        const LatentHead &lh, double *__restrict__ out)
 {
     GPMI_SMALL_LDS
-    const int tid = threadIdx.x;
-    if (stage) {   // host-mapped X, Z, Fbar: one coalesced pass into device memory
+    constexpr int KM = HEAD ? 2 : VJP_KMAX;   // columns the per-column loops unroll for (the heads have k <= 2)
+    // HEAD: at its phase boundaries below the thread index passes through an empty asm, so that what later phases derive from it
+    // (row and column addresses the compiler would otherwise form early) is not kept live, i.e. spilled, across the head's
+    // exp / log1p: with these the instance needs the scratch of the plain one (3824 B per lane), without them 56 B more
+    int tid = threadIdx.x;
+    if (stage) {   // host-mapped X, Z, Fbar (HEAD: Y): one coalesced pass into device memory
         const int nx = n * p.D, nz = n * k;
-        for (int e = tid; e < nx + 2 * nz; e += 256) {
-            if (e < nx) {
-                const int d = e / n, i = e - d * n;
-                stage[e] = X[(size_t)i + (size_t)d * ldx];
-            } else {
-                const int e2 = e - nx, src = e2 < nz ? e2 : e2 - nz, c = src / n, i = src - c * n;
-                stage[e] = e2 < nz ? Z[(size_t)i + (size_t)c * ldz] : Fb[(size_t)i + (size_t)c * ldfb];
+        if constexpr (HEAD) {
+            const int ny = n * lh.m;
+            for (int e = tid; e < nx + nz + ny; e += 256) {
+                if (e < nx) {
+                    const int d = e / n, i = e - d * n;
+                    stage[e] = X[(size_t)i + (size_t)d * ldx];
+                } else if (e < nx + nz) {
+                    const int c = (e - nx) / n, i = e - nx - c * n;
+                    stage[e] = Z[(size_t)i + (size_t)c * ldz];
+                } else {
+                    const int c = (e - nx - nz) / n, i = e - nx - nz - c * n;
+                    stage[e] = lh.Y[(size_t)i + (size_t)c * lh.ldy];
+                }
             }
+            __syncthreads();
+        } else {
+            for (int e = tid; e < nx + 2 * nz; e += 256) {
+                if (e < nx) {
+                    const int d = e / n, i = e - d * n;
+                    stage[e] = X[(size_t)i + (size_t)d * ldx];
+                } else {
+                    const int e2 = e - nx, src = e2 < nz ? e2 : e2 - nz, c = src / n, i = src - c * n;
+                    stage[e] = e2 < nz ? Z[(size_t)i + (size_t)c * ldz] : Fb[(size_t)i + (size_t)c * ldfb];
+                }
+            }
+            __syncthreads();
+            Fb = stage + nx + nz;
+            ldfb = n;
         }
-        __syncthreads();
         X = stage;
         Z = stage + nx;
-        Fb = stage + nx + nz;
-        ldx = ldz = ldfb = n;
+        ldx = ldz = n;
     }
     if (tid == 0) *info_w = 0;
     SmallSe se;
@@ -2693,6 +2723,7 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
     __syncthreads();
     small_potrf_partial<true>(smem, s_F, s_aux, W, ld, n, n, n, info_w, false, U);
     __syncthreads();
+    if constexpr (HEAD) asm volatile("" : "+v"(tid));
     const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // the packed factors are no longer needed: s_F holds the scaled coordinates, Fbar (then W) and Z, k n doubles each
     double *xg = s_F, *s_w = s_F + 2048, *s_z = s_F + 4096;
@@ -2703,11 +2734,12 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
     for (int e = tid; e < n * k; e += 256) {
         const int c = e / n, i = e - c * n;
         s_z[e] = Z[(size_t)i + (size_t)c * ldz];
-        s_w[e] = Fb[(size_t)i + (size_t)c * ldfb];
+        if constexpr (!HEAD) s_w[e] = Fb[(size_t)i + (size_t)c * ldfb];
     }
     __syncthreads();
     // F, one column at a time: the loop of k_exact_gp_small (row sums in column order)
-    if (F)
+    if constexpr (HEAD) asm volatile("" : "+v"(tid));
+    if (HEAD || F)
         for (int c = 0; c < k; ++c) {
             if (tid < n) {
                 const int i = tid;
@@ -2724,13 +2756,41 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
                     for (int q = 0; q < 16; ++q)
                         if (j0 + q <= i) acc = fma(u[q], zc[j0 + q], acc);
                 }
-                F[(size_t)i + (size_t)c * ldf] = info ? __builtin_nan("") : acc;
+                if (F) F[(size_t)i + (size_t)c * ldf] = info ? __builtin_nan("") : acc;
+                if constexpr (HEAD) s_w[c * n + i] = acc;   // the head reads its row of F here and leaves Fbar
             }
         }
-    // W = L^T Fbar: thread = column j of L, all k columns at once
-    double wj[VJP_KMAX];
+    if constexpr (HEAD) {
+        // the head on this thread's row, Fbar into LDS where the sweep reads it; lik and d lik / d sigma by a butterfly inside
+        // every wave and the four wave sums added in wave order
+        double red0 = 0.0, red1 = 0.0, fb0 = 0.0, fb1 = 0.0;
+        if (tid < n) {
+            // Y: the copy made at entry when staged (derived here rather than kept live across the factorisation)
+            const LatentHead hd{lh.family, stage ? stage + n * (p.D + k) : lh.Y, lh.m, stage ? n : lh.ldy, lh.sigma, lh.log_sigma};
+            latent_head_row(hd, s_w[tid], k > 1 ? s_w[n + tid] : 0.0, hd.Y + tid, red0, red1, fb0, fb1);
+            for (int c = 0; c < k; ++c) {
+                const double v = c ? fb1 : fb0;
+                s_w[c * n + tid] = v;
+                if (Fb) Fb[(size_t)tid + (size_t)c * ldfb] = info ? __builtin_nan("") : v;
+            }
+        }
 #pragma unroll
-    for (int c = 0; c < VJP_KMAX; ++c) wj[c] = 0.0;
+        for (int off = 32; off > 0; off >>= 1) {
+            red0 += __shfl_xor(red0, off, 64);
+            red1 += __shfl_xor(red1, off, 64);
+        }
+        if ((tid & 63) == 0) {
+            s_aux[(tid >> 6) * 2] = red0;
+            s_aux[(tid >> 6) * 2 + 1] = red1;
+        }
+        __syncthreads();   // (also: every row of Fbar is in s_w)
+        if (tid < 2) out[tid] = info ? __builtin_nan("") : ((s_aux[tid] + s_aux[2 + tid]) + s_aux[4 + tid]) + s_aux[6 + tid];
+        asm volatile("" : "+v"(tid));
+    }
+    // W = L^T Fbar: thread = column j of L, all k columns at once
+    double wj[KM];
+#pragma unroll
+    for (int c = 0; c < KM; ++c) wj[c] = 0.0;
     if (tid < n) {
         const int j = tid;
         const double *col = W + (size_t)j * ld;
@@ -2742,25 +2802,26 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
             for (int q = 0; q < 8; ++q)
                 if (i0 + q < n)
 #pragma unroll
-                    for (int c = 0; c < VJP_KMAX; ++c)
+                    for (int c = 0; c < KM; ++c)
                         if (c < k) wj[c] = fma(l8[q], s_w[c * n + i0 + q], wj[c]);
         }
     }
     __syncthreads();   // every thread has read Fbar
     if (tid < n)
 #pragma unroll
-        for (int c = 0; c < VJP_KMAX; ++c)
+        for (int c = 0; c < KM; ++c)
             if (c < k) {
                 s_w[c * n + tid] = wj[c];
                 Zb[(size_t)tid + (size_t)c * ldzb] = info ? __builtin_nan("") : wj[c];
             }
     __syncthreads();
+    if constexpr (HEAD) asm volatile("" : "+v"(tid));
     // V = U Phi(W Z^T): thread = row i, columns from the last to the first, one running suffix sum per column of Z
     if (tid < n) {
         const int i = tid;
-        double P[VJP_KMAX];
+        double P[KM];
 #pragma unroll
-        for (int c = 0; c < VJP_KMAX; ++c) P[c] = 0.0;
+        for (int c = 0; c < KM; ++c) P[c] = 0.0;
         for (int j1 = n; j1 > 0; j1 -= 16) {
             double u[16];
 #pragma unroll
@@ -2774,7 +2835,7 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
                 if (j < 0) break;
                 double v = 0.0;
 #pragma unroll
-                for (int c = 0; c < VJP_KMAX; ++c)
+                for (int c = 0; c < KM; ++c)
                     if (c < k) {
                         const double t = u[q] * s_w[c * n + j];
                         v = fma(s_z[c * n + j], fma(0.5, t, P[c]), v);
@@ -2786,6 +2847,7 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
         }
     }
     __syncthreads();
+    if constexpr (HEAD) asm volatile("" : "+v"(tid));
     // [V U] [U V]^T tile by tile (lower tiles), contracted where it is produced; the columns of [V U] left of the tile's first
     // column are skipped (U's rows there are zero in V U^T; U V^T needs them all)
     double acc[1 + GPMI_MAXD];
@@ -2880,6 +2942,31 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
         *info_out = info;
     }
     small_signal_done(done, seq);
+}
+
+__global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
+                                                            const double *__restrict__ Z, int k, int ldz, const double *__restrict__ Fb,
+                                                            int ldfb, double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
+                                                            double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
+                                                            VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                            int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
+{
+    exact_gp_vjp_small_body<false>(X, n, ldx, p, diag_add, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, W, R, ld, alpha, el, n_ell,
+                                   grad, info_out, info_w, ec, stage, done, seq, LatentHead{}, nullptr);
+}
+
+// forward product, likelihood head, its adjoint and the reverse sweep in one launch (gpmi_latent_gp_lp_grad, n <= 256, k <= 2):
+// out[0] = lik, out[1] = d lik / d sigma; Fb (nullable) receives Fbar
+__global__ __launch_bounds__(256, 2) void k_latent_gp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
+                                                         const double *__restrict__ Z, int k, int ldz, LatentHead lh,
+                                                         double *__restrict__ out, double *__restrict__ Fb, int ldfb,
+                                                         double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
+                                                         double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
+                                                         VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out, int *info_w,
+                                                         ExpC ec, double *__restrict__ stage, int *done, int seq)
+{
+    exact_gp_vjp_small_body<true>(X, n, ldx, p, diag_add, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, W, R, ld, alpha, el, n_ell, grad, info_out,
+                                  info_w, ec, stage, done, seq, lh, out);
 }
 
 // rbf_cov_chol (covariance.cpp:9-47) by ONE workgroup for n <= 128 (test_interpolate.R:5 runs it at N = 100, P = 10 times):
@@ -3339,6 +3426,7 @@ static void small_lds_attr()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gp_condition_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_vjp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_latent_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_cov_chol_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     const int gbytes = SMALL_GRAD_LDS_DOUBLES * (int)sizeof(double);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_grad_small), hipFuncAttributeMaxDynamicSharedMemorySize, gbytes);
@@ -4061,6 +4149,22 @@ void launch_exact_gp_vjp_small(hipStream_t s, const double *X, int n, int ldx, c
     for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
     hipLaunchKernelGGL(k_exact_gp_vjp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, Fb,
                        ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
+}
+
+// the same with a likelihood head between the product and the sweep (k <= 2); stage != null: n (D + k + m) doubles
+void launch_latent_gp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *Z, int k,
+                            int ldz, const LatentHead &lh, double *out, double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb,
+                            double *W, double alpha, const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work,
+                            double *stage, int *done, int seq)
+{
+    size_t ld, stride;
+    small_ws_layout(n, &ld, &stride);
+    small_lds_attr();
+    VjpSmallEll el;
+    for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
+    hipLaunchKernelGGL(k_latent_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, lh, out,
+                       Fb, ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done,
+                       seq);
 }
 
 // P <= 64 length-scales, one workgroup each (n <= 128); Wall: 3 P slices of small_ws_layout(n)

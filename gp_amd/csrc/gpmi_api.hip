@@ -2503,16 +2503,21 @@ static int exact_gp_vjp_reserve(gpmi_ctx *c, int n, int D, int k)
     const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
     double *b;
     if ((rc = stage_buf(c, 2, ldu * (3 * (size_t)n + 1) * sizeof(double), &b))) return rc;
-    const size_t vec = (size_t)n + GRAD_NS_MAX + ntiles * grad_ns(D) + (size_t)trmv_lower_chunks(n) * n + (size_t)k * nsch * n;
+    // (the last three terms: F, Fbar and the head's block partials of gpmi_latent_gp_lp_grad)
+    const size_t vec = (size_t)n + GRAD_NS_MAX + ntiles * grad_ns(D) + (size_t)trmv_lower_chunks(n) * n + (size_t)k * nsch * n +
+                       2 * (size_t)k * n + 2 * (size_t)latent_head_blocks(n);
     if ((rc = stage_buf(c, 1, vec * sizeof(double), &b))) return rc;
     return scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &b);
 }
 
 // The chain, enqueued on c->stream: device X (ldx), Z (ldz), Fbar (ldfb); F (nullable, ldf), Zbar (ldzb), grad (1 + n_ell)
 // and *d_info written.  F is formed exactly as gpmi_exact_gp_f's blocked path forms it (same factorisation, same mat-vec).
+// head != nullptr (gpmi_latent_gp_lp_grad): Fbar is not read but produced, by the likelihood head on F, into dFbOut (nullable:
+// a workspace slice) and d_out[0..1] = (lik, d lik / d sigma); the launches of the plain call are the same with head == nullptr.
 static int exact_gp_vjp_core(gpmi_ctx *c, const double *dX, int n, int ldx, const SeParams &p, double alpha, const double *ell,
                              int n_ell, double jitter, const double *dZ, int k, int ldz, const double *dFb, int ldfb, double *dF,
-                             int ldf, double *dZb, int ldzb, double *d_grad, int *d_info)
+                             int ldf, double *dZb, int ldzb, double *d_grad, int *d_info, const LatentHead *head = nullptr,
+                             double *dFbOut = nullptr, double *d_out = nullptr)
 {
     int rc;
     if ((rc = exact_gp_vjp_reserve(c, n, p.D, k))) return rc;
@@ -2527,7 +2532,21 @@ static int exact_gp_vjp_core(gpmi_ctx *c, const double *dX, int n, int ldx, cons
     // K and L exactly as gpmi_exact_gp_f (the packed factors for the solve are taken from L afterwards)
     launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, jitter, 1, c->W, ld);
     if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, c->d_info, nullptr))) return rc;
-    if (dF)
+    if (head) {   // F always (the head reads it), then Fbar = d lik / d F
+        double *hF = spart + (size_t)k * nsch * n, *hFb = hF + (size_t)k * n, *hpart = hFb + (size_t)k * n;
+        if (!dF) {
+            dF = hF;
+            ldf = n;
+        }
+        if (!dFbOut) {
+            dFbOut = hFb;
+            ldfb = n;
+        }
+        for (int q = 0; q < k; ++q) launch_trmv_lower(s, c->W, ld, n, dZ + (size_t)q * ldz, dF + (size_t)q * ldf, trpart);
+        launch_latent_head(s, dF, (size_t)ldf, n, k, *head, dFbOut, (size_t)ldfb, hpart, d_out, c->d_info);
+        dFb = dFbOut;
+        if (dF == hF) dF = nullptr;   // (nothing of the caller's to overwrite with NaN below)
+    } else if (dF)
         for (int q = 0; q < k; ++q) launch_trmv_lower(s, c->W, ld, n, dZ + (size_t)q * ldz, dF + (size_t)q * ldf, trpart);
     launch_trmv_lower_t(s, c->W, ld, n, dFb, (size_t)ldfb, dZb, (size_t)ldzb, k);   // Zbar = W = L^T Fbar
     // U = L^-T
@@ -2643,6 +2662,116 @@ extern "C" int gpmi_exact_gp_f_vjp(gpmi_ctx *c, const double *X, int n, int ldx,
     if (F && (rc = d2h_matrix(c, d + o_f, (size_t)n, n, k, F, ldf))) return rc;
     if ((rc = d2h_matrix(c, d + o_zb, (size_t)n, n, k, Zbar, ldzb))) return rc;
     HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return info;
+}
+
+// ---- latent GP: forward product, likelihood head, its adjoint and the reverse sweep with ONE factorisation -------------------
+// (models/exact_gp.stan, fit_full_gp.stan: NORMAL; westbrook_exact.stan: BERNOULLI_LOGIT; heteroscedastic.stan: NORMAL_LOGSD)
+static int latent_check(int n, int ldx, int D, double alpha, int k, int ldz, int family, int m, int ldy, double sigma, bool hasF,
+                        int ldf, bool hasFb, int ldfb, int ldzb)
+{
+    int rc;
+    if ((rc = exact_gp_vjp_check(n, ldx, D, alpha, k, ldz, hasFb ? ldfb : n, hasF, ldf, ldzb))) return rc;
+    if (family != GPMI_LIK_NORMAL && family != GPMI_LIK_BERNOULLI_LOGIT && family != GPMI_LIK_NORMAL_LOGSD)
+        return gpmi_fail(GPMI_EARG, "unknown likelihood family");
+    if (k != (family == GPMI_LIK_NORMAL_LOGSD ? 2 : 1)) return gpmi_fail(GPMI_EARG, "k must be 2 for NORMAL_LOGSD and 1 otherwise");
+    if (m < 1 || ldy < n) return gpmi_fail(GPMI_EARG, "bad size or leading dimension of Y");
+    if (family == GPMI_LIK_NORMAL && (!(sigma > 0.0) || !isfinite(sigma))) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
+    return 0;
+}
+
+extern "C" int gpmi_latent_gp_lp_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
+                                          int n_ell, double jitter, const double *dZ, int k, int ldz, int family, const double *dY, int m,
+                                          int ldy, double sigma, double *d_out, double *dF, int ldf, double *dFbar, int ldfb,
+                                          double *dZbar, int ldzb, double *d_grad, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = latent_check(n, ldx, D, alpha, k, ldz, family, m, ldy, sigma, dF != nullptr, ldf, dFbar != nullptr, ldfb, ldzb))) return rc;
+    if (!dX || !dZ || !dY || !d_out || !dZbar || !d_grad || !d_info) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    const LatentHead lh{family, dY, m, ldy, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if (small_vjp(c, n, D, k)) {
+        if ((rc = reserve_ws_small(c, n, 4))) return rc;
+        launch_latent_gp_small(c->stream, dX, n, ldx, p, jitter, dZ, k, ldz, lh, d_out, dFbar, ldfb, dF, ldf, dZbar, ldzb, c->W, alpha, ell,
+                               n_ell, d_grad, d_info, c->d_info, nullptr);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    return exact_gp_vjp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dZ, k, ldz, nullptr, ldfb, dF, ldf, dZbar, ldzb, d_grad, d_info,
+                             &lh, dFbar, d_out);
+}
+
+extern "C" int gpmi_latent_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
+                                      double jitter, const double *Z, int k, int ldz, int family, const double *Y, int m, int ldy,
+                                      double sigma, double *out, double *F, int ldf, double *Fbar, int ldfb, double *Zbar, int ldzb,
+                                      double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = latent_check(n, ldx, D, alpha, k, ldz, family, m, ldy, sigma, F != nullptr, ldf, Fbar != nullptr, ldfb, ldzb))) return rc;
+    if (!X || !Z || !Y || !out || !Zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    if (family == GPMI_LIK_BERNOULLI_LOGIT)
+        for (int q = 0; q < m; ++q)
+            for (int i = 0; i < n; ++i) {
+                const double v = Y[(size_t)i + (size_t)q * ldy];
+                if (v != 0.0 && v != 1.0) return gpmi_fail(GPMI_EARG, "BERNOULLI_LOGIT: y must be 0 or 1");
+            }
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    hipStream_t s = c->stream;
+    const size_t nk = (size_t)n * k, nm = (size_t)n * m;
+    if (small_vjp(c, n, D, k)) {
+        // one launch of one workgroup through the pinned, device-mapped buffer:
+        // [info, .., out (2), .., flag | grad (1 + D) | F | Fbar | Zbar | X | Z | Y]
+        const size_t o_out = 2, o_g = 8, o_f = 24, o_fb = o_f + nk, o_zb = o_fb + nk, o_x = o_zb + nk, o_z = o_x + (size_t)n * D,
+                     o_y = o_z + nk;
+        if ((rc = pin_reserve(c, (o_y + nm) * sizeof(double)))) return rc;
+        double *h = c->h_pin, *stage;
+        for (int d = 0; d < D; ++d) memcpy(h + o_x + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
+        for (int q = 0; q < k; ++q) memcpy(h + o_z + (size_t)q * n, Z + (size_t)q * ldz, (size_t)n * sizeof(double));
+        for (int q = 0; q < m; ++q) memcpy(h + o_y + (size_t)q * n, Y + (size_t)q * ldy, (size_t)n * sizeof(double));
+        if ((rc = scratch_buf(c, ((size_t)n * (D + k) + nm) * sizeof(double), &stage))) return rc;
+        if ((rc = reserve_ws_small(c, n, 4))) return rc;
+        const int seq = ++c->pin_seq;
+        __atomic_store_n((int *)(h + 7), 0, __ATOMIC_RELEASE);   // armed before the launch: a stale word never reads as done
+        double *pd = c->h_pin_dev;
+        const LatentHead lh{family, pd + o_y, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+        launch_latent_gp_small(s, pd + o_x, n, n, p, jitter, pd + o_z, k, n, lh, pd + o_out, Fbar ? pd + o_fb : nullptr, n,
+                               F ? pd + o_f : nullptr, n, pd + o_zb, n, c->W, alpha, ell, n_ell, pd + o_g, (int *)pd, c->d_info, stage,
+                               (int *)(pd + 7), seq);
+        HIPCHK(hipGetLastError());
+        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
+        for (int q = 0; q < k; ++q) {
+            if (F) memcpy(F + (size_t)q * ldf, h + o_f + (size_t)q * n, (size_t)n * sizeof(double));
+            if (Fbar) memcpy(Fbar + (size_t)q * ldfb, h + o_fb + (size_t)q * n, (size_t)n * sizeof(double));
+            memcpy(Zbar + (size_t)q * ldzb, h + o_zb + (size_t)q * n, (size_t)n * sizeof(double));
+        }
+        memcpy(out, h + o_out, 2 * sizeof(double));
+        memcpy(grad, h + o_g, (size_t)(1 + n_ell) * sizeof(double));
+        return *(const int *)h;
+    }
+    // blocked chain: [X | Z | Y | F | Fbar | Zbar | grad (65) | out (2) | info] staged in device memory
+    double *d;
+    const size_t o_z = (size_t)n * D, o_y = o_z + nk, o_f = o_y + nm, o_fb = o_f + nk, o_zb = o_fb + nk, o_g = o_zb + nk,
+                 o_out = o_g + 1 + GPMI_MAXD_BIG, o_i = o_out + 2;
+    if ((rc = stage_buf(c, 0, (o_i + 1) * sizeof(double), &d))) return rc;
+    if ((rc = h2d_matrix(c, X, n, D, ldx, d))) return rc;
+    if ((rc = h2d_matrix(c, Z, n, k, ldz, d + o_z))) return rc;
+    if ((rc = h2d_matrix(c, Y, n, m, ldy, d + o_y))) return rc;
+    const LatentHead lh{family, d + o_y, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if ((rc = exact_gp_vjp_core(c, d, n, n, p, alpha, ell, n_ell, jitter, d + o_z, k, n, nullptr, n, F ? d + o_f : nullptr, n, d + o_zb, n,
+                                d + o_g, (int *)(d + o_i), &lh, d + o_fb, d + o_out)))
+        return rc;
+    int info = 0;
+    if (F && (rc = d2h_matrix(c, d + o_f, (size_t)n, n, k, F, ldf))) return rc;
+    if (Fbar && (rc = d2h_matrix(c, d + o_fb, (size_t)n, n, k, Fbar, ldfb))) return rc;
+    if ((rc = d2h_matrix(c, d + o_zb, (size_t)n, n, k, Zbar, ldzb))) return rc;
+    HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, d + o_out, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return info;

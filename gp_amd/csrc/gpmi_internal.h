@@ -235,6 +235,26 @@ void launch_exact_gp_vjp_small(hipStream_t s, const double *X, int n, int ldx, c
                                int ldz, const double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb, double *W, double alpha,
                                const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage,
                                int *done = nullptr, int seq = 0);
+// A likelihood head of gpmi_latent_gp_lp_grad: the m replicate columns of Y against the rows of F; sigma is read by
+// GPMI_LIK_NORMAL alone
+struct LatentHead {
+    int family;        // GPMI_LIK_*
+    const double *Y;   // n x m, leading dimension ldy
+    int m, ldy;
+    double sigma, log_sigma;   // log_sigma = log(sigma), formed on the host (NORMAL only)
+};
+// launch_exact_gp_vjp_small with the head between the product and the sweep (k <= 2): out[0] = lik, out[1] = d lik / d sigma,
+// Fb (nullable) receives Fbar; stage != null: n (D + k + m) doubles of device scratch
+void launch_latent_gp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *Z, int k,
+                            int ldz, const LatentHead &lh, double *out, double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb,
+                            double *W, double alpha, const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work,
+                            double *stage, int *done = nullptr, int seq = 0);
+// the chain's head (latent_kernels.hip): Fbar (n x k, ldfb) from F (n x k, ldf) and the head, one partial (lik, d lik / d sigma)
+// pair per block of 256 rows in part (2 latent_head_blocks(n) doubles), added in index order into out[0..1] (NaN when *info != 0,
+// and then Fbar is NaN too)
+int latent_head_blocks(int n);
+void launch_latent_head(hipStream_t s, const double *F, size_t ldf, int n, int k, const LatentHead &lh, double *Fb, size_t ldfb,
+                        double *part, double *out, const int *info);
 // rbf_cov_chol (L and dL/dl) for P <= 64 length-scales, one workgroup each, n <= 128 (workspace: 3 P slices of small_ws_layout(n));
 // x / Lout, dLout, info_out may be host-mapped (stage != null: P n doubles of device scratch)
 void launch_rbf_cov_chol_small(hipStream_t s, const double *x, int n, const double *ls, int P, double *Wall, double *Lout, double *dLout,

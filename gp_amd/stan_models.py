@@ -4,6 +4,8 @@ models/fit_hyperparameters.stan:18-32 (== stan/fit_hyperparameters.stan):
     Sigma = cov_exp_quad(t, alpha, rho) + sigma^2 I;  L = cholesky_decompose(Sigma)
     y ~ multi_normal_cholesky(0, L)
 models/exact_gp.stan:16-26:  f = cholesky_decompose(cov_exp_quad(x, 1, l) + 1e-10 I) * z
+models/westbrook_exact.stan, models/heteroscedastic.stan, models/fit_full_gp.stan: the same latent transform under a Bernoulli,
+    a log-sd normal and a normal likelihood (gpmi_latent_gp_lp_grad: one factorisation per value/gradient pair)
 """
 import math
 
@@ -90,19 +92,31 @@ def exact_gp_f(x, l, z, ctx=None):
     return c.exact_gp_f(x, 1.0, [l], z, 1e-10)   # covariance, factor and product stay on the device (gpmi_exact_gp_f)
 
 
-def exact_gp_log_prob_grad(x, y, l, sigma, z, ctx=None):
+def exact_gp_log_prob_grad(x, y, l, sigma, z, ctx=None, fused=False):
     """(lp__, d lp__/d(l, sigma, z)) of models/exact_gp.stan -- the value/gradient pair NUTS asks for at every leapfrog step
     of test_interpolate.R:31-36.  Conventions of fit_hyperparameters_log_prob_grad: `~` drops constants, the <lower=0>
     Jacobians log l + log sigma are included:
         lp = -z'z / 2 + 3 log l - 4 l - N log sigma - |y - f|^2 / (2 sigma^2) + log l + log sigma.
     With ubar = (y - f) / sigma^2 the gradient is (ubar' (dL/dl) z + 4/l - 4, -N/sigma + |y - f|^2 / sigma^3 + 1/sigma,
     L' ubar - z); ubar' (dL/dl) z and L' ubar come from the vector-Jacobian product of the transform
-    (gpmi_exact_gp_f_vjp).  A non-positive-definite proposal returns (-inf, NaN)."""
+    (gpmi_exact_gp_f_vjp).  A non-positive-definite proposal returns (-inf, NaN).  fused=True takes
+    gpmi_latent_gp_lp_grad instead: product, likelihood, its adjoint and the sweep in one call with one factorisation."""
     c = ctx or default_context()
     z = np.asarray(z, float).ravel()
     y = np.asarray(y, float).ravel()
     n = z.size
     x = np.asarray(x, float).reshape(n, -1)
+    if fused:
+        try:
+            r = c.latent_gp_lp_grad(x, 1.0, [l], z, "normal", y, sigma, 1e-10, want_f=False)
+        except NotPositiveDefinite:
+            return -math.inf, np.full(2 + n, math.nan)
+        lp = -0.5 * float(z @ z) + 3.0 * math.log(l) - 4.0 * l + r["lik"] + math.log(l) + math.log(sigma)
+        grad = np.empty(2 + n)
+        grad[0] = r["grad"][1] + 4.0 / l - 4.0
+        grad[1] = r["dlik_dsigma"] + 1.0 / sigma
+        grad[2:] = r["Zbar"] - z
+        return lp, grad
     try:
         f = c.exact_gp_f(x, 1.0, [l], z, 1e-10)
         r = y - f
@@ -117,6 +131,74 @@ def exact_gp_log_prob_grad(x, y, l, sigma, z, ctx=None):
     grad[0] = g[1] + 4.0 / l - 4.0
     grad[1] = -n / sigma + rr / sigma ** 3 + 1.0 / sigma
     grad[2:] = zbar - z
+    return lp, grad
+
+
+def westbrook_exact_log_prob_grad(x, y, z, sigma, l, ctx=None, jitter=1e-12):
+    """(lp__, d lp__/d(z, sigma, l)) of models/westbrook_exact.stan (sigma is the GP's amplitude; y in {0, 1}):
+        lp = -z'z / 2 + 3 log l - 4 l - sigma^2 / 2 + sum(y f - softplus(f)) + log sigma + log l,  f = chol(K(sigma, l) + 1e-12 I) z.
+    The model writes y ~ bernoulli(inv_logit(f)); the likelihood here is the equal, stable bernoulli_logit form.  One call of
+    gpmi_latent_gp_lp_grad; conventions of exact_gp_log_prob_grad.  jitter: the model's 1e-12 unless overridden."""
+    c = ctx or default_context()
+    z = np.asarray(z, float).ravel()
+    n = z.size
+    x = np.asarray(x, float).reshape(n, -1)
+    try:
+        r = c.latent_gp_lp_grad(x, sigma, [l], z, "bernoulli_logit", np.asarray(y, float).ravel(), None, jitter, want_f=False)
+    except NotPositiveDefinite:
+        return -math.inf, np.full(2 + n, math.nan)
+    lp = -0.5 * float(z @ z) + 3.0 * math.log(l) - 4.0 * l - 0.5 * sigma * sigma + r["lik"] + math.log(sigma) + math.log(l)
+    grad = np.empty(2 + n)
+    grad[:n] = r["Zbar"] - z
+    grad[n] = r["grad"][0] - sigma + 1.0 / sigma
+    grad[n + 1] = r["grad"][1] + 4.0 / l - 4.0
+    return lp, grad
+
+
+def heteroscedastic_log_prob_grad(x, Y, l, sigmaf, z1, z2, ctx=None):
+    """(lp__, d lp__/d(l, sigmaf, z1, z2)) of models/heteroscedastic.stan (Y: N x M replicates; mu = L z1, sigma = exp(L z2),
+    L = chol(K(sigmaf, l) + 1e-9 I)):
+        lp = 3 log l - 4 l - sigmaf^2 / 2 - z1'z1 / 2 - z2'z2 / 2 + sum_im(-s_i - (y_im - mu_i)^2 exp(-2 s_i) / 2) + log l + log sigmaf.
+    One call of gpmi_latent_gp_lp_grad with two latent columns; conventions of exact_gp_log_prob_grad."""
+    c = ctx or default_context()
+    z1 = np.asarray(z1, float).ravel(); z2 = np.asarray(z2, float).ravel()
+    n = z1.size
+    x = np.asarray(x, float).reshape(n, -1)
+    Y = np.asarray(Y, float).reshape(n, -1)
+    try:
+        r = c.latent_gp_lp_grad(x, sigmaf, [l], np.column_stack([z1, z2]), "normal_logsd", Y, None, 1e-9, want_f=False)
+    except NotPositiveDefinite:
+        return -math.inf, np.full(2 + 2 * n, math.nan)
+    lp = (3.0 * math.log(l) - 4.0 * l - 0.5 * sigmaf * sigmaf - 0.5 * float(z1 @ z1) - 0.5 * float(z2 @ z2) + r["lik"]
+          + math.log(l) + math.log(sigmaf))
+    grad = np.empty(2 + 2 * n)
+    grad[0] = r["grad"][1] + 4.0 / l - 4.0
+    grad[1] = r["grad"][0] - sigmaf + 1.0 / sigmaf
+    grad[2:2 + n] = r["Zbar"][:, 0] - z1
+    grad[2 + n:] = r["Zbar"][:, 1] - z2
+    return lp, grad
+
+
+def fit_full_gp_log_prob_grad(x, y, l, alpha, sigma, zn, ctx=None):
+    """(lp__, d lp__/d(l, alpha, sigma, zn)) of models/fit_full_gp.stan (z = alpha chol(K(1, l) + 1e-12 I) zn, y ~ normal(z, sigma),
+    no prior on sigma):
+        lp = 3 log l - 4 l - alpha^2 / 2 - zn'zn / 2 - N log sigma - |y - z|^2 / (2 sigma^2) + log l + log alpha + log sigma.
+    The call with amplitude 1 and Z = alpha zn: zn_bar = alpha Zbar - zn, alpha_bar = Zbar . zn - alpha + 1 / alpha."""
+    c = ctx or default_context()
+    zn = np.asarray(zn, float).ravel()
+    n = zn.size
+    x = np.asarray(x, float).reshape(n, -1)
+    try:
+        r = c.latent_gp_lp_grad(x, 1.0, [l], alpha * zn, "normal", np.asarray(y, float).ravel(), sigma, 1e-12, want_f=False)
+    except NotPositiveDefinite:
+        return -math.inf, np.full(3 + n, math.nan)
+    lp = (3.0 * math.log(l) - 4.0 * l - 0.5 * alpha * alpha - 0.5 * float(zn @ zn) + r["lik"] + math.log(l) + math.log(alpha)
+          + math.log(sigma))
+    grad = np.empty(3 + n)
+    grad[0] = r["grad"][1] + 4.0 / l - 4.0
+    grad[1] = float(r["Zbar"] @ zn) - alpha + 1.0 / alpha
+    grad[2] = r["dlik_dsigma"] + 1.0 / sigma
+    grad[3:] = alpha * r["Zbar"] - zn
     return lp, grad
 
 

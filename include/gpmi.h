@@ -166,6 +166,31 @@ GPMI_API int gpmi_exact_gp_f_vjp_dev(gpmi_ctx *ctx, const double *dX, int n, int
                             int n_ell, double jitter, const double *dZ, int k, int ldz, const double *dFbar, int ldfb,
                             double *dF /* nullable */, int ldf, double *dZbar, int ldzb, double *d_grad, int *d_info);
 
+/* The latent exact-GP models' likelihood part of lp__ and its gradient in one call with ONE factorisation: forward product
+ * F = L Z, a likelihood head on F against the m replicate columns of Y (n x m, ldy), the head's adjoint Fbar = d lik / d F and the
+ * reverse sweep of gpmi_exact_gp_f_vjp on that Fbar.  Heads (the constants `~` drops are dropped; sums over rows i and columns c):
+ *   GPMI_LIK_NORMAL (k = 1; models/exact_gp.stan:27-33, fit_full_gp.stan): lik = sum(-log sigma - (y_ic - f_i)^2 / (2 sigma^2)),
+ *     Fbar_i = sum_c (y_ic - f_i) / sigma^2, out[1] = d lik / d sigma = -n m / sigma + sum r^2 / sigma^3;
+ *   GPMI_LIK_BERNOULLI_LOGIT (k = 1, y in {0, 1}; models/westbrook_exact.stan): lik = sum(y f - softplus(f)),
+ *     Fbar_i = sum_c (y_ic - inv_logit(f_i)), softplus(f) = max(f, 0) + log1p(exp(-|f|)): Stan's bernoulli_logit, finite for |f|
+ *     in the hundreds, where the model's bernoulli(inv_logit(f)) underflows;
+ *   GPMI_LIK_NORMAL_LOGSD (k = 2, mu = F[:,0], s = F[:,1]; models/heteroscedastic.stan:23-36): lik = sum(-s_i - (y_ic - mu_i)^2
+ *     exp(-2 s_i) / 2), Fbar[:,0] = sum_c (y - mu) exp(-2 s), Fbar[:,1] = sum_c ((y - mu)^2 exp(-2 s) - 1).
+ * out[0] = lik, out[1] = d lik / d sigma (0 for the heads without sigma); F and Fbar (both nullable, n x k) as computed; Zbar,
+ * grad, the return value and NaN on a non-positive leading minor (out[0] too) as gpmi_exact_gp_f_vjp.  Priors and Jacobians stay
+ * with the caller.  All sums run in a fixed order: repeated calls give identical bits.  GPMI_EARG: k or m not as the family asks,
+ * ldy < n, sigma <= 0 (NORMAL), unknown family, and on this host-buffer form y outside {0, 1} (BERNOULLI_LOGIT). */
+enum { GPMI_LIK_NORMAL = 0, GPMI_LIK_BERNOULLI_LOGIT = 1, GPMI_LIK_NORMAL_LOGSD = 2 };
+GPMI_API int gpmi_latent_gp_lp_grad(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
+                           double jitter, const double *Z, int k, int ldz, int family, const double *Y, int m, int ldy,
+                           double sigma, double *out, double *F /* nullable */, int ldf, double *Fbar /* nullable */, int ldfb,
+                           double *Zbar, int ldzb, double *grad);
+/* the same with device-resident X, Z, Y, out (2), F, Fbar, Zbar, grad and d_info (1 int), enqueued on the context's stream */
+GPMI_API int gpmi_latent_gp_lp_grad_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
+                               int n_ell, double jitter, const double *dZ, int k, int ldz, int family, const double *dY, int m,
+                               int ldy, double sigma, double *d_out, double *dF /* nullable */, int ldf,
+                               double *dFbar /* nullable */, int ldfb, double *dZbar, int ldzb, double *d_grad, int *d_info);
+
 /* ---- marginal likelihood ---------------------------------------------- */
 
 /* One evaluation of models/fit_hyperparameters.stan:18-32 with double inputs:

@@ -111,6 +111,15 @@ gp_exact_f <- function(X, alpha, rho, z, jitter = 1e-10)
 exact_gp_f_vjp <- function(X, alpha, rho, z, fbar, jitter = 1e-10)
   .Call("gpmi_R_exact_gp_f_vjp", as.matrix(X), alpha, as.double(rho), jitter, z + 0.0, fbar + 0.0)
 
+# forward product, likelihood head, its adjoint and the reverse sweep in one call with one factorisation: list(lik, dlik_dsigma,
+# f, fbar, zbar, grad) for family "normal" (models/exact_gp.stan, fit_full_gp.stan), "bernoulli_logit" (westbrook_exact.stan; the
+# stable form of bernoulli(inv_logit(f))) or "normal_logsd" (heteroscedastic.stan: z n x 2, y n x M); priors stay with the caller
+latent_gp_lp_grad <- function(X, alpha, rho, z, family, y, sigma = 1, jitter = 1e-10) {
+  fam <- match(family, c("normal", "bernoulli_logit", "normal_logsd")) - 1L
+  stopifnot(!is.na(fam))
+  .Call("gpmi_R_latent_gp_lp_grad", as.matrix(X), alpha, as.double(rho), jitter, z + 0.0, fam, y + 0.0, sigma)
+}
+
 # models/fit_hyperparameters.stan:18-32 as plain functions
 gp_log_marginal <- function(X, y, alpha, rho, sigma, jitter = 0)
   .Call("gpmi_R_logml", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)[1]

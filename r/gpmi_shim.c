@@ -300,6 +300,35 @@ SEXP gpmi_R_exact_gp_f_vjp(SEXP X, SEXP alpha, SEXP ell, SEXP jitter, SEXP z, SE
     return out;
 }
 
+/* list(lik, dlik_dsigma, f, fbar, zbar, grad): the likelihood part of a latent exact-GP model's lp__ and its gradient in one
+ * call with one factorisation (gpmi_latent_gp_lp_grad).  family: 0 normal, 1 bernoulli_logit, 2 normal_logsd (z n x 2);
+ * y: n-vector or n x m matrix of replicates. */
+SEXP gpmi_R_latent_gp_lp_grad(SEXP X, SEXP alpha, SEXP ell, SEXP jitter, SEXP z, SEXP family, SEXP y, SEXP sigma)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), ne = Rf_length(ell);
+    need(is_real(X) && is_real(z) && is_real(y) && is_real(ell), "X, z, y and the length-scales must be double");
+    need(n > 0 && Rf_length(z) % n == 0 && Rf_length(z) > 0, "length(z) must be a multiple of nrow(X)");
+    need(Rf_length(y) % n == 0 && Rf_length(y) > 0, "length(y) must be a multiple of nrow(X)");
+    need(ne == 1 || ne == D, "length-scale must have length 1 or ncol(X)");
+    int k = Rf_length(z) / n, m = Rf_length(y) / n;
+    SEXP f = PROTECT(Rf_duplicate(z)), fb = PROTECT(Rf_duplicate(z)), zb = PROTECT(Rf_duplicate(z));
+    SEXP g = PROTECT(Rf_allocVector(REALSXP, 1 + ne)), lik = PROTECT(Rf_allocVector(REALSXP, 1)), ds = PROTECT(Rf_allocVector(REALSXP, 1));
+    double o2[2] = {0.0, 0.0};
+    int rc = gpmi_latent_gp_lp_grad(ctx(), REAL(X), n, n, D, Rf_asReal(alpha), REAL(ell), ne, Rf_asReal(jitter), REAL(z), k, n,
+                                    Rf_asInteger(family), REAL(y), m, n, Rf_asReal(sigma), o2, REAL(f), n, REAL(fb), n, REAL(zb), n,
+                                    REAL(g));
+    static const char *nm[6] = {"lik", "dlik_dsigma", "f", "fbar", "zbar", "grad"};
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 6)), names = PROTECT(Rf_allocVector(STRSXP, 6));
+    REAL(lik)[0] = o2[0]; REAL(ds)[0] = o2[1];
+    SET_VECTOR_ELT(out, 0, lik); SET_VECTOR_ELT(out, 1, ds);
+    SET_VECTOR_ELT(out, 2, f); SET_VECTOR_ELT(out, 3, fb); SET_VECTOR_ELT(out, 4, zb); SET_VECTOR_ELT(out, 5, g);
+    for (int i = 0; i < 6; ++i) SET_STRING_ELT(names, i, Rf_mkChar(nm[i]));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(8);
+    check(rc);
+    return out;
+}
+
 /* list(value = c(logml, sum log L_ii, z'z), grad = c(d/dalpha, d/dell..., d/dsigma)): what Stan's
  * autodiff computes per leapfrog step for models/fit_hyperparameters.stan:18-32 */
 SEXP gpmi_R_logml_grad(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter)
