@@ -28,7 +28,8 @@ SYMBOLS = (
     "gpmi_interp_free", "gpmi_logml_grad", "gpmi_logml_grad_grid",
     "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
-    "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy",
+    "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy", "gpmi_seq_marginals",
+    "gpmi_gp_predict", "gpmi_gp_predict_dev",
     "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex",
 )
 # additionally exported by the probe build (libgpmi_probes.so, -DGPMI_PROBES; tools/ only)
@@ -543,6 +544,21 @@ class Context:
                                          max(m, 1)))
         return mn, Kn
 
+    def gp_predict(self, X, y, alpha, ell, sigma, jitter, Xs, want_var=True):
+        """Pointwise posterior of the latent function at the rows of Xs (m x D) given (X, y) under the ARD squared-exponential
+        model of logml: {"mean" (m,), "var" (m,) or None, "info"}.  var is alpha^2 - k^T Sigma^-1 k as computed (not clamped, no
+        sigma^2); info = k > 0: Sigma is not positive definite at order k (mean, var all NaN)."""
+        X = _mat(X); y = _vec(y); ell = _vec(ell); Xs = _mat(Xs)
+        n, D = X.shape
+        m = Xs.shape[0]
+        if y.size != n or Xs.shape[1] != D:
+            raise GpmiError(-1, "X, y and Xs disagree on N or D")
+        mean = np.empty(m); var = np.empty(m) if want_var else None
+        info = _chk(self._lib.gpmi_gp_predict(self._h, _p(X), n, max(n, 1), D, _p(y), _d(alpha), _p(ell), int(ell.size), _d(sigma),
+                                              _d(jitter), _p(Xs), m, max(m, 1), _p(mean), _p(var) if want_var else None),
+                    allow_info=True)
+        return {"mean": mean, "var": var, "info": int(info)}
+
     def sample_derivs(self, t, ts, y, l, a, sy, jitter, z):
         """(draw, mu): mu + chol(cov) z of sample_derivs (pendulum_fit.R:227-255), fused on the device."""
         t = _vec(t); ts = _vec(ts); y = _vec(y); z = _vec(z)
@@ -579,6 +595,14 @@ class Context:
         _chk(self._lib.gpmi_logml_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), C.c_void_p(dy_ptr),
                                       _d(alpha), _p(ell), int(ell.size), _d(sigma), _d(jitter),
                                       C.c_void_p(dout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def gp_predict_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, ell, sigma, jitter, dXs_ptr, m, ldxs, dmean_ptr, dvar_ptr, dinfo_ptr):
+        """gpmi_gp_predict_dev on device pointers (dvar_ptr may be None: mean only); enqueued, not synchronised."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_gp_predict_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), C.c_void_p(dy_ptr), _d(alpha),
+                                           _p(ell), int(ell.size), _d(sigma), _d(jitter), C.c_void_p(dXs_ptr), int(m), int(ldxs),
+                                           C.c_void_p(dmean_ptr), C.c_void_p(dvar_ptr) if dvar_ptr else None,
+                                           C.c_void_p(dinfo_ptr)))
 
     def exact_gp_f_vjp_dev(self, dX_ptr, n, ldx, D, alpha, ell, jitter, dZ_ptr, k, ldz, dFbar_ptr, ldfb, dF_ptr, ldf, dZbar_ptr,
                            ldzb, dgrad_ptr, dinfo_ptr):
@@ -705,6 +729,17 @@ class SeqSampler:
         out = np.empty(2)
         _chk(self._lib.gpmi_seq_step(self._h, _p(xs), _p(out)))
         return out[0], out[1]
+
+    def marginals(self, Xs):
+        """(mean (m,), var (m,)): for each row of Xs what step() would return on a sampler with no committed draws
+        (R/tests.R:89-97 in one call); the sampler itself is left as it was."""
+        Xs = _mat(Xs)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise GpmiError(-1, "Xs must have D = %d columns" % self.D)
+        m = Xs.shape[0]
+        mean = np.empty(m); var = np.empty(m)
+        _chk(self._lib.gpmi_seq_marginals(self._h, _p(Xs), m, max(m, 1), _p(mean), _p(var)))
+        return mean, var
 
     def commit(self, dot_xs):
         _chk(self._lib.gpmi_seq_commit(self._h, _d(dot_xs)))

@@ -2550,6 +2550,61 @@ __global__ __launch_bounds__(256, 2) void k_gp_condition_small(const double *__r
     small_signal_done(done, seq);
 }
 
+// gpmi_gp_predict (pointwise posterior mean and variance at m new D-dimensional inputs; what the sweep of R/tests.R:89-97 asks
+// of create_p_dotXnS, R/ode_gp_library.R:43-93) at the reference's sizes by ONE workgroup: joint matrix
+// [[K + diag_add I, .], [Ks, alpha^2 on the diagonal]] of the n + m points [X; Xs] built with se_cov_tile (the arithmetic of
+// gpmi_se_cov), the row [y^T, 0], partial factorisation of the first n columns; the Schur block's diagonal is then var and the
+// last row -mean.  X, Xs, y are read exactly once each (into LDS / the workspace), so host-mapped inputs need no staging copy;
+// mean / var (nullable) / info_out may be host-mapped as well.
+__global__ __launch_bounds__(256, 2) void k_gp_predict_small(const double *__restrict__ X, int n, int ldx, const double *__restrict__ Xs,
+                                                          int m, int ldxs, const double *__restrict__ y, SeParams p, double diag_add,
+                                                          double *__restrict__ W, size_t ld, double *__restrict__ mean,
+                                                          double *__restrict__ var, int *info_out, int *info_w, ExpC ec, int *done,
+                                                          int seq)
+{
+    GPMI_SMALL_LDS
+    const int tid = threadIdx.x, nt = n + m;
+    if (tid == 0) *info_w = 0;
+    SmallSe se;
+    se.a2 = p.a2;
+    se.D = p.D;
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
+    {
+        double *xs = &smem[0][0][0][0];   // nt * D <= 1024 * GPMI_MAXD doubles fit the tile staging buffer
+#pragma unroll
+        for (int d = 0; d < GPMI_MAXD; ++d)
+            if (d < se.D)
+                for (int i = tid; i < nt; i += 256)
+                    xs[i + d * nt] = __dmul_rn(i < n ? X[(size_t)i + (size_t)d * ldx] : Xs[(size_t)(i - n) + (size_t)d * ldxs], se.inv_ell[d]);
+        __syncthreads();
+        for (int row0 = 0; row0 < nt; row0 += SE_TR)
+            for (int col0 = 0; col0 < row0 + SE_TR && col0 < nt; col0 += SE_TC) {
+                switch (se.D) {
+                case 1: se_cov_tile<1, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                case 2: se_cov_tile<2, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                case 3: se_cov_tile<3, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                default: se_cov_tile<0, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                }
+            }
+    }
+    __syncthreads();
+    // the new points carry the latent function's prior variance: no noise term on their diagonal
+    for (int i = n + tid; i < nt; i += 256) W[(size_t)i * (ld + 1)] = se.a2;
+    for (int j = tid; j < nt; j += 256) W[(size_t)nt + (size_t)j * ld] = j < n ? y[j] : 0.0;
+    __syncthreads();
+    small_potrf_partial(smem, s_F, s_aux, W, ld, nt + 1, nt, n, info_w, false);
+    __syncthreads();
+    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int r = tid; r < m; r += 256) {
+        const size_t c = (size_t)(n + r);
+        mean[r] = info ? __builtin_nan("") : -W[(size_t)nt + c * ld];
+        if (var) var[r] = info ? __builtin_nan("") : W[c * (ld + 1)];
+    }
+    if (tid == 0) *info_out = info;
+    small_signal_done(done, seq);
+}
+
 // f = chol(cov_exp_quad(X, alpha, ell) + diag_add I) z (models/exact_gp.stan:17-25: the latent exact GP's transform, once per
 // leapfrog step with a new length-scale) by ONE workgroup for n <= 256: build (se_cov_tile), factorisation, and the row sums
 // f_i = sum_{j <= i} L_ij z_j in column order (the order of k_trmv_lower_part inside its first chunk).  stage (nullable): X, z
@@ -3424,6 +3479,7 @@ static void small_lds_attr()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_small_batch_dev), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sample_derivs_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gp_condition_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gp_predict_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_vjp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_latent_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -3461,6 +3517,8 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->grad_aug_ng = 2304;
     t->small_vjp = 256;
     t->small_gc = 180;    // gpmi_gp_condition by one workgroup up to n + m + 1 rows (tools/cond_bench.py)
+    t->small_pr = 180;    // gpmi_gp_predict by one workgroup up to n + m + 1 rows (tools/predict_bench.py)
+    t->predict_mb = 0;    // rows of Xs per chunk of the blocked prediction chain (0: auto, about n / 4)
     t->small_sd = 640;
     t->small_sdb = 5;     // tools/sample_derivs_bench.py: one workgroup 0.21 / 0.56 / 0.73 ms at n = m = 79 / 199 / 256, the lanes 95 / 136 / 129 us per draw
     t->small_n2 = 1024;
@@ -4124,6 +4182,17 @@ void launch_gp_condition_small(hipStream_t s, const double *t, int n, const doub
     CondArgs q{kindK, kindS, kindSS, compat, a2, l2, s2, jitter};
     hipLaunchKernelGGL(k_gp_condition_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, t, n, ts, m, y, q, W, ld, Kn, ldo, mn,
                        info_out, d_info_work, stage, done, seq);
+}
+
+void launch_gp_predict_small(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const double *y,
+                             const SeParams &p, double diag_add, double *W, double *mean, double *var, int *info_out, int *d_info_work,
+                             int *done, int seq)
+{
+    size_t ld, stride;
+    small_ws_layout(n + m, &ld, &stride);
+    small_lds_attr();
+    hipLaunchKernelGGL(k_gp_predict_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, Xs, m, ldxs, y, p, diag_add, W,
+                       ld, mean, var, info_out, d_info_work, h_exp, done, seq);
 }
 
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,

@@ -429,6 +429,16 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         c->tune.small_gc = value;
         return 0;
     }
+    if (!strcmp(name, "small_pr")) {  // gp_predict by one workgroup up to this many rows n + m + 1 (0: every size takes the chain)
+        if (value < 0 || value > 1024) return gpmi_fail(GPMI_EARG, "small_pr must be 0 .. 1024");
+        c->tune.small_pr = value;
+        return 0;
+    }
+    if (!strcmp(name, "predict_mb")) {  // rows of Xs per chunk of the prediction chains (0: auto)
+        if (value < 0) return gpmi_fail(GPMI_EARG, "predict_mb must be >= 0");
+        c->tune.predict_mb = value;
+        return 0;
+    }
     if (!strcmp(name, "small_sd")) {  // sample_derivs[_batch]: one workgroup per draw up to this many rows n + m + 1 (0: off)
         if (value < 0 || value > 1024) return gpmi_fail(GPMI_EARG, "small_sd must be 0 .. 1024");
         c->tune.small_sd = value;
@@ -2965,6 +2975,138 @@ extern "C" int gpmi_gp_condition(gpmi_ctx *c, const double *t, int n, const doub
     return info;
 }
 
+// ---- GP posterior at new D-dimensional inputs: pointwise mean and variance ---------------------------
+// Sigma = K(X, X) + (sigma^2 + jitter) I = L L^T (gpmi_logml's matrix), k_j = K(X, xs_j):
+//   mean_j = k_j^T Sigma^-1 y = t_j . z,  var_j = alpha^2 - t_j . t_j,  t_j = L^-1 k_j,  z = L^-1 y.
+// What create_p_dotXnS conditions on (R/ode_gp_library.R:43-93, QQard with D = ncol(X)) and what the sweep of
+// R/tests.R:89-97 takes of it: the first step of a fresh sampler at each of 41 states.
+// Blocked chain: one factorisation with the augmented row y^T (-> z) that keeps its packed panel factors, then Xs in chunks
+// of mb rows built below the factor, whitened by launch_trsm_right and reduced by launch_predict_rows.  Without the variance
+// there is no n^2 m solve: a = L^-T z by launch_trsv_lower_t and mean_j = sum_i k(xs_j, x_i) a_i by launch_predict_mean.
+static int predict_chunk_rows(const gpmi_ctx *c, int n, int m)
+{
+    // auto: about n / 4 rows (a multiple of 128, at least 128): with the 16-row alignment gap the workspace stays
+    // within that of a factorisation of order 1.25 n
+    int mb = c->tune.predict_mb > 0 ? c->tune.predict_mb : ((n / 4 + 127) / 128) * 128;
+    if (mb < 1) mb = 128;
+    return mb > m ? m : mb;
+}
+
+static bool small_predict(const gpmi_ctx *c, int n, int m, int D)
+{
+    return c->tune.small_pr > 0 && (long long)n + m + 1 <= (long long)c->tune.small_pr && D <= GPMI_MAXD;
+}
+
+static int predict_check(int n, int ldx, int D, double alpha, double sigma, int m, int ldxs)
+{
+    if (n < 1 || m < 1) return gpmi_fail(GPMI_EARG, "n and m must be positive");
+    if (D < 1 || D > GPMI_MAXD_BIG) return gpmi_fail(GPMI_EARG, "D = %d unsupported (1..%d)", D, GPMI_MAXD_BIG);
+    if (ldx < n || ldxs < m) return gpmi_fail(GPMI_EARG, "leading dimension smaller than the number of rows");
+    if (!(alpha > 0.0)) return gpmi_fail(GPMI_EARG, "alpha must be positive");
+    if (!(sigma >= 0.0)) return gpmi_fail(GPMI_EARG, "sigma must be non-negative");
+    return 0;
+}
+
+static int predict_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
+                        const double *dXs, int m, int ldxs, double *d_mean, double *d_var, int *d_info)
+{
+    int rc;
+    hipStream_t s = c->stream;
+    if (small_predict(c, n, m, p.D)) {
+        if ((rc = reserve_ws_small(c, n + m, 1))) return rc;
+        launch_gp_predict_small(s, dX, n, ldx, dXs, m, ldxs, dy, p, diag_add, c->W, d_mean, d_var, d_info, c->d_info);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    const int rs = ((n + 1 + 15) / 16) * 16;   // first row of the chunk: 16-row aligned below the factor and the row of z
+    const int mb = d_var ? predict_chunk_rows(c, n, m) : 0;
+    if ((rc = reserve_ws(c, d_var ? rs + mb : n + 1, n))) return rc;
+    const size_t ld = (size_t)c->ld;
+    const int npan = (n + GPMI_NB - 1) / GPMI_NB;
+    const size_t n_part = d_var ? predict_rows_part_doubles(n, mb) : predict_mean_part_doubles(n, m);
+    double *Fall;
+    if ((rc = stage_buf(c, 2, ((size_t)npan * GPMI_FPACK + 2 * (size_t)n + n_part) * sizeof(double), &Fall))) return rc;
+    double *zw = Fall + (size_t)npan * GPMI_FPACK, *av = zw + n, *part = av + n;
+    HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
+    launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, diag_add, 1, c->W, ld);
+    launch_set_row(s, c->W, ld, n, dy, n, n);
+    if ((rc = launch_potrf_partial(c, c->W, ld, n + 1, n, n, c->d_info, d_var ? Fall : nullptr))) return rc;
+    if (!d_var) {
+        launch_get_row(s, c->W, ld, n, 0, n, 1.0, zw);
+        launch_trsv_lower_t(s, c->W, ld, n, zw, av);
+        launch_predict_mean(s, dX, n, ldx, dXs, m, ldxs, p, av, part, d_mean, c->d_info, d_info);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    double *T = c->W + rs;
+    for (int j0 = 0; j0 < m; j0 += mb) {
+        const int mc = (m - j0 < mb) ? m - j0 : mb;
+        launch_se_cov(c, s, dXs + j0, mc, ldxs, dX, n, ldx, p, 0.0, 0, T, ld);
+        if ((rc = launch_trsm_right(c, c->W, ld, n, T, ld, mc, Fall))) return rc;
+        launch_predict_rows(s, T, ld, T, ld, c->W + n, ld, n, mc, p.a2, part, d_mean + j0, d_var + j0, c->d_info, d_info);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_gp_predict_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, double alpha,
+                                   const double *ell, int n_ell, double sigma, double jitter, const double *dXs, int m, int ldxs,
+                                   double *d_mean, double *d_var, int *d_info)
+{
+    ENTER(c);
+    if (!dX || !dy || !dXs || !d_mean || !d_info) return gpmi_fail(GPMI_EARG, "NULL argument");
+    int rc;
+    if ((rc = predict_check(n, ldx, D, alpha, sigma, m, ldxs))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    return predict_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dXs, m, ldxs, d_mean, d_var, d_info);
+}
+
+extern "C" int gpmi_gp_predict(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double alpha, const double *ell,
+                               int n_ell, double sigma, double jitter, const double *Xs, int m, int ldxs, double *mean, double *var)
+{
+    ENTER(c);
+    if (!X || !y || !Xs || !mean) return gpmi_fail(GPMI_EARG, "NULL argument");
+    int rc;
+    if ((rc = predict_check(n, ldx, D, alpha, sigma, m, ldxs))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    const double diag_add = sigma * sigma + jitter;
+    if (small_predict(c, n, m, D)) {
+        // the reference's sizes: ONE launch; X, Xs, y go in and mean, var, info come back through the pinned, device-mapped
+        // buffer (no copy call): layout [info, flag | mean (m) | var (m) | X (n D) | Xs (m D) | y (n)]
+        const size_t o_mean = 8, o_var = o_mean + m, o_X = o_var + m, o_Xs = o_X + (size_t)n * D, o_y = o_Xs + (size_t)m * D;
+        if ((rc = pin_reserve(c, (o_y + n) * sizeof(double)))) return rc;
+        double *h = c->h_pin, *pd = c->h_pin_dev;
+        for (int d = 0; d < D; ++d) {
+            memcpy(h + o_X + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
+            memcpy(h + o_Xs + (size_t)d * m, Xs + (size_t)d * ldxs, (size_t)m * sizeof(double));
+        }
+        memcpy(h + o_y, y, (size_t)n * sizeof(double));
+        if ((rc = reserve_ws_small(c, n + m, 1))) return rc;
+        const int seq = ++c->pin_seq;
+        launch_gp_predict_small(c->stream, pd + o_X, n, n, pd + o_Xs, m, m, pd + o_y, p, diag_add, c->W, pd + o_mean,
+                                var ? pd + o_var : nullptr, (int *)pd, c->d_info, (int *)(pd + 7), seq);
+        HIPCHK(hipGetLastError());
+        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
+        memcpy(mean, h + o_mean, (size_t)m * sizeof(double));
+        if (var) memcpy(var, h + o_var, (size_t)m * sizeof(double));
+        return *(const int *)h;
+    }
+    double *dX, *dy, *dXs;
+    if ((rc = stage_buf(c, 3, ((size_t)m * D + 2 * (size_t)m) * sizeof(double), &dXs))) return rc;
+    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
+    if ((rc = h2d_matrix(c, Xs, m, D, ldxs, dXs))) return rc;
+    double *dmean = dXs + (size_t)m * D, *dvar = var ? dmean + m : nullptr;
+    if ((rc = predict_core(c, dX, n, n, dy, p, diag_add, dXs, m, m, dmean, dvar, c->d_info + 1))) return rc;
+    int info = 0;
+    HIPCHK(hipMemcpyAsync(mean, dmean, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, dvar, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&info, c->d_info + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return info;
+}
+
 // ---- sample_derivs: one draw of the derivative process, fused on the device --------------------
 // pendulum_fit.R:227-255 (lorenz.Rmd:80-107 with separate prediction times): K = a^2 QQ(ti, ti),
 // KsK = a^2 RQ(tis, ti), KsKs = a^2 RR(tis, tis); mu = KsK (K + sy^2 I)^-1 y (:242-245);
@@ -3477,6 +3619,42 @@ extern "C" int gpmi_seq_commit(gpmi_seq *q, double dot_xs)
 }
 
 extern "C" int gpmi_seq_count(const gpmi_seq *q) { return q ? q->i : 0; }
+
+// The first step of a FRESH sampler at each of the m rows of Xs (R/tests.R:89-97 builds a sampler per state and takes only
+// its first step), from the stored factor, B and b: t_j = L^-1 k_j, mean_j = t_j . b, var_j = k(xs, xs) + jitter - t_j^T B t_j.
+// Blocked chain in the context's workspace (chunks of mb rows: T, then W = T B^T beside it); the sampler is only read.
+extern "C" int gpmi_seq_marginals(gpmi_seq *q, const double *Xs, int m, int ldxs, double *mean, double *var)
+{
+    if (!q) return gpmi_fail(GPMI_EARG, "sampler is NULL");
+    gpmi_ctx *c = q->c;
+    ENTER(c);
+    if (!Xs || !mean || !var || m < 1 || ldxs < m) return gpmi_fail(GPMI_EARG, "bad argument");
+    const int n = q->n, D = q->D;
+    hipStream_t s = c->stream;
+    int rc;
+    const int mb = predict_chunk_rows(c, n, m), mbp = ((mb + 15) / 16) * 16;
+    if ((rc = reserve_ws(c, 2 * mbp, n))) return rc;
+    const size_t ld = (size_t)c->ld;
+    double *dXs, *part;
+    if ((rc = stage_buf(c, 3, ((size_t)m * D + 2 * (size_t)m) * sizeof(double), &dXs))) return rc;
+    if ((rc = stage_buf(c, 2, predict_rows_part_doubles(n, mb) * sizeof(double), &part))) return rc;
+    double *dmean = dXs + (size_t)m * D, *dvar = dmean + m;
+    if ((rc = h2d_matrix(c, Xs, m, D, ldxs, dXs))) return rc;
+    double *T = c->W, *TB = c->W + mbp;
+    for (int j0 = 0; j0 < m; j0 += mb) {
+        const int mc = (m - j0 < mb) ? m - j0 : mb;
+        launch_se_cov(c, s, dXs + j0, mc, m, q->dX, n, n, q->p, 0.0, 0, T, ld);
+        if ((rc = launch_trsm_right(c, q->L, q->ldm, n, T, ld, mc, q->Fall))) return rc;
+        launch_gemm_nt(c, s, T, ld, q->B, q->ldm, TB, ld, mc, n, n, 0);   // B is stored symmetric: T B^T = T B
+        launch_predict_rows(s, T, ld, TB, ld, q->a, 1, n, mc, q->p.a2 + q->jitter, part, dmean + j0, dvar + j0, nullptr, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(mean, dmean, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(var, dvar, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 
 // ---- diagnostics ---------------------------------------------------------------
 extern "C" int gpmi_last_timing(gpmi_ctx *c, double *ms3)

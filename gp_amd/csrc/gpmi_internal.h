@@ -40,6 +40,8 @@ struct gpmi_tuning {
     int grad_aug_n, grad_aug_ng;  // gpmi_logml_grad / _grid: K^-1 and K^-1 y from one augmented partial factorisation up to this n (0: off)
     int small_vjp;           // gpmi_exact_gp_f_vjp[_dev]: one workgroup, one launch, up to n <= small_vjp (<= 256, D <= GPMI_MAXD, k <= GPMI_VJP_KMAX; 0: off)
     int small_gc;            // gpmi_gp_condition: one workgroup, one launch, up to n + m + 1 <= small_gc rows (0: off)
+    int small_pr;            // gpmi_gp_predict[_dev]: one workgroup, one launch, up to n + m + 1 <= small_pr rows and D <= GPMI_MAXD (0: off)
+    int predict_mb;          // gpmi_gp_predict / gpmi_seq_marginals: rows of Xs per chunk of the blocked chain (0: auto)
     int small_sd, small_sdb; // sample_derivs_batch: one workgroup per draw when n + m + 1 <= small_sd rows and at least small_sdb (n + m + 1)^2 / 400^2 draws (0: off)
     int small_n2, small_g2;  // grids of >= small_g2 (n / 1024)^2 + 2 points: one workgroup per point up to n <= small_n2 (every CU a problem of its own)
 };
@@ -224,6 +226,11 @@ void launch_sample_derivs_small_batch(hipStream_t s, const double *dt, int n, co
 void launch_gp_condition_small(hipStream_t s, const double *t, int n, const double *ts, int m, const double *y, int kindK, int kindS,
                                int kindSS, int compat, double a2, double l2, double s2, double jitter, double *W, double *Kn, size_t ldo,
                                double *mn, int *info_out, int *d_info_work, double *stage, int *done = nullptr, int seq = 0);
+// gp_predict by one workgroup (workspace: one slice of small_ws_layout(n + m), D <= GPMI_MAXD); every pointer but W and
+// d_info_work may be host-mapped (each input is read once: no staging copy); var nullable
+void launch_gp_predict_small(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const double *y,
+                             const SeParams &p, double diag_add, double *W, double *mean, double *var, int *info_out, int *d_info_work,
+                             int *done = nullptr, int seq = 0);
 // f = chol(K + diag_add I) z by one workgroup (n <= 256, D <= GPMI_MAXD); X, z / f, info_out may be host-mapped (stage != null)
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,
                            double *W, double *f, int *info_out, int *d_info_work, double *stage, int *done = nullptr, int seq = 0);
@@ -284,3 +291,23 @@ void launch_syrk_probe(const gpmi_ctx *c, hipStream_t s, const double *P, size_t
 void launch_probe_mfma(hipStream_t s, const double *A, const double *B, double *D);
 void launch_probe_peak(hipStream_t s, double *sink, int iters, int *blocks, int *threads);
 #endif
+
+// ---- kernel launchers (predict_kernels.hip): the ends of the prediction chains ------------------------------
+#define GPMI_PRED_SLICE 512      // columns of T per partial sum of the fused row reduction
+#define GPMI_PRED_KSLICE 256     // training points per partial sum of the fused build-and-contract kernel
+#define GPMI_PRED_BWD 64         // block order of the backward substitution
+// doubles of `part` the two reductions need for mrows rows / m test points against n columns / training points
+size_t predict_rows_part_doubles(int n, int mrows);
+size_t predict_mean_part_doubles(int n, int m);
+// mean[j] = T_j . v and var[j] = base - T_j . U_j over the n columns of the rows j < mrows of T (ldt) and U (ldu; U == T gives
+// the squared norm), v[i * vstride]; slice partials, then their sum in slice order: identical bits on every call.  info
+// (nullable, device): non-zero -> NaN outputs; info_out (nullable) receives it.  var nullable.
+void launch_predict_rows(hipStream_t s, const double *T, size_t ldt, const double *U, size_t ldu, const double *v, size_t vstride,
+                         int n, int mrows, double base, double *part, double *mean, double *var, const int *info, int *info_out);
+// a = L^-T z (z: n contiguous doubles, overwritten with intermediate values; a: n doubles) by a chain of one launch per block
+// of GPMI_PRED_BWD columns, last block first: diagonal-block back-substitution by one wave, then z[0 .. k0) -= L[k, 0 .. k0)^T a_k
+// by wave-wide sums of a fixed shape
+void launch_trsv_lower_t(hipStream_t s, const double *L, size_t ldl, int n, double *z, double *a);
+// mean[j] = sum_i k(xs_j, x_i) a_i without storing the cross-covariance: entries as gpmi_se_cov writes them
+void launch_predict_mean(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const SeParams &p,
+                         const double *a, double *part, double *mean, const int *info, int *info_out);

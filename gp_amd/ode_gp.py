@@ -39,6 +39,15 @@ def p_dotXn(tn, Xn, phi_n, sigma_n, joint=False, compat=None, ctx=None):
     return _ret(mn, Kn)
 
 
+def p_fXs(X, y, theta, sigma, Xs, jitter=0.0, want_var=True, ctx=None):
+    """Pointwise posterior of the latent function at new D-dimensional inputs Xs (m x D) given noisy values y at X (N x D):
+    mean = K_sX (K_XX + (sigma^2 + jitter) I)^-1 y, var = alpha^2 - diag(K_sX (K_XX + (sigma^2 + jitter) I)^-1 K_Xs) with
+    K = QQard(., ., theta) (R/kernels.R:11-19) -- p_Xn's moments at new inputs, any D, without the m x m covariance.
+    theta = (alpha, length-scale(s)) as for logml.  Returns {"mean", "var" (None without want_var), "info"}."""
+    a, l = _k._phi(theta)
+    return (ctx or default_context()).gp_predict(X, y, a, l, float(sigma), jitter, Xs, want_var=want_var)
+
+
 # R/ode_gp_library.R:83 draws rnorm(1, condMean, condVar): the conditional VARIANCE is passed
 # where rnorm expects a standard deviation.  False = the intended draw (sd = sqrt(condVar));
 # True reproduces the file as written.  The returned `sigma` is condVar either way, as in the
@@ -69,4 +78,7 @@ def create_p_dotXnS(Xn_list, mn, Kn, theta, rng=None, compat_sd=None, max_steps=
         return {"mu": mu, "sigma": var, "dot_xs": dot_xs}
 
     p_dotXnS.sampler = smp
+    # the sweep of R/tests.R:89-97 (a fresh sampler per state, first step only) in one call: (mean, var) at the rows of Xs
+    # with no draw committed; reads the sampler, changes nothing in it
+    p_dotXnS.marginals = smp.marginals
     return p_dotXnS

@@ -88,7 +88,9 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * "nb_thr1024", "nb_thr512", "nb_thr256", "small_n", "small_n1", "small_m" (one-workgroup kernels for small
  * problems), "small_ng1", "small_ng" (value + gradient by one workgroup: one evaluation up to n <= small_ng1, several at once
  * up to n <= small_ng <= 256), "grad_aug_n", "grad_aug_ng" (value + gradient through ONE augmented partial factorisation up
- * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_vjp" (gpmi_exact_gp_f_vjp[_dev] by
+ * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_pr" (gpmi_gp_predict[_dev] in
+ * one launch up to n + m + 1 <= small_pr rows and D <= 8; 0 sends every size to the blocked chain), "predict_mb" (rows of Xs per chunk of the
+ * chains of gpmi_gp_predict / gpmi_seq_marginals; 0 = auto, about n / 4), "small_vjp" (gpmi_exact_gp_f_vjp[_dev] by
  * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
  * n + m + 1 <= small_sd rows for at least small_sdb ((n + m + 1) / 400)^2 draws), "small_n2", "small_g2" (grids of at least small_g2 (n / 1024)^2 + 2 points run one workgroup per point up
  * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing"; unknown names return GPMI_EARG.  Switches of variants that
@@ -331,6 +333,27 @@ GPMI_API int gpmi_gp_condition(gpmi_ctx *ctx, const double *t, int n, const doub
                       const double *y, double alpha, double l, double s2, double jitter,
                       int kindK, int kindS, int kindSS, int flags, double *mn, double *Kn, int ldkn);
 
+/* Pointwise posterior of the latent function at m new D-dimensional inputs Xs (m x D, column-major, ldxs) under the ARD
+ * squared-exponential model of gpmi_logml: Sigma = K(X, X) + (sigma^2 + jitter) I = L L^T (exactly gpmi_logml's matrix, so fitted
+ * hyper-parameters go in unchanged), k_j = K(X, xs_j),
+ *   mean[j] = k_j^T Sigma^-1 y,   var[j] = alpha^2 - k_j^T Sigma^-1 k_j.
+ * var is the LATENT function's variance (the caller adds sigma^2 for a new observation) and is returned AS COMPUTED, not
+ * clamped: where the posterior is tight it is a difference of O(alpha^2) terms and may come out as a tiny negative number.
+ * This is what create_p_dotXnS conditions on (QQard(X, X, theta) with D = ncol(X), R/ode_gp_library.R:43-93) and the D-dimensional
+ * counterpart of the (QQ, QQ, QQ) case of gpmi_gp_condition without the m x m covariance: one factorisation of order n, Xs in
+ * chunks (any m).  var == NULL: the mean alone through a = Sigma^-1 y and a fused kernel evaluation, no n^2 m solve.
+ * n + m + 1 <= small_pr rows and D <= 8: one launch of one workgroup.  ell / n_ell as in gpmi_se_cov.  All sums run in a fixed
+ * order: repeated calls give identical bits.  Returns 0, or the order k of the first non-positive leading minor of Sigma (mean and
+ * var are all NaN then).  GPMI_EARG: n or m < 1, D outside 1..64, ldx < n, ldxs < m, alpha <= 0, a length-scale <= 0, sigma < 0, a
+ * NULL pointer other than var. */
+GPMI_API int gpmi_gp_predict(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, const double *y,
+                    double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                    const double *Xs, int m, int ldxs, double *mean /* m */, double *var /* m, nullable */);
+/* the same with device-resident X, y, Xs, mean, var (nullable) and d_info (1 int), enqueued on the context's stream (ell: host) */
+GPMI_API int gpmi_gp_predict_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                        double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                        const double *dXs, int m, int ldxs, double *d_mean, double *d_var /* nullable */, int *d_info);
+
 /* One draw of the derivative process given noisy values: sample_derivs(params = (l, a, sy), ynoise, ti),
  * pendulum_fit.R:227-255 (separate prediction times ts: lorenz.Rmd:80-107, jitter 1e-6 there, 1e-8 here):
  * draw = mu + chol(cov) z with the (QQ, RQ, RR) moments of gpmi_gp_condition, fused on the device -- the
@@ -371,6 +394,13 @@ GPMI_API int gpmi_seq_step(gpmi_seq *seq, const double *xs /* D */, double *out2
 GPMI_API int gpmi_seq_commit(gpmi_seq *seq, double dot_xs);
 GPMI_API int gpmi_seq_count(const gpmi_seq *seq); /* committed draws */
 GPMI_API int gpmi_seq_destroy(gpmi_seq *seq);
+/* For each of the m rows of Xs (m x D, column-major, ldxs): what gpmi_seq_step would return as out2 on a sampler with NO
+ * committed draws -- the sweep of R/tests.R:89-97, which builds a fresh sampler per state and takes only its first step, in one
+ * call and without a factorisation.  With the stored factor L, B = I - L^-1 Kn L^-T, b = L^-1 mn and t_j = L^-1 k_j:
+ *   mean[j] = t_j . b,   var[j] = k(xs, xs) + jitter - t_j^T B t_j   (as computed, not clamped).
+ * The sampler is only read: committed draws, a pending step and gpmi_seq_count stay as they were.  Returns 0 (there is no joint
+ * factor, hence no positive-definiteness status), or GPMI_EARG: m < 1, ldxs < m, a NULL pointer. */
+GPMI_API int gpmi_seq_marginals(gpmi_seq *seq, const double *Xs, int m, int ldxs, double *mean, double *var);
 
 /* ---- diagnostics (tests / bench) -------------------------------------- */
 

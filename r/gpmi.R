@@ -172,3 +172,19 @@ create_p_dotXnS <- function(Xn_list, mn, Kn, theta, max_steps = 256L) {
     list(mu = r[1], sigma = r[2], dot_xs = dot_xs)
   }
 }
+
+# the sweep of R/tests.R:89-97 -- a fresh sampler per new state, first step only -- in one call on a sampler made by
+# create_p_dotXnS: list(mean, var) at the rows of Xs with no draw committed; the sampler is left as it was
+p_dotXnS_marginals <- function(p_dotXnS, Xs) {
+  e <- environment(p_dotXnS)
+  r <- .Call("gpmi_R_seq_marginals", e$h, as.matrix(Xs) + 0.0, ncol(e$X))
+  list(mean = r[[1]], var = r[[2]])
+}
+
+# posterior mean and variance of the latent function at new inputs Xs (m x D) under QQard(X, X, theta) + (sigma^2 + jitter) I,
+# the matrix create_p_dotXnS conditions on (R/ode_gp_library.R:43-93) and gp_log_marginal factors: list(mean, var); var is the
+# latent variance as computed (add sigma^2 for a new observation)
+gp_predict <- function(X, y, alpha, rho, sigma, Xs, jitter = 0) {
+  r <- .Call("gpmi_R_gp_predict", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter, as.matrix(Xs) + 0.0)
+  list(mean = r[[1]], var = r[[2]])
+}

@@ -421,6 +421,25 @@ SEXP gpmi_R_gp_condition(SEXP t, SEXP ts, SEXP y, SEXP alpha, SEXP l, SEXP s2, S
     return out;
 }
 
+/* list(mean, var): pointwise posterior of the latent function at the rows of Xs under QQard(X, X, theta) + (sigma^2 + jitter) I
+ * (what create_p_dotXnS conditions on, R/ode_gp_library.R:43-93); var is alpha^2 - k' Sigma^-1 k as computed */
+SEXP gpmi_R_gp_predict(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter, SEXP Xs)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), m = Rf_nrows(Xs);
+    need(is_real(X) && is_real(y) && is_real(ell) && is_real(Xs), "X, y, the length-scales and Xs must be double");
+    need(Rf_length(y) == n, "length(y) must equal nrow(X)");
+    need(Rf_ncols(Xs) == D, "Xs must have ncol(X) columns");
+    need(Rf_length(ell) == 1 || Rf_length(ell) == D, "length-scale must have length 1 or ncol(X)");
+    SEXP mean = PROTECT(Rf_allocVector(REALSXP, m)), var = PROTECT(Rf_allocVector(REALSXP, m));
+    int rc = gpmi_gp_predict(ctx(), REAL(X), n, n, D, REAL(y), Rf_asReal(alpha), REAL(ell), Rf_length(ell), Rf_asReal(sigma),
+                             Rf_asReal(jitter), REAL(Xs), m, m, REAL(mean), REAL(var));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, mean); SET_VECTOR_ELT(out, 1, var);
+    UNPROTECT(3);
+    check(rc);
+    return out;
+}
+
 /* sample_derivs(params, ynoise, ti): pendulum_fit.R:227-255, one draw mu + chol(cov) z fused on the device; z = rnorm(m)
  * comes from R's own RNG (the reference's MASS::mvrnorm stream cannot be reproduced: eigen-decomposition draw) */
 SEXP gpmi_R_sample_derivs(SEXP t, SEXP ts, SEXP y, SEXP params, SEXP jitter, SEXP z)
@@ -504,6 +523,23 @@ SEXP gpmi_R_seq_step(SEXP ptr, SEXP xs, SEXP D)
     SEXP out = PROTECT(Rf_allocVector(REALSXP, 2)); /* condMean, condVar */
     int rc = gpmi_seq_step(q, REAL(xs), REAL(out));
     UNPROTECT(1);
+    check(rc);
+    return out;
+}
+
+/* list(mean, var): for every row of Xs the first step of a fresh sampler -- the sweep of R/tests.R:89-97 in one call; the
+ * sampler is left as it was */
+SEXP gpmi_R_seq_marginals(SEXP ptr, SEXP Xs, SEXP D)
+{
+    gpmi_seq *q = (gpmi_seq *)R_ExternalPtrAddr(ptr);
+    need(q != NULL, "the sampler has been released");
+    int m = Rf_nrows(Xs);
+    need(is_real(Xs) && Rf_ncols(Xs) == Rf_asInteger(D), "Xs must be a double matrix with one column per input dimension");
+    SEXP mean = PROTECT(Rf_allocVector(REALSXP, m)), var = PROTECT(Rf_allocVector(REALSXP, m));
+    int rc = gpmi_seq_marginals(q, REAL(Xs), m, m, REAL(mean), REAL(var));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, mean); SET_VECTOR_ELT(out, 1, var);
+    UNPROTECT(3);
     check(rc);
     return out;
 }
