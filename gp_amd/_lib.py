@@ -22,6 +22,7 @@ SYMBOLS = (
     "gpmi_se_cov", "gpmi_se_cov_dev", "gpmi_deriv_cov", "gpmi_deriv_cov_dev", "gpmi_deriv_elem",
     "gpmi_joint_cov", "gpmi_potrf", "gpmi_potrf_dev", "gpmi_trmv_lower", "gpmi_trsv_lower", "gpmi_exact_gp_f",
     "gpmi_trmv_lower_t", "gpmi_exact_gp_f_vjp", "gpmi_exact_gp_f_vjp_dev", "gpmi_latent_gp_lp_grad", "gpmi_latent_gp_lp_grad_dev",
+    "gpmi_centered_gp_lp_grad", "gpmi_centered_gp_lp_grad_dev",
     "gpmi_logml", "gpmi_logml_dev", "gpmi_logml_grid", "gpmi_logml_grid_dev", "gpmi_logml_grid_ard", "gpmi_logml_grid_ard_dev",
     "gpmi_joint_logml", "gpmi_joint_logml_dev", "gpmi_joint_logml_grid_dev", "gpmi_rbf_cov_chol", "gpmi_gp_condition", "gpmi_sample_derivs", "gpmi_sample_derivs_batch",
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
@@ -131,11 +132,14 @@ def _mat(X):
 
 
 LIK_FAMILIES = {"normal": 0, "bernoulli_logit": 1, "normal_logsd": 2}   # GPMI_LIK_*
+LIK_NONE = 3    # GPMI_LIK_NONE ("none"): no head, the prior part alone -- gpmi_centered_gp_lp_grad[_dev] only
 
 
 def lik_family(family):
     """GPMI_LIK_* of a family name; integers pass through (the library rejects unknown ones)."""
     if isinstance(family, str):
+        if family == "none":
+            return LIK_NONE
         if family not in LIK_FAMILIES:
             raise GpmiError(-1, "unknown likelihood family %r" % (family,))
         return LIK_FAMILIES[family]
@@ -331,6 +335,37 @@ class Context:
         sq = (lambda A: None if A is None else (A[:, 0] if one else A))
         return {"lik": float(out[0]), "dlik_dsigma": float(out[1]), "F": sq(F), "Fbar": sq(Fb), "Zbar": sq(Zb), "grad": g,
                 "info": int(info)}
+
+    def centered_gp_lp_grad(self, X, alpha, ell, F, family, Y=None, sigma=None, jitter=1e-9, raise_not_pd=True):
+        """The centred latent GP's log-density and gradient with one factorisation (gpmi_centered_gp_lp_grad): the columns of F
+        (n or n x k) are parameters with the prior multi_normal_cholesky(0, chol(cov_exp_quad(X, alpha, ell) + jitter I)), and the
+        head `family` ("normal", "bernoulli_logit", "normal_logsd", or "none": the prior alone, any k) is evaluated on F against
+        the columns of Y (n or n x m).  Returns a dict: lp = prior + lik, prior = -quad / 2 - k sum_log_diag, lik, dlik_dsigma,
+        sum_log_diag, quad = sum_c f_c' Sigma^-1 f_c, Fgrad = d lp / d F (in F's shape), grad = (d/dalpha, d/dell...) of the prior,
+        info.  Not positive definite: raises NotPositiveDefinite, or with raise_not_pd=False returns the NaN outputs and info =
+        the minor's order."""
+        X = _mat(X); ell = _vec(ell)
+        n, D = X.shape
+        one = np.ndim(F) == 1
+        Fm = _mat(F)
+        fam = lik_family(family)
+        none = fam == LIK_NONE
+        if not none and Y is None:
+            raise GpmiError(-1, "the %s head needs Y" % family)
+        Ym = None if none else _mat(Y)
+        if Fm.shape[0] != n or (Ym is not None and Ym.shape[0] != n):
+            raise GpmiError(-1, "X, F and Y disagree on N")
+        k = Fm.shape[1]; m = 0 if none else Ym.shape[1]
+        if fam == LIK_FAMILIES["normal"] and sigma is None:
+            raise GpmiError(-1, "the normal head needs sigma")
+        Fg = np.empty((n, k), order="F"); g = np.empty(1 + ell.size); out = np.empty(4)
+        ld = max(n, 1)
+        info = _chk(self._lib.gpmi_centered_gp_lp_grad(self._h, _p(X), n, ld, D, _d(alpha), _p(ell), int(ell.size), _d(jitter), _p(Fm),
+                                                       k, ld, fam, None if none else _p(Ym), m, ld, _d(0.0 if sigma is None else sigma),
+                                                       _p(out), _p(Fg), ld, _p(g)), allow_info=not raise_not_pd)
+        prior = -0.5 * out[3] - k * out[2]
+        return {"lp": float(out[0]), "prior": float(prior), "lik": float(out[0] - prior), "dlik_dsigma": float(out[1]),
+                "sum_log_diag": float(out[2]), "quad": float(out[3]), "Fgrad": Fg[:, 0] if one else Fg, "grad": g, "info": int(info)}
 
     # ---- marginal likelihood -------------------------------------------------
     def logml(self, X, y, alpha, ell, sigma, jitter=0.0):
@@ -623,6 +658,17 @@ class Context:
                                                   C.c_void_p(dout_ptr), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
                                                   C.c_void_p(dFbar_ptr) if dFbar_ptr else None, int(ldfb), C.c_void_p(dZbar_ptr),
                                                   int(ldzb), C.c_void_p(dgrad_ptr), C.c_void_p(dinfo_ptr)))
+
+    def centered_gp_lp_grad_dev(self, dX_ptr, n, ldx, D, alpha, ell, jitter, dF_ptr, k, ldf, family, dY_ptr, m, ldy, sigma, dout_ptr,
+                                dFgrad_ptr, ldfg, dgrad_ptr, dinfo_ptr):
+        """gpmi_centered_gp_lp_grad_dev on device pointers (dY_ptr may be None with "none"; dout: 4 doubles); enqueued, not
+        synchronised."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_centered_gp_lp_grad_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), _d(alpha), _p(ell),
+                                                    int(ell.size), _d(jitter), C.c_void_p(dF_ptr), int(k), int(ldf), lik_family(family),
+                                                    C.c_void_p(dY_ptr) if dY_ptr else None, int(m), int(ldy),
+                                                    _d(0.0 if sigma is None else sigma), C.c_void_p(dout_ptr), C.c_void_p(dFgrad_ptr),
+                                                    int(ldfg), C.c_void_p(dgrad_ptr), C.c_void_p(dinfo_ptr)))
 
     def logml_grid_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, rho, sigma, jitter, dout_ptr, dinfo_ptr):
         a = _vec(alpha); r = _vec(rho); s = _vec(sigma)

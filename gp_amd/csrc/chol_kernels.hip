@@ -3024,6 +3024,271 @@ __global__ __launch_bounds__(256, 2) void k_latent_gp_small(const double *__rest
                                   info_w, ec, stage, done, seq, lh, out);
 }
 
+// The CENTRED latent GP (models/heteroscedastic_centered.stan:24-34; gpmi_centered_gp_lp_grad) by ONE workgroup for n <= 256,
+// D <= GPMI_MAXD, k <= CEN_KMAX: the k latent columns are parameters with the GP as their prior.  logml_grad_small_body with k
+// augmented rows instead of one:
+//   build; F^T rides as rows n .. n + k - 1 of the partial factorisation and comes out as Z^T, U = L^-T rides along
+//   (small_potrf_partial<true>); sum log L_ii and sum_c z_c'z_c by the tree of k_logml_partial;
+//   a_c = U z_c for all columns in one pass over U (thread = row); the head on this thread's row of F, Fgrad = Fbar - a;
+//   Sigma^-1 = U U^T tile by tile, contracted in registers with g_ij = 1/2 (sum_c a_ic a_jc - k Sigma^-1_ij) against dSigma/dtheta.
+// W: n + k rows; out (4), Fg (n x k, ldfg), grad (1 + n_ell) and info_out may be host-mapped (stage != null: n (D + k + m)
+// doubles of device scratch receive X, F and Y in one coalesced pass).  The gradient is finished on the device.
+constexpr int CEN_KMAX = GPMI_CEN_KMAX;
+__global__ __launch_bounds__(256, 2) void k_centered_gp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
+                                                           const double *__restrict__ F, int k, int ldf, LatentHead lh,
+                                                           double *__restrict__ out, double *__restrict__ Fg, int ldfg,
+                                                           double *__restrict__ W, double *__restrict__ U, size_t ld, double alpha,
+                                                           VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                           int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
+{
+    GPMI_SMALL_LDS
+    int tid = threadIdx.x;
+    const bool head = lh.family != GPMI_LIK_NONE;
+    if (stage) {   // host-mapped X, F, Y: one coalesced pass into device memory
+        const int nx = n * p.D, nf = n * k, ny = head ? n * lh.m : 0;
+        for (int e = tid; e < nx + nf + ny; e += 256) {
+            if (e < nx) {
+                const int d = e / n, i = e - d * n;
+                stage[e] = X[(size_t)i + (size_t)d * ldx];
+            } else if (e < nx + nf) {
+                const int c = (e - nx) / n, i = e - nx - c * n;
+                stage[e] = F[(size_t)i + (size_t)c * ldf];
+            } else {
+                const int c = (e - nx - nf) / n, i = e - nx - nf - c * n;
+                stage[e] = lh.Y[(size_t)i + (size_t)c * lh.ldy];
+            }
+        }
+        __syncthreads();
+        X = stage;
+        F = stage + nx;
+        ldx = ldf = n;
+    }
+    if (tid == 0) *info_w = 0;
+    SmallSe se;
+    se.a2 = p.a2;
+    se.D = p.D;
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
+    {
+        double *xs = &smem[0][0][0][0];
+#pragma unroll
+        for (int d = 0; d < GPMI_MAXD; ++d)
+            if (d < se.D)
+                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
+        __syncthreads();
+        for (int row0 = 0; row0 < n; row0 += SE_TR)
+            for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
+                switch (se.D) {
+                case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
+                }
+            }
+    }
+    for (int c = 0; c < k; ++c)   // F^T as rows n .. n + k - 1
+        for (int j = tid; j < n; j += 256) W[(size_t)(n + c) + (size_t)j * ld] = F[(size_t)j + (size_t)c * ldf];
+    {   // U = I (as logml_grad_small_body)
+        const int rp = 2 * (tid & 127), cp = tid >> 7;
+        if (rp < n)
+            for (int j = cp; j < n; j += 2) *reinterpret_cast<double2 *>(U + (size_t)rp + (size_t)j * ld) = make_double2(0.0, 0.0);
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) U[(size_t)i * (ld + 1)] = 1.0;
+    }
+    __syncthreads();
+    small_potrf_partial<true>(smem, s_F, s_aux, W, ld, n + k, n, n, info_w, k == 1, U);
+    __syncthreads();
+    asm volatile("" : "+v"(tid));
+    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the packed factors are no longer needed: s_F holds the scaled coordinates, A = Sigma^-1 F and Z, k n doubles each
+    double *xg = s_F, *s_av = s_F + 2048, *s_z = s_F + 4096;
+    double *s_a = s_aux, *s_b = s_aux + 256;
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d)
+        if (d < se.D)
+            for (int i = tid; i < n; i += 256) xg[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
+    {   // value: one slice (n <= 256), the tree of k_logml_partial; the squares of a row's k entries of Z in column order
+        double a = 0.0, b = 0.0;
+        if (tid < n) {
+            a = log(W[(size_t)tid * (ld + 1)]);
+            for (int c = 0; c < k; ++c) {
+                const double z = W[(size_t)(n + c) + (size_t)tid * ld];
+                s_z[c * n + tid] = z;
+                b += z * z;
+            }
+        }
+        s_a[tid] = a;
+        s_b[tid] = b;
+        __syncthreads();
+        for (int st = 128; st > 0; st >>= 1) {
+            if (tid < st) {
+                s_a[tid] += s_a[tid + st];
+                s_b[tid] += s_b[tid + st];
+            }
+            __syncthreads();
+        }
+    }
+    const double sum_log = s_a[0], zz = s_b[0];
+    __syncthreads();   // (s_a, s_b are written again below)
+    // A = U Z (U upper triangular: the columns left of a wave's first row are zero): one pass over U for all k columns,
+    // sixteen loads in flight per round trip
+    double av[CEN_KMAX];
+#pragma unroll
+    for (int c = 0; c < CEN_KMAX; ++c) av[c] = 0.0;
+    {
+        const int ir = tid < n ? tid : n - 1;
+        for (int j0 = tid & ~63; j0 < n; j0 += 16) {
+            double u[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int j = j0 + q < n ? j0 + q : n - 1;
+                u[q] = U[(size_t)ir + (size_t)j * ld];
+            }
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if (j0 + q < n)
+#pragma unroll
+                    for (int c = 0; c < CEN_KMAX; ++c)
+                        if (c < k) av[c] = fma(u[q], s_z[c * n + j0 + q], av[c]);
+        }
+    }
+    if (tid < n)
+#pragma unroll
+        for (int c = 0; c < CEN_KMAX; ++c)
+            if (c < k) s_av[c * n + tid] = av[c];
+    // the head on this thread's row of F; Fgrad = Fbar - A; lik and d lik / d sigma by a butterfly inside every wave and the
+    // four wave sums added in wave order
+    {
+        double red0 = 0.0, red1 = 0.0, fb0 = 0.0, fb1 = 0.0;
+        if (tid < n) {
+            if (head) {
+                const LatentHead hd{lh.family, stage ? stage + n * (p.D + k) : lh.Y, lh.m, stage ? n : lh.ldy, lh.sigma, lh.log_sigma};
+                latent_head_row(hd, F[tid], k > 1 ? F[(size_t)tid + (size_t)ldf] : 0.0, hd.Y + tid, red0, red1, fb0, fb1);
+            }
+#pragma unroll
+            for (int c = 0; c < CEN_KMAX; ++c)
+                if (c < k) {
+                    const double fb = c == 0 ? fb0 : (c == 1 ? fb1 : 0.0);
+                    Fg[(size_t)tid + (size_t)c * ldfg] = info ? __builtin_nan("") : fb - av[c];
+                }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            red0 += __shfl_xor(red0, off, 64);
+            red1 += __shfl_xor(red1, off, 64);
+        }
+        if ((tid & 63) == 0) {
+            s_b[(tid >> 6) * 2] = red0;
+            s_b[(tid >> 6) * 2 + 1] = red1;
+        }
+    }
+    __syncthreads();   // (also: every row of A is in s_av, the coordinates in xg)
+    const double lik = ((s_b[0] + s_b[2]) + s_b[4]) + s_b[6], dsig = ((s_b[1] + s_b[3]) + s_b[5]) + s_b[7];
+    asm volatile("" : "+v"(tid));
+    // Sigma^-1 = U U^T tile by tile (lower tiles; only the columns >= the tile row's first), contracted where it is produced
+    double acc[1 + GPMI_MAXD];
+#pragma unroll
+    for (int q = 0; q < 1 + GPMI_MAXD; ++q) acc[q] = 0.0;
+    const double a2 = se.a2, kd = (double)k;
+    auto kinv_tiles = [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;   // compile-time dimension count (0: se.D at run time, <= GPMI_MAXD)
+        const int Dn = DT ? DT : se.D;
+        constexpr int DH = DT ? DT : 1;
+        double xm[4][DH], am[4], xn[DH], an = 0.0;
+        int mm[4], ncur = 0;
+        bool okn = false;
+        auto contract = make_epi3(
+            [&](int tm, int m, bool ok) {
+                mm[tm] = ok ? m : -1;           // a row outside the matrix lies above every column: weight 0
+                const int mc = ok ? m : 0;
+                am[tm] = s_av[mc];
+                if constexpr (DT != 0) {
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) xm[tm][d] = xg[mc + d * n];
+                }
+            },
+            [&](int nn, bool ok) {
+                ncur = ok ? nn : 0;
+                okn = ok;
+                an = s_av[ncur];
+                if constexpr (DT != 0) {
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) xn[d] = xg[ncur + d * n];
+                }
+            },
+            [&](double kinv, int tm) {
+                double e = 0.0, r2[GPMI_MAXD];
+                const int mc = mm[tm] < 0 ? 0 : mm[tm];
+#pragma unroll
+                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) {
+                    double r;
+                    if constexpr (DT != 0) r = xm[tm][d] - xn[d];
+                    else r = d < Dn ? xg[mc + d * n] - xg[ncur + d * n] : 0.0;
+                    r2[d] = r * r;
+                    e += r2[d];
+                }
+                const double kse = a2 * exp_nonpos(-0.5 * e, ec);
+                double aa = am[tm] * an;        // sum_c a_mc a_nc, columns in index order (the first pair from registers)
+                for (int c = 1; c < k; ++c) aa += s_av[c * n + mc] * s_av[c * n + ncur];
+                const double g = 0.5 * (aa - kd * kinv);
+                const bool lower = okn && ncur <= mm[tm];
+                const double cc = lower ? ((ncur == mm[tm]) ? 1.0 : 2.0) * g * kse : 0.0;
+                acc[0] += cc;
+#pragma unroll
+                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) acc[1 + d] += cc * r2[d];
+            });
+        for (int ti = 0; ti * GT < n; ++ti)
+            for (int tj = 0; tj <= ti; ++tj) {
+                const int k0 = ti * GT;
+                gemm_tile<3>(smem, U + (size_t)k0 * ld, ld, U + (size_t)k0 * ld, ld, W, ld, n, n, n - k0, ti, tj, 0, (int)threadIdx.x,
+                             contract);
+                __syncthreads();
+            }
+    };
+    switch (se.D) {
+    case 1: kinv_tiles(ic<1>{}); break;
+    case 2: kinv_tiles(ic<2>{}); break;
+    case 3: kinv_tiles(ic<3>{}); break;
+    default: kinv_tiles(ic<0>{}); break;
+    }
+#pragma unroll
+    for (int d = 0; d < GPMI_MAXD; ++d)   // sums over UNSCALED squared differences (layout of k_grad_partial)
+        acc[1 + d] = (d < se.D) ? acc[1 + d] / (se.inv_ell[d] * se.inv_ell[d]) : 0.0;
+    // fixed-shape reduction: butterfly inside every wave, the four wave sums added in wave order
+    double *s_r = s_aux;
+#pragma unroll
+    for (int q = 0; q < 1 + GPMI_MAXD; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if ((tid & 63) == 0) s_r[(tid >> 6) * (1 + GPMI_MAXD) + q] = v;
+    }
+    __syncthreads();
+    if (tid < 1 + GPMI_MAXD) {
+        constexpr int S = 1 + GPMI_MAXD;
+        s_r[4 * S + tid] = ((s_r[tid] + s_r[S + tid]) + s_r[2 * S + tid]) + s_r[3 * S + tid];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double *hs = s_r + 4 * (1 + GPMI_MAXD);
+        const double nan = __builtin_nan("");
+        grad[0] = info ? nan : 2.0 * hs[0] / alpha;
+        if (n_ell == 1) {
+            double t = 0.0;
+            for (int d = 0; d < se.D; ++d) t += hs[1 + d];
+            grad[1] = info ? nan : t / (el.ell[0] * el.ell[0] * el.ell[0]);
+        } else {
+            for (int d = 0; d < se.D; ++d) grad[1 + d] = info ? nan : hs[1 + d] / (el.ell[d] * el.ell[d] * el.ell[d]);
+        }
+        out[0] = info ? nan : (-0.5 * zz - kd * sum_log) + lik;
+        out[1] = info ? nan : dsig;
+        out[2] = info ? nan : sum_log;
+        out[3] = info ? nan : zz;
+        *info_out = info;
+    }
+    small_signal_done(done, seq);
+}
+
 // rbf_cov_chol (covariance.cpp:9-47) by ONE workgroup for n <= 128 (test_interpolate.R:5 runs it at N = 100, P = 10 times):
 // Sigma_ij = exp(-(x_i - x_j)^2 / (2 l^2)) + 1e-10 [i == j], L = chol(Sigma), and the forward-mode tangent
 // dL/dl = L Phi(L^-1 Sdot L^-T), Sdot_ij = Sigma_ij (x_i - x_j)^2 / l^3, Phi = lower triangle with halved diagonal --
@@ -3483,6 +3748,7 @@ static void small_lds_attr()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_vjp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_latent_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_centered_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_cov_chol_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     const int gbytes = SMALL_GRAD_LDS_DOUBLES * (int)sizeof(double);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_grad_small), hipFuncAttributeMaxDynamicSharedMemorySize, gbytes);
@@ -3516,6 +3782,8 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->grad_aug_n = 3072;
     t->grad_aug_ng = 2304;
     t->small_vjp = 256;
+    t->small_cen = 192;   // tools/centered_gp_bench.py (k = 2, normal_logsd, m = 5): one workgroup 68 / 100 / 144 / 261 / 306 / 363 / 392 us at
+                          // n = 10 / 64 / 128 / 160 / 192 / 224 / 256, the blocked chain 188 / 206 / 236 / 309 / 323 / 338 / 339
     t->small_gc = 180;    // gpmi_gp_condition by one workgroup up to n + m + 1 rows (tools/cond_bench.py)
     t->small_pr = 180;    // gpmi_gp_predict by one workgroup up to n + m + 1 rows (tools/predict_bench.py)
     t->predict_mb = 0;    // rows of Xs per chunk of the blocked prediction chain (0: auto, about n / 4)
@@ -4234,6 +4502,21 @@ void launch_latent_gp_small(hipStream_t s, const double *X, int n, int ldx, cons
     hipLaunchKernelGGL(k_latent_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, lh, out,
                        Fb, ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done,
                        seq);
+}
+
+// one workgroup; W: 2 slices of small_ws_layout(n + k - 1) -- the covariance / factor with the k rows of F^T below, then U
+void launch_centered_gp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *F, int k,
+                              int ldf, const LatentHead &lh, double *out, double *Fg, int ldfg, double *W, double alpha,
+                              const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage, int *done,
+                              int seq)
+{
+    size_t ld, stride;
+    small_ws_layout(n + k - 1, &ld, &stride);
+    small_lds_attr();
+    VjpSmallEll el;
+    for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
+    hipLaunchKernelGGL(k_centered_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, F, k, ldf, lh,
+                       out, Fg, ldfg, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
 }
 
 // P <= 64 length-scales, one workgroup each (n <= 128); Wall: 3 P slices of small_ws_layout(n)

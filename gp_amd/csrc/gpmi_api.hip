@@ -424,6 +424,11 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         c->tune.small_vjp = value;
         return 0;
     }
+    if (!strcmp(name, "small_cen")) {  // gpmi_centered_gp_lp_grad by one workgroup up to this n (<= 256; 0: every size takes the chain)
+        if (value < 0 || value > 256) return gpmi_fail(GPMI_EARG, "small_cen must be 0 .. 256");
+        c->tune.small_cen = value;
+        return 0;
+    }
     if (!strcmp(name, "small_gc")) {  // gp_condition by one workgroup up to this many rows n + m + 1 (0: off)
         if (value < 0 || value > 1024) return gpmi_fail(GPMI_EARG, "small_gc must be 0 .. 1024");
         c->tune.small_gc = value;
@@ -2077,9 +2082,12 @@ __global__ __launch_bounds__(256) void k_upper_mv_sum(const double *__restrict__
 constexpr int GRAD_NS = 2 + GPMI_MAXD;           // slots per tile of the D <= 8 kernel
 constexpr int GRAD_NS_MAX = 2 + GPMI_MAXD_BIG;   // ... and the most the generic one writes (D = 64)
 static inline int grad_ns(int D) { return 2 + ((D + 7) / 8) * 8; }
+// KC (gpmi_centered_gp_lp_grad): a holds kc columns (leading dimension lda) and g = (sum_c a_ic a_jc + kc Wij) / 2, the columns
+// added in index order; the plain instance is the statement it always was
+template <bool KC = false>
 __global__ __launch_bounds__(256) void k_grad_partial(const double *__restrict__ X, int n, int ldx, SeParams p,
                                                       const double *__restrict__ a, const double *__restrict__ W,
-                                                      size_t ld, double *__restrict__ part)
+                                                      size_t ld, double *__restrict__ part, int kc, size_t lda)
 {
     __shared__ double red[256];
     const int ti = blockIdx.x, tj = blockIdx.y;
@@ -2105,7 +2113,13 @@ __global__ __launch_bounds__(256) void k_grad_partial(const double *__restrict__
                 e += r2[d] * p.inv_ell[d] * p.inv_ell[d];
             }
             const double kse = p.a2 * exp(-0.5 * e);
-            const double g = 0.5 * (ai * a[j] + W[(size_t)i + (size_t)j * ld]);
+            double g;
+            if constexpr (KC) {
+                double aa = ai * a[j];
+                for (int c = 1; c < kc; ++c) aa += a[(size_t)i + (size_t)c * lda] * a[(size_t)j + (size_t)c * lda];
+                g = 0.5 * (aa + (double)kc * W[(size_t)i + (size_t)j * ld]);
+            } else
+                g = 0.5 * (ai * a[j] + W[(size_t)i + (size_t)j * ld]);
             const double w = (i == j) ? 1.0 : 2.0;
             acc[0] += w * g * kse;
 #pragma unroll
@@ -2133,9 +2147,10 @@ __global__ __launch_bounds__(256) void k_grad_partial(const double *__restrict__
 // over the workgroup, one fixed-shape tree per dimension (deterministic).  Slots per tile: ns = 2 + roundup(D, 8):
 // [0] sum c, [1 + d] per dimension, [ns - 1] the diagonal term -- the layout of k_grad_partial for D <= 8.
 // O(N^2 D) next to the O(N^3) of K^-1: 64 trees per tile at D = 64 are noise.
+template <bool KC = false>
 __global__ __launch_bounds__(256) void k_grad_partial_big(const double *__restrict__ X, int n, int ldx, SeParams p,
                                                           const double *__restrict__ a, const double *__restrict__ W,
-                                                          size_t ld, double *__restrict__ part, int ns)
+                                                          size_t ld, double *__restrict__ part, int ns, int kc, size_t lda)
 {
     __shared__ double sx[16][64], sy[16][64], red[256];
     const int ti = blockIdx.x, tj = blockIdx.y;
@@ -2177,7 +2192,13 @@ __global__ __launch_bounds__(256) void k_grad_partial_big(const double *__restri
         const int j = j0 + q;
         double cq = 0.0;
         if (i < n && j < n && j <= i) {
-            const double g = 0.5 * (a[i] * a[j] + W[(size_t)i + (size_t)j * ld]);
+            double g;
+            if constexpr (KC) {
+                double aa = a[i] * a[j];
+                for (int c = 1; c < kc; ++c) aa += a[(size_t)i + (size_t)c * lda] * a[(size_t)j + (size_t)c * lda];
+                g = 0.5 * (aa + (double)kc * W[(size_t)i + (size_t)j * ld]);
+            } else
+                g = 0.5 * (a[i] * a[j] + W[(size_t)i + (size_t)j * ld]);
             cq = ((i == j) ? 1.0 : 2.0) * g * (p.a2 * exp(-0.5 * e[q]));
             if (i == j) cdiag += g;
         }
@@ -2309,9 +2330,9 @@ static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const 
         const double *av = c->W + (size_t)(n + 1) + (size_t)n * ld;
         const double *Wk = c->W + (size_t)(n + 1) + (size_t)(n + 1) * ld;
         if (p.D <= GPMI_MAXD)
-            hipLaunchKernelGGL(k_grad_partial, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part);
+            hipLaunchKernelGGL(k_grad_partial<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, 1, (size_t)0);
         else
-            hipLaunchKernelGGL(k_grad_partial_big, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, ns);
+            hipLaunchKernelGGL(k_grad_partial_big<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, ns, 1, (size_t)0);
         hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, d_res + 3, ns);
         HIPCHK(hipGetLastError());
         return 0;
@@ -2340,9 +2361,9 @@ static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const 
     HIPCHK(hipMemsetAsync(c->W, 0, ld * (size_t)n * sizeof(double), s));
     launch_syrk_uut(c, s, U, ldu, c->W, ld, n);
     if (p.D <= GPMI_MAXD)   // register-resident coordinates
-        hipLaunchKernelGGL(k_grad_partial, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, c->W, ld, part);
+        hipLaunchKernelGGL(k_grad_partial<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, c->W, ld, part, 1, (size_t)0);
     else                    // any D: LDS-staged coordinates, one pass for the distances and one per dimension
-        hipLaunchKernelGGL(k_grad_partial_big, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, c->W, ld, part, ns);
+        hipLaunchKernelGGL(k_grad_partial_big<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, c->W, ld, part, ns, 1, (size_t)0);
     hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, d_res + 3, ns);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2571,9 +2592,9 @@ static int exact_gp_vjp_core(gpmi_ctx *c, const double *dX, int n, int ldx, cons
     // <Sbar, dK/dtheta>: the gradient contraction with a = 0
     HIPCHK(hipMemsetAsync(zero, 0, (size_t)n * sizeof(double), s));
     if (p.D <= GPMI_MAXD)
-        hipLaunchKernelGGL(k_grad_partial, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part);
+        hipLaunchKernelGGL(k_grad_partial<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part, 1, (size_t)0);
     else
-        hipLaunchKernelGGL(k_grad_partial_big, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part, ns);
+        hipLaunchKernelGGL(k_grad_partial_big<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part, ns, 1, (size_t)0);
     hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, sums, ns);
     VjpEll e;
     for (int d = 0; d < GPMI_MAXD_BIG; ++d) e.ell[d] = d < n_ell ? ell[d] : 0.0;
@@ -2782,6 +2803,254 @@ extern "C" int gpmi_latent_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int l
     if ((rc = d2h_matrix(c, d + o_zb, (size_t)n, n, k, Zbar, ldzb))) return rc;
     HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out, d + o_out, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return info;
+}
+
+// ---- centred latent GP: the k latent columns are parameters, the GP their prior (models/heteroscedastic_centered.stan:24-34) ----
+// prior = sum_c (-1/2 f_c' Sigma^-1 f_c - sum log L_ii), d prior / d F = -Sigma^-1 F = -A, d prior / d theta = 1/2 tr((A A^T - k Sigma^-1)
+// dSigma/dtheta); the head is evaluated on F itself and does not see the hyper-parameters.  The chain is logml_grad_core's with k
+// augmented rows instead of one: F^T rides as rows n .. n + k - 1 of the partial factorisation and comes out as Z^T = (L^-1 F)^T,
+// U = L^-T by the triangular panel substitution from the identity, A = U Z column by column, -Sigma^-1 = -U U^T by the SYRK kernel,
+// the k-column contraction (k_grad_partial[_big]<true>), the head, and one kernel that writes Fgrad = Fbar - A and the results.
+namespace {
+// slice q of 256 pivots: part[2 q] = sum log L_ii, part[2 q + 1] = sum_i sum_c z_ic^2 (columns in index order), the tree of
+// k_logml_partial; Zt: the k rows below L (W + n), Zv (n x k, packed) receives Z
+__global__ __launch_bounds__(256) void k_cen_value_part(const double *__restrict__ W, size_t ld, int n, int k, double *__restrict__ Zv,
+                                                        double *__restrict__ part)
+{
+    __shared__ double s_a[256], s_b[256];
+    const int tid = threadIdx.x, i = blockIdx.x * 256 + tid;
+    double a = 0.0, b = 0.0;
+    if (i < n) {
+        a = log(W[(size_t)i * (ld + 1)]);
+        for (int c = 0; c < k; ++c) {
+            const double z = W[(size_t)(n + c) + (size_t)i * ld];
+            Zv[(size_t)i + (size_t)c * n] = z;
+            b += z * z;
+        }
+    }
+    s_a[tid] = a;
+    s_b[tid] = b;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) {
+            s_a[tid] += s_a[tid + st];
+            s_b[tid] += s_b[tid + st];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        part[2 * (size_t)blockIdx.x] = s_a[0];
+        part[2 * (size_t)blockIdx.x + 1] = s_b[0];
+    }
+}
+
+// Fgrad = Fbar - A (Fb == nullptr: no head, Fbar = 0); thread 0 of block 0 adds the slice sums in slice order and writes
+// out[0..3], the gradient (k_vjp_finish's statement) and the status; not positive definite: NaN everywhere
+__global__ __launch_bounds__(256) void k_cen_finish(const double *__restrict__ A, const double *__restrict__ Fb, int n, int k,
+                                                    double *__restrict__ Fg, size_t ldfg, const double *__restrict__ vpart, int nslice,
+                                                    const double *__restrict__ lik2, const double *__restrict__ hs, int D, double alpha,
+                                                    VjpEll e, int n_ell, const int *__restrict__ info, double *__restrict__ out,
+                                                    double *__restrict__ grad, int *__restrict__ info_out)
+{
+    const bool bad = *info != 0;
+    const double nan = __builtin_nan("");
+    const size_t total = (size_t)n * k;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (size_t)gridDim.x * 256) {
+        const size_t c = q / (size_t)n, i = q - c * (size_t)n;
+        const double fb = Fb ? Fb[q] : 0.0;
+        Fg[i + c * ldfg] = bad ? nan : fb - A[q];
+    }
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double sl = 0.0, zz = 0.0;
+    for (int q = 0; q < nslice; ++q) {
+        sl += vpart[2 * (size_t)q];
+        zz += vpart[2 * (size_t)q + 1];
+    }
+    const double lik = lik2 ? lik2[0] : 0.0, dsig = lik2 ? lik2[1] : 0.0;
+    out[0] = bad ? nan : (-0.5 * zz - (double)k * sl) + lik;
+    out[1] = bad ? nan : dsig;
+    out[2] = bad ? nan : sl;
+    out[3] = bad ? nan : zz;
+    grad[0] = bad ? nan : 2.0 * hs[0] / alpha;
+    if (n_ell == 1) {
+        double t = 0.0;
+        for (int d = 0; d < D; ++d) t += hs[1 + d];
+        grad[1] = bad ? nan : t / (e.ell[0] * e.ell[0] * e.ell[0]);
+    } else {
+        for (int d = 0; d < D; ++d) grad[1 + d] = bad ? nan : hs[1 + d] / (e.ell[d] * e.ell[d] * e.ell[d]);
+    }
+    *info_out = *info;
+}
+}  // namespace
+
+// every buffer of the chain at its final size: c->W (Sigma with the k rows of F^T below, L, then -Sigma^-1), stage[2] = U (ldu),
+// stage[3] = vectors, scratch = the packed factors
+static int centered_gp_reserve(gpmi_ctx *c, int n, int D, int k)
+{
+    int rc;
+    if ((rc = reserve_ws(c, n + k, n))) return rc;
+    const size_t ldu = (size_t)(((n + 15) / 16) * 16 + 16);
+    const int npan = (n + GPMI_NB - 1) / GPMI_NB, nchunk = (n + UMV_COLS - 1) / UMV_COLS, nslice = (n + 255) / 256;
+    const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
+    double *b;
+    if ((rc = stage_buf(c, 2, ldu * (size_t)(n + 1) * sizeof(double), &b))) return rc;
+    const size_t vec = 3 * (size_t)k * n + GRAD_NS_MAX + ntiles * grad_ns(D) + (size_t)nchunk * n + 2 * (size_t)nslice + 2 +
+                       2 * (size_t)latent_head_blocks(n);
+    if ((rc = stage_buf(c, 3, vec * sizeof(double), &b))) return rc;
+    return scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &b);
+}
+
+// The chain, enqueued on c->stream: device X (ldx), F (ldf), the head's Y; d_out (4), dFg (ldfg), d_grad (1 + n_ell), *d_info written
+static int centered_gp_core(gpmi_ctx *c, const double *dX, int n, int ldx, const SeParams &p, double alpha, const double *ell, int n_ell,
+                            double jitter, const double *dF, int k, int ldf, const LatentHead &lh, double *d_out, double *dFg, int ldfg,
+                            double *d_grad, int *d_info)
+{
+    int rc;
+    if ((rc = centered_gp_reserve(c, n, p.D, k))) return rc;
+    const size_t ld = (size_t)c->ld, ldu = (size_t)(((n + 15) / 16) * 16 + 16);
+    const int nchunk = (n + UMV_COLS - 1) / UMV_COLS, nslice = (n + 255) / 256, ns = grad_ns(p.D);
+    const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2, nk = (size_t)n * k;
+    double *U = c->stage[2], *Zv = c->stage[3], *Av = Zv + nk, *Fb = Av + nk, *sums = Fb + nk, *part = sums + GRAD_NS_MAX;
+    double *mvpart = part + ntiles * ns, *vpart = mvpart + (size_t)nchunk * n, *lik2 = vpart + 2 * (size_t)nslice, *hpart = lik2 + 2;
+    double *Fall = c->scratch;
+    const bool head = lh.family != GPMI_LIK_NONE;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
+    // factorisation with the k augmented rows, all panel factors kept
+    launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, jitter, 1, c->W, ld);
+    for (int q = 0; q < k; ++q) launch_set_row(s, c->W, ld, n + q, dF + (size_t)q * ldf, n, n);
+    if ((rc = launch_potrf_partial(c, c->W, ld, n + k, n, n, c->d_info, Fall))) return rc;
+    hipLaunchKernelGGL(k_cen_value_part, dim3(nslice), 256, 0, s, c->W, ld, n, k, Zv, vpart);
+    // U = L^-T, A = U Z = Sigma^-1 F
+    hipLaunchKernelGGL(k_set_identity, dim3((n + 63) / 64, (n + 15) / 16), 256, 0, s, U, ldu, n);
+    if ((rc = launch_trsm_right(c, c->W, ld, n, U, ldu, n, Fall, 1))) return rc;
+    for (int q = 0; q < k; ++q) {
+        hipLaunchKernelGGL(k_upper_mv_part, dim3((n + UMV_ROWS - 1) / UMV_ROWS, nchunk), UMV_ROWS, 0, s, U, ldu, n, Zv + (size_t)q * n,
+                           mvpart);
+        hipLaunchKernelGGL(k_upper_mv_sum, dim3((n + 255) / 256), 256, 0, s, mvpart, n, nchunk, Av + (size_t)q * n);
+    }
+    // W(lower) = -U U^T = -Sigma^-1, contracted with g_ij = 1/2 (sum_c a_ic a_jc + k W_ij)
+    HIPCHK(hipMemsetAsync(c->W, 0, ld * (size_t)n * sizeof(double), s));
+    launch_syrk_uut(c, s, U, ldu, c->W, ld, n);
+    if (p.D <= GPMI_MAXD)
+        hipLaunchKernelGGL(k_grad_partial<true>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, Av, c->W, ld, part, k, (size_t)n);
+    else
+        hipLaunchKernelGGL(k_grad_partial_big<true>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, Av, c->W, ld, part, ns, k,
+                           (size_t)n);
+    hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, sums, ns);
+    if (head) launch_latent_head(s, dF, (size_t)ldf, n, k, lh, Fb, (size_t)n, hpart, lik2, c->d_info);
+    VjpEll e;
+    for (int d = 0; d < GPMI_MAXD_BIG; ++d) e.ell[d] = d < n_ell ? ell[d] : 0.0;
+    const unsigned fblocks = (unsigned)((nk + 255) / 256 < 1024 ? (nk + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_cen_finish, dim3(fblocks), 256, 0, s, Av, head ? Fb : nullptr, n, k, dFg, (size_t)ldfg, vpart, nslice,
+                       head ? lik2 : nullptr, sums, p.D, alpha, e, n_ell, c->d_info, d_out, d_grad, d_info);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int centered_check(int n, int ldx, int D, double alpha, int k, int ldf, int family, int m, int ldy, double sigma, int ldfg)
+{
+    if (n < 1 || k < 1 || D < 1 || ldx < n || ldf < n || ldfg < n) return gpmi_fail(GPMI_EARG, "bad size or leading dimension");
+    if (!(alpha > 0.0) || !isfinite(alpha)) return gpmi_fail(GPMI_EARG, "alpha must be positive and finite");
+    if (family == GPMI_LIK_NONE) return 0;
+    if (family != GPMI_LIK_NORMAL && family != GPMI_LIK_BERNOULLI_LOGIT && family != GPMI_LIK_NORMAL_LOGSD)
+        return gpmi_fail(GPMI_EARG, "unknown likelihood family");
+    if (k != (family == GPMI_LIK_NORMAL_LOGSD ? 2 : 1)) return gpmi_fail(GPMI_EARG, "k must be 2 for NORMAL_LOGSD and 1 otherwise");
+    if (m < 1 || ldy < n) return gpmi_fail(GPMI_EARG, "bad size or leading dimension of Y");
+    if (family == GPMI_LIK_NORMAL && (!(sigma > 0.0) || !isfinite(sigma))) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
+    return 0;
+}
+
+// one workgroup (k_centered_gp_small) up to n <= tune.small_cen
+static bool small_cen(const gpmi_ctx *c, int n, int D, int k)
+{
+    return c->tune.small_cen > 0 && n <= c->tune.small_cen && n <= 256 && D <= GPMI_MAXD && k <= GPMI_CEN_KMAX;
+}
+
+extern "C" int gpmi_centered_gp_lp_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
+                                            int n_ell, double jitter, const double *dF, int k, int ldf, int family, const double *dY, int m,
+                                            int ldy, double sigma, double *d_out, double *dFgrad, int ldfg, double *d_grad, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = centered_check(n, ldx, D, alpha, k, ldf, family, m, ldy, sigma, ldfg))) return rc;
+    const bool head = family != GPMI_LIK_NONE;
+    if (!dX || !dF || (head && !dY) || !d_out || !dFgrad || !d_grad || !d_info) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    const LatentHead lh{family, head ? dY : nullptr, head ? m : 0, head ? ldy : 0, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if (small_cen(c, n, D, k)) {
+        if ((rc = reserve_ws_small(c, n + k - 1, 2))) return rc;
+        launch_centered_gp_small(c->stream, dX, n, ldx, p, jitter, dF, k, ldf, lh, d_out, dFgrad, ldfg, c->W, alpha, ell, n_ell, d_grad,
+                                 d_info, c->d_info, nullptr);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    return centered_gp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dF, k, ldf, lh, d_out, dFgrad, ldfg, d_grad, d_info);
+}
+
+extern "C" int gpmi_centered_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
+                                        double jitter, const double *F, int k, int ldf, int family, const double *Y, int m, int ldy,
+                                        double sigma, double *out, double *Fgrad, int ldfg, double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = centered_check(n, ldx, D, alpha, k, ldf, family, m, ldy, sigma, ldfg))) return rc;
+    const bool head = family != GPMI_LIK_NONE;
+    if (!X || !F || (head && !Y) || !out || !Fgrad || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    if (family == GPMI_LIK_BERNOULLI_LOGIT)
+        for (int q = 0; q < m; ++q)
+            for (int i = 0; i < n; ++i) {
+                const double v = Y[(size_t)i + (size_t)q * ldy];
+                if (v != 0.0 && v != 1.0) return gpmi_fail(GPMI_EARG, "BERNOULLI_LOGIT: y must be 0 or 1");
+            }
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    hipStream_t s = c->stream;
+    if (!head) m = 0;
+    const size_t nk = (size_t)n * k, nm = (size_t)n * m;
+    if (small_cen(c, n, D, k)) {
+        // one launch of one workgroup through the pinned, device-mapped buffer:
+        // [info, .., out (4), .., flag | grad (1 + D) | Fgrad | X | F | Y]
+        const size_t o_out = 2, o_g = 8, o_fg = 24, o_x = o_fg + nk, o_f = o_x + (size_t)n * D, o_y = o_f + nk;
+        if ((rc = pin_reserve(c, (o_y + nm) * sizeof(double)))) return rc;
+        double *h = c->h_pin, *stage;
+        for (int d = 0; d < D; ++d) memcpy(h + o_x + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
+        for (int q = 0; q < k; ++q) memcpy(h + o_f + (size_t)q * n, F + (size_t)q * ldf, (size_t)n * sizeof(double));
+        for (int q = 0; q < m; ++q) memcpy(h + o_y + (size_t)q * n, Y + (size_t)q * ldy, (size_t)n * sizeof(double));
+        if ((rc = scratch_buf(c, ((size_t)n * (D + k) + nm) * sizeof(double), &stage))) return rc;
+        if ((rc = reserve_ws_small(c, n + k - 1, 2))) return rc;
+        const int seq = ++c->pin_seq;
+        __atomic_store_n((int *)(h + 7), 0, __ATOMIC_RELEASE);   // armed before the launch: a stale word never reads as done
+        double *pd = c->h_pin_dev;
+        const LatentHead lh{family, head ? pd + o_y : nullptr, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+        launch_centered_gp_small(s, pd + o_x, n, n, p, jitter, pd + o_f, k, n, lh, pd + o_out, pd + o_fg, n, c->W, alpha, ell, n_ell,
+                                 pd + o_g, (int *)pd, c->d_info, stage, (int *)(pd + 7), seq);
+        HIPCHK(hipGetLastError());
+        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
+        for (int q = 0; q < k; ++q) memcpy(Fgrad + (size_t)q * ldfg, h + o_fg + (size_t)q * n, (size_t)n * sizeof(double));
+        memcpy(out, h + o_out, 4 * sizeof(double));
+        memcpy(grad, h + o_g, (size_t)(1 + n_ell) * sizeof(double));
+        return *(const int *)h;
+    }
+    // blocked chain: [X | F | Y | Fgrad | grad (65) | out (4) | info] staged in device memory
+    double *d;
+    const size_t o_f = (size_t)n * D, o_y = o_f + nk, o_fg = o_y + nm, o_g = o_fg + nk, o_out = o_g + 1 + GPMI_MAXD_BIG, o_i = o_out + 4;
+    if ((rc = stage_buf(c, 0, (o_i + 1) * sizeof(double), &d))) return rc;
+    if ((rc = h2d_matrix(c, X, n, D, ldx, d))) return rc;
+    if ((rc = h2d_matrix(c, F, n, k, ldf, d + o_f))) return rc;
+    if (head && (rc = h2d_matrix(c, Y, n, m, ldy, d + o_y))) return rc;
+    const LatentHead lh{family, head ? d + o_y : nullptr, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if ((rc = centered_gp_core(c, d, n, n, p, alpha, ell, n_ell, jitter, d + o_f, k, n, lh, d + o_out, d + o_fg, n, d + o_g,
+                               (int *)(d + o_i))))
+        return rc;
+    int info = 0;
+    if ((rc = d2h_matrix(c, d + o_fg, (size_t)n, n, k, Fgrad, ldfg))) return rc;
+    HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, d + o_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return info;

@@ -39,6 +39,7 @@ struct gpmi_tuning {
     int small_ng1, small_ng; // value + gradient by one workgroup: one evaluation up to n <= small_ng1, several (a sampler's chains) up to small_ng (<= 256; 0: off)
     int grad_aug_n, grad_aug_ng;  // gpmi_logml_grad / _grid: K^-1 and K^-1 y from one augmented partial factorisation up to this n (0: off)
     int small_vjp;           // gpmi_exact_gp_f_vjp[_dev]: one workgroup, one launch, up to n <= small_vjp (<= 256, D <= GPMI_MAXD, k <= GPMI_VJP_KMAX; 0: off)
+    int small_cen;           // gpmi_centered_gp_lp_grad[_dev]: one workgroup, one launch, up to n <= small_cen (<= 256, D <= GPMI_MAXD, k <= GPMI_CEN_KMAX; 0: off)
     int small_gc;            // gpmi_gp_condition: one workgroup, one launch, up to n + m + 1 <= small_gc rows (0: off)
     int small_pr;            // gpmi_gp_predict[_dev]: one workgroup, one launch, up to n + m + 1 <= small_pr rows and D <= GPMI_MAXD (0: off)
     int predict_mb;          // gpmi_gp_predict / gpmi_seq_marginals: rows of Xs per chunk of the blocked chain (0: auto)
@@ -256,6 +257,14 @@ void launch_latent_gp_small(hipStream_t s, const double *X, int n, int ldx, cons
                             int ldz, const LatentHead &lh, double *out, double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb,
                             double *W, double alpha, const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work,
                             double *stage, int *done = nullptr, int seq = 0);
+// gpmi_centered_gp_lp_grad by one workgroup (n <= 256, D <= GPMI_MAXD, k <= GPMI_CEN_KMAX; workspace: 2 slices of
+// small_ws_layout(n + k - 1)): lh.family == GPMI_LIK_NONE: no head.  F, lh.Y (inputs) and out (4), Fg, grad (1 + n_ell), info_out
+// may be host-mapped (stage != null: n (D + k + m) doubles of device scratch)
+#define GPMI_CEN_KMAX 8
+void launch_centered_gp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *F, int k,
+                              int ldf, const LatentHead &lh, double *out, double *Fg, int ldfg, double *W, double alpha,
+                              const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage,
+                              int *done = nullptr, int seq = 0);
 // the chain's head (latent_kernels.hip): Fbar (n x k, ldfb) from F (n x k, ldf) and the head, one partial (lik, d lik / d sigma)
 // pair per block of 256 rows in part (2 latent_head_blocks(n) doubles), added in index order into out[0..1] (NaN when *info != 0,
 // and then Fbar is NaN too)

@@ -6,6 +6,8 @@ models/fit_hyperparameters.stan:18-32 (== stan/fit_hyperparameters.stan):
 models/exact_gp.stan:16-26:  f = cholesky_decompose(cov_exp_quad(x, 1, l) + 1e-10 I) * z
 models/westbrook_exact.stan, models/heteroscedastic.stan, models/fit_full_gp.stan: the same latent transform under a Bernoulli,
     a log-sd normal and a normal likelihood (gpmi_latent_gp_lp_grad: one factorisation per value/gradient pair)
+models/heteroscedastic_centered.stan: the CENTRED parameterisation -- mu and sigma_log are parameters themselves with the GP as
+    their prior (gpmi_centered_gp_lp_grad: one factorisation for both columns)
 """
 import math
 
@@ -176,6 +178,33 @@ def heteroscedastic_log_prob_grad(x, Y, l, sigmaf, z1, z2, ctx=None):
     grad[1] = r["grad"][0] - sigmaf + 1.0 / sigmaf
     grad[2:2 + n] = r["Zbar"][:, 0] - z1
     grad[2 + n:] = r["Zbar"][:, 1] - z2
+    return lp, grad
+
+
+def heteroscedastic_centered_log_prob_grad(x, Y, l, sigmaf, mu, sigma_log, ctx=None, jitter=1e-9):
+    """(lp__, d lp__/d(l, sigmaf, mu, sigma_log)) of models/heteroscedastic_centered.stan (Y: N x M replicates; mu and sigma_log
+    ~ multi_normal_cholesky(0, L), L = chol(K(sigmaf, l) + 1e-9 I), y[:, m] ~ normal(mu, exp(sigma_log)), :24-41):
+        lp = sum_c(-f_c' Sigma^-1 f_c / 2 - sum log L_ii) + sum_im(-s_i - (y_im - mu_i)^2 exp(-2 s_i) / 2) + 3 log l - 4 l
+             - sigmaf^2 / 2 + log l + log sigmaf + sum_i log sigma_log_i,   f = (mu, sigma_log), s = sigma_log;
+    the last term is the Jacobian of vector<lower=0>[N] sigma_log (:16), so d/dsigma_log_i gains 1 / sigma_log_i.  One call of
+    gpmi_centered_gp_lp_grad with two latent columns; conventions of exact_gp_log_prob_grad (`~` constants dropped, gradient in
+    the constrained values).  A non-positive-definite proposal returns (-inf, NaN).  jitter: the model's 1e-9 unless overridden."""
+    c = ctx or default_context()
+    mu = np.asarray(mu, float).ravel(); sigma_log = np.asarray(sigma_log, float).ravel()
+    n = mu.size
+    x = np.asarray(x, float).reshape(n, -1)
+    Y = np.asarray(Y, float).reshape(n, -1)
+    try:
+        r = c.centered_gp_lp_grad(x, sigmaf, [l], np.column_stack([mu, sigma_log]), "normal_logsd", Y, None, jitter)
+    except NotPositiveDefinite:
+        return -math.inf, np.full(2 + 2 * n, math.nan)
+    lp = (r["lp"] + 3.0 * math.log(l) - 4.0 * l - 0.5 * sigmaf * sigmaf + math.log(l) + math.log(sigmaf)
+          + float(np.sum(np.log(sigma_log))))
+    grad = np.empty(2 + 2 * n)
+    grad[0] = r["grad"][1] + 4.0 / l - 4.0
+    grad[1] = r["grad"][0] - sigmaf + 1.0 / sigmaf
+    grad[2:2 + n] = r["Fgrad"][:, 0]
+    grad[2 + n:] = r["Fgrad"][:, 1] + 1.0 / sigma_log
     return lp, grad
 
 

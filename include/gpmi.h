@@ -91,7 +91,8 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_pr" (gpmi_gp_predict[_dev] in
  * one launch up to n + m + 1 <= small_pr rows and D <= 8; 0 sends every size to the blocked chain), "predict_mb" (rows of Xs per chunk of the
  * chains of gpmi_gp_predict / gpmi_seq_marginals; 0 = auto, about n / 4), "small_vjp" (gpmi_exact_gp_f_vjp[_dev] by
- * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
+ * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_cen" (gpmi_centered_gp_lp_grad[_dev] by one
+ * workgroup up to n <= small_cen <= 256 (default 192: the measured crossover), D <= 8, k <= 8; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
  * n + m + 1 <= small_sd rows for at least small_sdb ((n + m + 1) / 400)^2 draws), "small_n2", "small_g2" (grids of at least small_g2 (n / 1024)^2 + 2 points run one workgroup per point up
  * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing"; unknown names return GPMI_EARG.  Switches of variants that
  * were measured and rejected ("lookahead", "syrk_order", "diag_waves", "gemm_variant", ...) exist in the probe
@@ -192,6 +193,32 @@ GPMI_API int gpmi_latent_gp_lp_grad_dev(gpmi_ctx *ctx, const double *dX, int n, 
                                int n_ell, double jitter, const double *dZ, int k, int ldz, int family, const double *dY, int m,
                                int ldy, double sigma, double *d_out, double *dF /* nullable */, int ldf,
                                double *dFbar /* nullable */, int ldfb, double *dZbar, int ldzb, double *d_grad, int *d_info);
+
+/* The CENTRED latent GP (models/heteroscedastic_centered.stan:24-34): the latent columns F (n x k, ldf) are parameters
+ * themselves and the GP is their prior, f_c ~ multi_normal_cholesky(0, L), Sigma = alpha^2 K0(X; ell) + jitter I = L L^T (the
+ * matrix of gpmi_exact_gp_f), with a likelihood head evaluated directly on F.  One factorisation serves all k columns.  With
+ * z_c = L^-1 f_c and a_c = Sigma^-1 f_c:
+ *   out[2] = sum_i log L_ii, out[3] = sum_c z_c' z_c, prior = -1/2 out[3] - k out[2] (the -n k / 2 log(2 pi) that `~` drops is
+ *   dropped); out[0] = prior + lik(F, Y), out[1] = d lik / d sigma, lik exactly as for gpmi_latent_gp_lp_grad (same heads, same k
+ *   per head); family GPMI_LIK_NONE: no head (lik = 0; any k >= 1; Y, m, ldy, sigma ignored) -- accepted by these two entry
+ *   points only;
+ *   Fgrad (n x k, ldfg) = d out[0] / d F = Fbar_head - [a_1 .. a_k];
+ *   grad[0] = d prior / d alpha, grad[1 .. n_ell] = d prior / d ell = 1/2 sum_ij (sum_c a_ic a_jc - k Sigma^-1_ij) dSigma_ij / dtheta
+ *   (the head does not depend on the hyper-parameters in this parameterisation).
+ * D <= 64, n_ell in {1, D}, alpha > 0, any k (n <= small_cen, default 192, at most 256, D <= 8, k <= 8: one launch of one workgroup).  Returns 0, or
+ * the order of the first non-positive leading minor (every output NaN).  All sums run in a fixed order: repeated calls give
+ * identical bits.  Priors on the hyper-parameters and Jacobians stay with the caller.  GPMI_EARG: n or k < 1; ldx, ldf, ldfg < n;
+ * k not as the head asks; ldy < n or m < 1 with a head; sigma <= 0 (NORMAL); unknown family; a NULL pointer; and on this
+ * host-buffer form y outside {0, 1} (BERNOULLI_LOGIT). */
+enum { GPMI_LIK_NONE = 3 };
+GPMI_API int gpmi_centered_gp_lp_grad(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, double alpha, const double *ell,
+                             int n_ell, double jitter, const double *F, int k, int ldf, int family, const double *Y, int m,
+                             int ldy, double sigma, double *out /* 4 */, double *Fgrad, int ldfg, double *grad /* 1 + n_ell */);
+/* the same with device-resident X, F, Y, out (4), Fgrad, grad and d_info (1 int), enqueued on the context's stream without
+ * synchronisation (ell: host) */
+GPMI_API int gpmi_centered_gp_lp_grad_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
+                                 int n_ell, double jitter, const double *dF, int k, int ldf, int family, const double *dY, int m,
+                                 int ldy, double sigma, double *d_out, double *dFgrad, int ldfg, double *d_grad, int *d_info);
 
 /* ---- marginal likelihood ---------------------------------------------- */
 

@@ -120,6 +120,15 @@ latent_gp_lp_grad <- function(X, alpha, rho, z, family, y, sigma = 1, jitter = 1
   .Call("gpmi_R_latent_gp_lp_grad", as.matrix(X), alpha, as.double(rho), jitter, z + 0.0, fam, y + 0.0, sigma)
 }
 
+# the CENTRED latent GP (models/heteroscedastic_centered.stan:24-34): the columns of f are parameters with the GP as their prior;
+# list(lp = prior + lik, dlik_dsigma, sum_log_diag, quad, fgrad = d lp / d f, grad = c(d/dalpha, d/drho...) of the prior) with
+# prior = -quad / 2 - k sum_log_diag; family as latent_gp_lp_grad, or "none" for the prior alone (any number of columns)
+centered_gp_lp_grad <- function(X, alpha, rho, f, family, y = NULL, sigma = 1, jitter = 1e-9) {
+  fam <- match(family, c("normal", "bernoulli_logit", "normal_logsd", "none")) - 1L
+  stopifnot(!is.na(fam))
+  .Call("gpmi_R_centered_gp_lp_grad", as.matrix(X), alpha, as.double(rho), jitter, f + 0.0, fam, if (is.null(y)) 0.0 else y + 0.0, sigma)
+}
+
 # models/fit_hyperparameters.stan:18-32 as plain functions
 gp_log_marginal <- function(X, y, alpha, rho, sigma, jitter = 0)
   .Call("gpmi_R_logml", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)[1]

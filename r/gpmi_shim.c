@@ -329,6 +329,38 @@ SEXP gpmi_R_latent_gp_lp_grad(SEXP X, SEXP alpha, SEXP ell, SEXP jitter, SEXP z,
     return out;
 }
 
+/* list(lp, dlik_dsigma, sum_log_diag, quad, fgrad, grad): the centred latent GP's log-density and gradient in one call with one
+ * factorisation (gpmi_centered_gp_lp_grad; models/heteroscedastic_centered.stan:24-34).  f: the latent columns (n-vector or
+ * n x k); family: 0 normal, 1 bernoulli_logit, 2 normal_logsd (f n x 2), 3 none (the prior alone: y is not read). */
+SEXP gpmi_R_centered_gp_lp_grad(SEXP X, SEXP alpha, SEXP ell, SEXP jitter, SEXP f, SEXP family, SEXP y, SEXP sigma)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), ne = Rf_length(ell), fam = Rf_asInteger(family);
+    need(is_real(X) && is_real(f) && is_real(ell), "X, f and the length-scales must be double");
+    need(n > 0 && Rf_length(f) % n == 0 && Rf_length(f) > 0, "length(f) must be a multiple of nrow(X)");
+    need(fam == GPMI_LIK_NONE || (is_real(y) && Rf_length(y) % n == 0 && Rf_length(y) > 0),
+         "y must be double and length(y) a multiple of nrow(X)");
+    need(ne == 1 || ne == D, "length-scale must have length 1 or ncol(X)");
+    int k = Rf_length(f) / n, m = fam == GPMI_LIK_NONE ? 0 : Rf_length(y) / n;
+    SEXP fg = PROTECT(Rf_duplicate(f)), g = PROTECT(Rf_allocVector(REALSXP, 1 + ne));
+    double o4[4] = {0.0, 0.0, 0.0, 0.0};
+    int rc = gpmi_centered_gp_lp_grad(ctx(), REAL(X), n, n, D, Rf_asReal(alpha), REAL(ell), ne, Rf_asReal(jitter), REAL(f), k, n, fam,
+                                      fam == GPMI_LIK_NONE ? NULL : REAL(y), m, n, Rf_asReal(sigma), o4, REAL(fg), n, REAL(g));
+    static const char *nm[6] = {"lp", "dlik_dsigma", "sum_log_diag", "quad", "fgrad", "grad"};
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 6)), names = PROTECT(Rf_allocVector(STRSXP, 6));
+    for (int i = 0; i < 4; ++i) {
+        SEXP v = PROTECT(Rf_allocVector(REALSXP, 1));
+        REAL(v)[0] = o4[i];
+        SET_VECTOR_ELT(out, i, v);
+        UNPROTECT(1);
+    }
+    SET_VECTOR_ELT(out, 4, fg); SET_VECTOR_ELT(out, 5, g);
+    for (int i = 0; i < 6; ++i) SET_STRING_ELT(names, i, Rf_mkChar(nm[i]));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
 /* list(value = c(logml, sum log L_ii, z'z), grad = c(d/dalpha, d/dell..., d/dsigma)): what Stan's
  * autodiff computes per leapfrog step for models/fit_hyperparameters.stan:18-32 */
 SEXP gpmi_R_logml_grad(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter)
