@@ -2686,9 +2686,6 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_small(const double *__restr
 //   2 Sbar = V U^T + U V^T = [V U] [U V]^T by gemm_tile<3> with K = 2n (V, U, V stored side by side, so that ONE product per
 //   tile forms it) and contracted in registers against dK/dtheta as logml_grad_small_body contracts K^-1.
 // R: 3 n columns of leading dimension ld, [V | U | V]; the gradient (1 + n_ell) is finished on the device.
-struct VjpSmallEll {
-    double ell[GPMI_MAXD];
-};
 constexpr int VJP_KMAX = GPMI_VJP_KMAX;
 // HEAD: Fbar is not an input but the adjoint of a likelihood head evaluated on F (gpmi_latent_gp_lp_grad): F is formed
 // unconditionally, thread = row evaluates latent_head_row (k <= 2), lik and d lik / d sigma are reduced in a fixed order into
@@ -2699,7 +2696,7 @@ __device__ __forceinline__ void exact_gp_vjp_small_body(const double *__restrict
                                                         std::conditional_t<HEAD, double, const double> *__restrict__ Fb, int ldfb,
                                                         double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
                                                         double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                        const VjpSmallEll &el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                        const GradEll &el, int n_ell, double *__restrict__ grad, int *info_out,
                                                         int *info_w, const ExpC &ec, double *__restrict__ stage, int *done, int seq,
                                                         const LatentHead &lh, double *__restrict__ out)
 {
@@ -2984,16 +2981,11 @@ __device__ __forceinline__ void exact_gp_vjp_small_body(const double *__restrict
     }
     __syncthreads();
     if (tid == 0) {
-        const double *hs = s_r + 4 * (1 + GPMI_MAXD);
         const double nan = __builtin_nan("");
-        grad[0] = info ? nan : 2.0 * hs[0] / alpha;
-        if (n_ell == 1) {
-            double t = 0.0;
-            for (int d = 0; d < se.D; ++d) t += hs[1 + d];
-            grad[1] = info ? nan : t / (el.ell[0] * el.ell[0] * el.ell[0]);
-        } else {
-            for (int d = 0; d < se.D; ++d) grad[1 + d] = info ? nan : hs[1 + d] / (el.ell[d] * el.ell[d] * el.ell[d]);
-        }
+        if (info)
+            for (int q = 0; q <= n_ell; ++q) grad[q] = nan;
+        else
+            gpmi_grad_from_sums(s_r + 4 * (1 + GPMI_MAXD), se.D, alpha, el.ell, n_ell, grad);
         *info_out = info;
     }
     small_signal_done(done, seq);
@@ -3003,7 +2995,7 @@ __global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__r
                                                             const double *__restrict__ Z, int k, int ldz, const double *__restrict__ Fb,
                                                             int ldfb, double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
                                                             double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                            VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                            GradEll el, int n_ell, double *__restrict__ grad, int *info_out,
                                                             int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
 {
     exact_gp_vjp_small_body<false>(X, n, ldx, p, diag_add, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, W, R, ld, alpha, el, n_ell,
@@ -3017,7 +3009,7 @@ __global__ __launch_bounds__(256, 2) void k_latent_gp_small(const double *__rest
                                                          double *__restrict__ out, double *__restrict__ Fb, int ldfb,
                                                          double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
                                                          double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                         VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out, int *info_w,
+                                                         GradEll el, int n_ell, double *__restrict__ grad, int *info_out, int *info_w,
                                                          ExpC ec, double *__restrict__ stage, int *done, int seq)
 {
     exact_gp_vjp_small_body<true>(X, n, ldx, p, diag_add, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, W, R, ld, alpha, el, n_ell, grad, info_out,
@@ -3038,7 +3030,7 @@ __global__ __launch_bounds__(256, 2) void k_centered_gp_small(const double *__re
                                                            const double *__restrict__ F, int k, int ldf, LatentHead lh,
                                                            double *__restrict__ out, double *__restrict__ Fg, int ldfg,
                                                            double *__restrict__ W, double *__restrict__ U, size_t ld, double alpha,
-                                                           VjpSmallEll el, int n_ell, double *__restrict__ grad, int *info_out,
+                                                           GradEll el, int n_ell, double *__restrict__ grad, int *info_out,
                                                            int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
 {
     GPMI_SMALL_LDS
@@ -3270,16 +3262,11 @@ __global__ __launch_bounds__(256, 2) void k_centered_gp_small(const double *__re
     }
     __syncthreads();
     if (tid == 0) {
-        const double *hs = s_r + 4 * (1 + GPMI_MAXD);
         const double nan = __builtin_nan("");
-        grad[0] = info ? nan : 2.0 * hs[0] / alpha;
-        if (n_ell == 1) {
-            double t = 0.0;
-            for (int d = 0; d < se.D; ++d) t += hs[1 + d];
-            grad[1] = info ? nan : t / (el.ell[0] * el.ell[0] * el.ell[0]);
-        } else {
-            for (int d = 0; d < se.D; ++d) grad[1 + d] = info ? nan : hs[1 + d] / (el.ell[d] * el.ell[d] * el.ell[d]);
-        }
+        if (info)
+            for (int q = 0; q <= n_ell; ++q) grad[q] = nan;
+        else
+            gpmi_grad_from_sums(s_r + 4 * (1 + GPMI_MAXD), se.D, alpha, el.ell, n_ell, grad);
         out[0] = info ? nan : (-0.5 * zz - kd * sum_log) + lik;
         out[1] = info ? nan : dsig;
         out[2] = info ? nan : sum_log;
@@ -4482,8 +4469,7 @@ void launch_exact_gp_vjp_small(hipStream_t s, const double *X, int n, int ldx, c
     size_t ld, stride;
     small_ws_layout(n, &ld, &stride);
     small_lds_attr();
-    VjpSmallEll el;
-    for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
+    const GradEll el = grad_ell(ell, n_ell);
     hipLaunchKernelGGL(k_exact_gp_vjp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, Fb,
                        ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
 }
@@ -4497,8 +4483,7 @@ void launch_latent_gp_small(hipStream_t s, const double *X, int n, int ldx, cons
     size_t ld, stride;
     small_ws_layout(n, &ld, &stride);
     small_lds_attr();
-    VjpSmallEll el;
-    for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
+    const GradEll el = grad_ell(ell, n_ell);
     hipLaunchKernelGGL(k_latent_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, lh, out,
                        Fb, ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done,
                        seq);
@@ -4513,8 +4498,7 @@ void launch_centered_gp_small(hipStream_t s, const double *X, int n, int ldx, co
     size_t ld, stride;
     small_ws_layout(n + k - 1, &ld, &stride);
     small_lds_attr();
-    VjpSmallEll el;
-    for (int d = 0; d < GPMI_MAXD; ++d) el.ell[d] = d < n_ell ? ell[d] : 0.0;
+    const GradEll el = grad_ell(ell, n_ell);
     hipLaunchKernelGGL(k_centered_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, F, k, ldf, lh,
                        out, Fg, ldfg, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
 }

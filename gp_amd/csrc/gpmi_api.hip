@@ -568,6 +568,26 @@ static int reserve_ws(gpmi_ctx *c, int rows, int cols)
     return 0;
 }
 
+// workspace for `count` slices of the small-N kernel
+static int reserve_ws_small(gpmi_ctx *c, int n, int count)
+{
+    size_t ld, stride;
+    small_ws_layout(n, &ld, &stride);
+    const size_t need = (stride * (size_t)count + 4096) * sizeof(double);
+    if (need > c->W_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->W) HIPCHK(hipFree(c->W));
+        c->W = nullptr;
+        c->W_bytes = 0;
+        if (hipMalloc((void **)&c->W, need) != hipSuccess)
+            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of workspace", need);
+        c->W_bytes = need;
+    }
+    c->ld = (int)ld;
+    c->ncols = n;
+    return 0;
+}
+
 extern "C" int gpmi_reserve(gpmi_ctx *c, int n_max)
 {
     ENTER(c);
@@ -635,17 +655,192 @@ static int fill_params(SeParams *p, int D, double alpha, const double *ell, int 
 static int h2d_matrix(gpmi_ctx *c, const double *h, int rows, int cols, int ldh, double *d)
 {
     if (rows <= 0 || cols <= 0) return 0;
-    HIPCHK(hipMemcpy2DAsync(d, (size_t)rows * sizeof(double), h, (size_t)ldh * sizeof(double),
-                            (size_t)rows * sizeof(double), cols, hipMemcpyHostToDevice, c->stream));
+    if (cols == 1)
+        HIPCHK(hipMemcpyAsync(d, h, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    else
+        HIPCHK(hipMemcpy2DAsync(d, (size_t)rows * sizeof(double), h, (size_t)ldh * sizeof(double),
+                                (size_t)rows * sizeof(double), cols, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 static int d2h_matrix(gpmi_ctx *c, const double *d, size_t ldd, int rows, int cols, double *h, int ldh)
 {
     if (rows <= 0 || cols <= 0) return 0;
-    HIPCHK(hipMemcpy2DAsync(h, (size_t)ldh * sizeof(double), d, ldd * sizeof(double),
-                            (size_t)rows * sizeof(double), cols, hipMemcpyDeviceToHost, c->stream));
+    if (cols == 1)
+        HIPCHK(hipMemcpyAsync(h, d, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    else
+        HIPCHK(hipMemcpy2DAsync(h, (size_t)ldh * sizeof(double), d, ldd * sizeof(double),
+                                (size_t)rows * sizeof(double), cols, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
+
+// X (n x D, ldx) and y into staging buffers 0 and 1
+static int upload_xy(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double **dX, double **dy)
+{
+    int rc;
+    if ((rc = stage_buf(c, 0, (size_t)n * D * sizeof(double), dX))) return rc;
+    if ((rc = stage_buf(c, 1, (size_t)n * sizeof(double), dy))) return rc;
+    if ((rc = h2d_matrix(c, X, n, D, ldx, *dX))) return rc;
+    return h2d_matrix(c, y, n, 1, n, *dy);
+}
+
+// ---- host-buffer calls ----------------------------------------------------------
+// An entry point that takes host pointers travels one of two ways, and both lay their matrices out the same way: packed
+// (leading dimension = rows) one behind the other in ONE buffer, behind a head of GPMI_HB_HEAD doubles.  The head: word 0
+// holds the info word (an int), word 7 the completion flag (an int) of a one-launch call, the rest is spare.  Kernels take
+// every address as a pointer of its own, so this layout is the host's alone.  A caller names its slots -- in(): copied in
+// from (src, rows, cols, ld) by begin(); out(): copied out to (dst, rows, cols, ld) by finish(), a null pointer keeps the slot
+// and copies nothing; mat(): a slot the caller reads itself -- and launches on dev() pointers between begin() and finish().
+#define GPMI_HB_HEAD 8
+struct HbCall {
+    struct Slot {
+        size_t off;
+        const double *src;
+        double *dst;
+        int rows, cols, ld;
+    };
+    gpmi_ctx *c;
+    size_t used = GPMI_HB_HEAD;   // doubles handed out so far
+    Slot slot[12];                // (the widest caller names 8)
+    int nslot = 0;
+    explicit HbCall(gpmi_ctx *ctx) : c(ctx) {}
+    size_t mat(size_t rows, size_t cols = 1)   // offset of a packed rows x cols slot; every slot starts a 64-byte line
+    {
+        const size_t o = used;
+        used = (used + rows * cols + 7) & ~(size_t)7;
+        return o;
+    }
+    size_t in(const double *src, int rows, int cols, int ld)
+    {
+        slot[nslot] = Slot{mat(rows, cols), src, nullptr, rows, cols, ld};
+        return slot[nslot++].off;
+    }
+    size_t out(double *dst, int rows, int cols, int ld)
+    {
+        slot[nslot] = Slot{mat(rows, cols), nullptr, dst, rows, cols, ld};
+        return slot[nslot++].off;
+    }
+};
+
+// pinned, device-mapped host buffer of the one-launch host-buffer calls (inputs in, results out, no copy call)
+static int pin_reserve(gpmi_ctx *c, size_t need)
+{
+    if (need <= c->h_pin_bytes) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->h_pin) HIPCHK(hipHostFree(c->h_pin));
+    c->h_pin = c->h_pin_dev = nullptr;
+    c->h_pin_bytes = 0;
+    const size_t want = need > 65536 ? need : 65536;
+    if (hipHostMalloc((void **)&c->h_pin, want, hipHostMallocMapped) != hipSuccess)
+        return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of pinned host memory", want);
+    HIPCHK(hipHostGetDevicePointer((void **)&c->h_pin_dev, c->h_pin, 0));
+    c->h_pin_bytes = want;
+    return 0;
+}
+
+// wait for the completion flag a one-launch kernel publishes in the pinned buffer (small_signal_done): polling the mapped
+// word costs ~1-2 us after the kernel's last store, a stream synchronisation ~10; the stream is the fallback
+static int pin_wait(gpmi_ctx *c, const int *flag, int seq)
+{
+    for (long it = 0; it < 20000000L; ++it) {
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return 0;
+        __builtin_ia32_pause();
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return 0;
+    return gpmi_fail(GPMI_EHIP, "the kernel of a one-launch call did not publish its completion flag");
+}
+
+// The one-launch call: begin() packs the inputs (by the CPU) into the pinned, device-mapped buffer that the kernel reads
+// directly, reserves the caller's device scratch (stage) and `ws_count` one-workgroup workspace slices of order ws_n, and arms
+// the completion flag; the kernel writes its results and info() straight into the buffer and publishes (flag(), seq) last;
+// finish() waits for it, unpacks the outputs and returns the info word: no copy call in either direction.  Callers whose
+// kernels publish no flag (several launches) pack(), wait on the stream and unpack().
+struct PinCall : HbCall {
+    using HbCall::HbCall;
+    int seq = 0;
+    double *stage = nullptr;
+    double *host(size_t o) const { return c->h_pin + o; }
+    double *dev(size_t o) const { return c->h_pin_dev + o; }
+    int *info() const { return (int *)c->h_pin_dev; }
+    int *flag() const { return (int *)(c->h_pin_dev + 7); }
+    int host_info() const { return *(const int *)c->h_pin; }
+    int pack()
+    {
+        int rc = pin_reserve(c, used * sizeof(double));
+        if (rc) return rc;
+        for (int q = 0; q < nslot; ++q) {
+            const Slot &t = slot[q];
+            if (!t.src) continue;
+            for (int j = 0; j < t.cols; ++j) memcpy(host(t.off) + (size_t)j * t.rows, t.src + (size_t)j * t.ld, (size_t)t.rows * sizeof(double));
+        }
+        return 0;
+    }
+    void unpack() const
+    {
+        for (int q = 0; q < nslot; ++q) {
+            const Slot &t = slot[q];
+            if (!t.dst) continue;
+            for (int j = 0; j < t.cols; ++j) memcpy(t.dst + (size_t)j * t.ld, host(t.off) + (size_t)j * t.rows, (size_t)t.rows * sizeof(double));
+        }
+    }
+    int begin(size_t stage_doubles, int ws_n, int ws_count)
+    {
+        int rc;
+        if ((rc = pack())) return rc;
+        if ((rc = scratch_buf(c, stage_doubles * sizeof(double), &stage))) return rc;
+        if ((rc = reserve_ws_small(c, ws_n, ws_count))) return rc;
+        // the flag is cleared first: pin_reserve hands out fresh memory when the buffer grows, and a stale word must never
+        // read as done
+        __atomic_store_n((int *)(c->h_pin + 7), 0, __ATOMIC_RELEASE);
+        seq = ++c->pin_seq;
+        return 0;
+    }
+    int wait() const
+    {
+        HIPCHK(hipGetLastError());
+        return pin_wait(c, (const int *)(c->h_pin + 7), seq);
+    }
+    int finish() const
+    {
+        int rc = wait();
+        if (rc) return rc;
+        unpack();
+        return host_info();
+    }
+};
+
+// The staged call: the same layout in a staging buffer of the device (slot 0 unless the core it runs needs that one): begin()
+// copies the inputs up, finish() the outputs and the info word at d_info (nullable: none) down, with one synchronisation at
+// the end.
+static int staged_finish(gpmi_ctx *c, const int *d_info)
+{
+    int info = 0;
+    if (d_info) HIPCHK(hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return info;
+}
+struct StageCall : HbCall {
+    using HbCall::HbCall;
+    double *d = nullptr;
+    double *dev(size_t o) const { return d + o; }
+    int *info() const { return (int *)d; }
+    int begin(int stage_slot = 0)
+    {
+        int rc;
+        if ((rc = stage_buf(c, stage_slot, used * sizeof(double), &d))) return rc;
+        for (int q = 0; q < nslot; ++q)
+            if (slot[q].src && (rc = h2d_matrix(c, slot[q].src, slot[q].rows, slot[q].cols, slot[q].ld, d + slot[q].off))) return rc;
+        return 0;
+    }
+    int finish(const int *d_info) const
+    {
+        int rc;
+        for (int q = 0; q < nslot; ++q)
+            if (slot[q].dst && (rc = d2h_matrix(c, d + slot[q].off, (size_t)slot[q].rows, slot[q].rows, slot[q].cols, slot[q].dst, slot[q].ld)))
+                return rc;
+        return staged_finish(c, d_info);
+    }
+};
 
 // ---- covariance builders ------------------------------------------------------
 extern "C" int gpmi_se_cov_dev(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dY, int m,
@@ -937,10 +1132,6 @@ static void lanes_join(gpmi_ctx *c, int lanes, hipStream_t caller, int la_saved)
 }
 
 // ---- latent exact GP: f = chol(K) z --------------------------------------------------------
-static int pin_reserve(gpmi_ctx *c, size_t need);
-static int pin_wait(gpmi_ctx *c, const int *flag, int seq);
-static int reserve_ws_small(gpmi_ctx *c, int n, int count);
-static int upload_xy(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double **dX, double **dy);
 extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
                                double jitter, const double *z, double *f)
 {
@@ -951,21 +1142,13 @@ extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
     hipStream_t s = c->stream;
     if (n <= 256 && D <= GPMI_MAXD) {
-        // one launch of one workgroup; X, z in and f, info out through the pinned, device-mapped buffer: [info | f | X | z]
-        const size_t need = (8 + (size_t)n * (D + 2)) * sizeof(double);
-        if ((rc = pin_reserve(c, need))) return rc;
-        double *hf = c->h_pin + 8, *hX = hf + n, *hz = hX + (size_t)n * D, *stage;
-        for (int d = 0; d < D; ++d) memcpy(hX + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        memcpy(hz, z, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, (size_t)n * (D + 1) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 1))) return rc;
-        double *pd = c->h_pin_dev;
-        launch_exact_gp_small(s, pd + 8 + n, n, n, pd + 8 + n + (size_t)n * D, p, jitter, c->W, pd + 8, (int *)pd, c->d_info, stage,
-                              (int *)(pd + 7), ++c->pin_seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(c->h_pin + 7), c->pin_seq))) return rc;
-        memcpy(f, hf, (size_t)n * sizeof(double));
-        return *(const int *)c->h_pin;
+        // one launch of one workgroup; X, z in and f, info out through the pinned, device-mapped buffer
+        PinCall pc(c);
+        const size_t f_ = pc.out(f, n, 1, n), X_ = pc.in(X, n, D, ldx), z_ = pc.in(z, n, 1, n);
+        if ((rc = pc.begin((size_t)n * (D + 1), n, 1))) return rc;
+        launch_exact_gp_small(s, pc.dev(X_), n, n, pc.dev(z_), p, jitter, c->W, pc.dev(f_), pc.info(), c->d_info, pc.stage, pc.flag(),
+                              pc.seq);
+        return pc.finish();
     }
     double *dX, *dz;
     if ((rc = upload_xy(c, X, n, ldx, D, z, &dX, &dz))) return rc;
@@ -978,10 +1161,8 @@ extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int
     launch_se_cov(c, s, dX, n, n, nullptr, n, n, p, jitter, 1, c->W, ld);
     if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, c->d_info, nullptr))) return rc;
     launch_trmv_lower(s, c->W, ld, n, dz, df, part);
-    int info = 0;
-    HIPCHK(hipMemcpyAsync(f, df, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&info, c->d_info, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = d2h_matrix(c, df, (size_t)n, n, 1, f, n))) return rc;
+    const int info = staged_finish(c, c->d_info);
     if (info)
         for (int i = 0; i < n; ++i) f[i] = NAN;
     return info;
@@ -990,35 +1171,6 @@ extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int
 // ---- marginal likelihood -----------------------------------------------------
 // n small enough for the one-workgroup evaluation (k_logml_small): the sizes the reference's own drivers run
 // at (R/tests.R:5 N = 21, pendulum_fit*.R 79 .. 199, BASELINE c1 N = 256)
-// pinned, device-mapped host buffer of the one-launch host-buffer calls (inputs in, results out, no copy call)
-static int pin_reserve(gpmi_ctx *c, size_t need)
-{
-    if (need <= c->h_pin_bytes) return 0;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->h_pin) HIPCHK(hipHostFree(c->h_pin));
-    c->h_pin = c->h_pin_dev = nullptr;
-    c->h_pin_bytes = 0;
-    const size_t want = need > 65536 ? need : 65536;
-    if (hipHostMalloc((void **)&c->h_pin, want, hipHostMallocMapped) != hipSuccess)
-        return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of pinned host memory", want);
-    HIPCHK(hipHostGetDevicePointer((void **)&c->h_pin_dev, c->h_pin, 0));
-    c->h_pin_bytes = want;
-    return 0;
-}
-
-// wait for the completion flag a one-launch kernel publishes in the pinned buffer (small_signal_done): polling the mapped
-// word costs ~1-2 us after the kernel's last store, a stream synchronisation ~10; the stream is the fallback
-static int pin_wait(gpmi_ctx *c, const int *flag, int seq)
-{
-    for (long it = 0; it < 20000000L; ++it) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return 0;
-        __builtin_ia32_pause();
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return 0;
-    return gpmi_fail(GPMI_EHIP, "the kernel of a one-launch call did not publish its completion flag");
-}
-
 static bool small_logml(const gpmi_ctx *c, int n, int D, int G = 1)
 {
     // one workgroup against the multi-CU launch chain (tools/small_n_bench.py, one evaluation / 64 points, us per
@@ -1078,26 +1230,6 @@ static int small_grid(gpmi_ctx *c, const double *dX, int n, int ldx, int D, cons
                                      sigma + g0, gc, jitter, c->d_spar, c->W, d_out3 + 3 * (size_t)g0, d_info + g0, c->d_sinfo);
     }
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// workspace for `count` slices of the small-N kernel
-static int reserve_ws_small(gpmi_ctx *c, int n, int count)
-{
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    const size_t need = (stride * (size_t)count + 4096) * sizeof(double);
-    if (need > c->W_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->W) HIPCHK(hipFree(c->W));
-        c->W = nullptr;
-        c->W_bytes = 0;
-        if (hipMalloc((void **)&c->W, need) != hipSuccess)
-            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of workspace", need);
-        c->W_bytes = need;
-    }
-    c->ld = (int)ld;
-    c->ncols = n;
     return 0;
 }
 
@@ -1221,16 +1353,6 @@ extern "C" int gpmi_logml_grid_ard_dev(gpmi_ctx *c, const double *dX, int n, int
     return 0;
 }
 
-static int upload_xy(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double **dX, double **dy)
-{
-    int rc;
-    if ((rc = stage_buf(c, 0, (size_t)n * D * sizeof(double), dX))) return rc;
-    if ((rc = stage_buf(c, 1, (size_t)n * sizeof(double), dy))) return rc;
-    if ((rc = h2d_matrix(c, X, n, D, ldx, *dX))) return rc;
-    HIPCHK(hipMemcpyAsync(*dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
-
 extern "C" int gpmi_logml(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y,
                           double alpha, const double *ell, int n_ell, double sigma, double jitter, double *out3)
 {
@@ -1245,28 +1367,17 @@ extern "C" int gpmi_logml(gpmi_ctx *c, const double *X, int n, int ldx, int D, c
         // more than the kernel itself)
         SeParams p;
         if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-        const size_t need = (8 + (size_t)n * (D + 1)) * sizeof(double);
-        if ((rc = pin_reserve(c, need))) return rc;
-        double *hX = c->h_pin + 8, *hy = hX + (size_t)n * D, *stage;
-        for (int d = 0; d < D; ++d) memcpy(hX + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        memcpy(hy, y, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, (size_t)n * (D + 1) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 1))) return rc;
-        double *pd = c->h_pin_dev;
-        const int seq = ++c->pin_seq;
-        launch_logml_small(c->stream, pd + 8, n, n, pd + 8 + (size_t)n * D, p, sigma * sigma + jitter, c->W, (size_t)c->ld, pd,
-                           (int *)(pd + 3), c->d_info, stage, (int *)(pd + 7), seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(c->h_pin + 7), seq))) return rc;
-        memcpy(out3, c->h_pin, 3 * sizeof(double));
-        return *(const int *)(c->h_pin + 3);
+        PinCall pc(c);
+        const size_t out_ = pc.out(out3, 3, 1, 3), X_ = pc.in(X, n, D, ldx), y_ = pc.in(y, n, 1, n);
+        if ((rc = pc.begin((size_t)n * (D + 1), n, 1))) return rc;
+        launch_logml_small(c->stream, pc.dev(X_), n, n, pc.dev(y_), p, sigma * sigma + jitter, c->W, (size_t)c->ld, pc.dev(out_),
+                           pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
+        return pc.finish();
     }
     if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
     if ((rc = gpmi_logml_dev(c, dX, n, n, D, dy, alpha, ell, n_ell, sigma, jitter, c->d_out, c->d_info + 1))) return rc;
-    int info = 0;
-    HIPCHK(hipMemcpyAsync(out3, c->d_out, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&info, c->d_info + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = d2h_matrix(c, c->d_out, 3, 3, 1, out3, 3))) return rc;
+    const int info = staged_finish(c, c->d_info + 1);
     if (c->timing) {
         float ms;
         for (int i = 0; i < 3; ++i) {
@@ -1276,9 +1387,11 @@ extern "C" int gpmi_logml(gpmi_ctx *c, const double *X, int n, int ldx, int D, c
     return info;
 }
 
-extern "C" int gpmi_logml_grid(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y,
-                               const double *alpha, const double *rho, const double *sigma, int G,
-                               double jitter, double *out3, int *info)
+// the host-buffer grids: X, y up, G result records and info words down; dev_grid is gpmi_logml_grid_dev or its ARD twin
+typedef int (*logml_grid_dev_fn)(gpmi_ctx *, const double *, int, int, int, const double *, const double *, const double *,
+                                 const double *, int, double, double *, int *);
+static int logml_grid_host(gpmi_ctx *c, logml_grid_dev_fn dev_grid, const double *X, int n, int ldx, int D, const double *y,
+                           const double *alpha, const double *ell, const double *sigma, int G, double jitter, double *out3, int *info)
 {
     ENTER(c);
     if (G < 0) return gpmi_fail(GPMI_EARG, "negative grid size");
@@ -1289,30 +1402,24 @@ extern "C" int gpmi_logml_grid(gpmi_ctx *c, const double *X, int n, int ldx, int
     if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
     if ((rc = scratch_buf(c, (size_t)G * (3 * sizeof(double) + sizeof(int)) + 64, &dres))) return rc;
     int *dinfo = (int *)(dres + 3 * (size_t)G);
-    if ((rc = gpmi_logml_grid_dev(c, dX, n, n, D, dy, alpha, rho, sigma, G, jitter, dres, dinfo))) return rc;
-    HIPCHK(hipMemcpyAsync(out3, dres, (size_t)G * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = dev_grid(c, dX, n, n, D, dy, alpha, ell, sigma, G, jitter, dres, dinfo))) return rc;
+    if ((rc = d2h_matrix(c, dres, 3, 3 * G, 1, out3, 3))) return rc;
     HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
+extern "C" int gpmi_logml_grid(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y,
+                               const double *alpha, const double *rho, const double *sigma, int G,
+                               double jitter, double *out3, int *info)
+{
+    return logml_grid_host(c, gpmi_logml_grid_dev, X, n, ldx, D, y, alpha, rho, sigma, G, jitter, out3, info);
+}
+
 extern "C" int gpmi_logml_grid_ard(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, const double *alpha,
                                    const double *ell, const double *sigma, int G, double jitter, double *out3, int *info)
 {
-    ENTER(c);
-    if (G < 0) return gpmi_fail(GPMI_EARG, "negative grid size");
-    if (G == 0) return 0;
-    if (n <= 0 || !X || !y || !out3 || !info || ldx < n || D < 1) return gpmi_fail(GPMI_EARG, "bad argument");
-    double *dX, *dy, *dres;
-    int rc;
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = scratch_buf(c, (size_t)G * (3 * sizeof(double) + sizeof(int)) + 64, &dres))) return rc;
-    int *dinfo = (int *)(dres + 3 * (size_t)G);
-    if ((rc = gpmi_logml_grid_ard_dev(c, dX, n, n, D, dy, alpha, ell, sigma, G, jitter, dres, dinfo))) return rc;
-    HIPCHK(hipMemcpyAsync(out3, dres, (size_t)G * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return logml_grid_host(c, gpmi_logml_grid_ard_dev, X, n, ldx, D, y, alpha, ell, sigma, G, jitter, out3, info);
 }
 
 static int joint_logml_core(gpmi_ctx *c, const double *dt, int n, const double *dyy, double alpha, double l, double sigma,
@@ -1387,11 +1494,8 @@ extern "C" int gpmi_joint_logml(gpmi_ctx *c, const double *t, int n, const doubl
     HIPCHK(hipMemcpyAsync(dt, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dyy, yy, (size_t)2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if ((rc = gpmi_joint_logml_dev(c, dt, n, dyy, alpha, l, sigma, jitter, c->d_out, c->d_info + 1))) return rc;
-    int info = 0;
-    HIPCHK(hipMemcpyAsync(out3, c->d_out, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&info, c->d_info + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return info;
+    if ((rc = d2h_matrix(c, c->d_out, 3, 3, 1, out3, 3))) return rc;
+    return staged_finish(c, c->d_info + 1);
 }
 
 // ---- rbf_cov_chol (covariance.cpp:9-47) ---------------------------------------
@@ -1478,34 +1582,27 @@ extern "C" int gpmi_rbf_cov_chol(gpmi_ctx *c, const double *x, int n, double l, 
     double *dx, *Lc, *S;
     hipStream_t s = c->stream;
     if (n <= 64) {
-        // small n: ONE launch of one workgroup; x in, L / dL/dl / info out through the pinned, device-mapped buffer:
-        // [info | x | L (n x n) | dLdl (n x n)]  (tools/interp_small_bench.py: n = 50 144 -> 84 us; at n = 100 one workgroup
-        // takes 170 us against the chain's 157 -- ONE call stays on the chain there, the table build below does not)
-        const size_t o_x = 8, o_L = o_x + n, o_dL = o_L + (size_t)n * n;
-        if ((rc = pin_reserve(c, (o_dL + (size_t)n * n) * sizeof(double)))) return rc;
-        memcpy(c->h_pin + o_x, x, (size_t)n * sizeof(double));
+        // small n: ONE launch of one workgroup; x in, L / dL/dl / info out through the pinned, device-mapped buffer
+        // (tools/interp_small_bench.py: n = 50 144 -> 84 us; at n = 100 one workgroup takes 170 us against the chain's
+        // 157 -- ONE call stays on the chain there, the table build below does not); the kernel publishes no flag
+        PinCall pc(c);
+        const size_t x_ = pc.in(x, n, 1, n), L_ = pc.out(L, n, n, ldl), dL_ = pc.out(dLdl, n, n, lddl);
+        if ((rc = pc.pack())) return rc;
         double *stage;
         if ((rc = scratch_buf(c, (size_t)n * sizeof(double), &stage))) return rc;
         if ((rc = reserve_ws_small(c, n, 3))) return rc;
-        double *pd = c->h_pin_dev;
-        launch_rbf_cov_chol_small(s, pd + o_x, n, &l, 1, c->W, pd + o_L, pd + o_dL, 0, (size_t)n, (int *)pd, c->d_info, stage);
+        launch_rbf_cov_chol_small(s, pc.dev(x_), n, &l, 1, c->W, pc.dev(L_), pc.dev(dL_), 0, (size_t)n, pc.info(), c->d_info, stage);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
-        for (int j = 0; j < n; ++j) {
-            memcpy(L + (size_t)j * ldl, c->h_pin + o_L + (size_t)j * n, (size_t)n * sizeof(double));
-            memcpy(dLdl + (size_t)j * lddl, c->h_pin + o_dL + (size_t)j * n, (size_t)n * sizeof(double));
-        }
-        return *(const int *)c->h_pin;
+        pc.unpack();
+        return pc.host_info();
     }
     if ((rc = stage_buf(c, 0, (size_t)n * sizeof(double), &dx))) return rc;
-    HIPCHK(hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = h2d_matrix(c, x, n, 1, n, dx))) return rc;
     if ((rc = rbf_cov_chol_core(c, dx, n, l, &Lc, &S, &ldd))) return rc;
-    int info = 0;
-    HIPCHK(hipMemcpyAsync(&info, c->d_info, sizeof(int), hipMemcpyDeviceToHost, s));
     if ((rc = d2h_matrix(c, Lc, (size_t)ldd, n, n, L, ldl))) return rc;
     if ((rc = d2h_matrix(c, S, (size_t)ldd, n, n, dLdl, lddl))) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    return info;
+    return staged_finish(c, c->d_info);
 }
 
 // ---- Cholesky-factor interpolation over the length-scale ---------------------------
@@ -1714,25 +1811,23 @@ static int approx_Lz_host(gpmi_ctx *c, double l, const double *z, double *f, dou
     if (n <= 4096) {
         // the per-iteration call of the interpolated model at the reference's size (N = 100, test_interpolate.R:5): z goes in
         // and f (dfdl) come back through the pinned, device-mapped buffer -- three small launches, no copy call
-        const size_t need = (3 * (size_t)n + 8) * sizeof(double);
-        if ((rc = pin_reserve(c, need))) return rc;
-        memcpy(c->h_pin, z, (size_t)n * sizeof(double));
-        double *pd = c->h_pin_dev;
-        const double *zsrc = pd;
+        PinCall pc(c);
+        const size_t z_ = pc.in(z, n, 1, n), f_ = pc.out(f, n, 1, n), g_ = pc.out(dfdl, n, 1, n);
+        if ((rc = pc.pack())) return rc;
+        const double *zsrc = pc.dev(z_);
         if (n > GPMI_HMV_SMALL_N) {   // the chunked kernels read z once per row block: staged in device memory first
-            launch_copy_matrix(c->stream, pd, (size_t)n, dz, (size_t)n, n, 1, 0);
+            launch_copy_matrix(c->stream, zsrc, (size_t)n, dz, (size_t)n, n, 1, 0);
             zsrc = dz;
         }
-        if ((rc = approx_Lz_core(c, l, zsrc, pd + n, dfdl ? pd + 2 * (size_t)n : nullptr))) return rc;
+        if ((rc = approx_Lz_core(c, l, zsrc, pc.dev(f_), dfdl ? pc.dev(g_) : nullptr))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
-        memcpy(f, c->h_pin + n, (size_t)n * sizeof(double));
-        if (dfdl) memcpy(dfdl, c->h_pin + 2 * (size_t)n, (size_t)n * sizeof(double));
+        pc.unpack();
         return 0;
     }
-    HIPCHK(hipMemcpyAsync(dz, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = h2d_matrix(c, z, n, 1, n, dz))) return rc;
     if ((rc = approx_Lz_core(c, l, dz, dz + n, dfdl ? dz + 2 * (size_t)n : nullptr))) return rc;
-    HIPCHK(hipMemcpyAsync(f, dz + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (dfdl) HIPCHK(hipMemcpyAsync(dfdl, dz + 2 * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = d2h_matrix(c, dz + n, (size_t)n, n, 1, f, n))) return rc;
+    if (dfdl && (rc = d2h_matrix(c, dz + 2 * (size_t)n, (size_t)n, n, 1, dfdl, n))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1802,45 +1897,25 @@ static int tri_host(gpmi_ctx *c, int model, double l, const double *Z, int k, in
     int rc;
     if ((rc = tri_check(c, model, l, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, lbar, vjp))) return rc;
     const int n = model == TRI_GP ? c->igp_n : c->itp_n;
-    const size_t nk = (size_t)n * k;
-    // [Z | Fbar | F | Zbar | lbar], n x k each, leading dimension n
-    const size_t oZ = 0, oFb = nk, oF = 2 * nk, oZb = 3 * nk, oL = 4 * nk, need = (4 * nk + 8) * sizeof(double);
-    double *base;
-    bool pinned = tri_vjp_one_launch(n, k);
-    if (pinned) {
-        if ((rc = pin_reserve(c, need))) return rc;
-        base = c->h_pin;
-        for (int j = 0; j < k; ++j) {
-            memcpy(base + oZ + (size_t)j * n, Z + (size_t)j * ldz, (size_t)n * sizeof(double));
-            if (vjp) memcpy(base + oFb + (size_t)j * n, Fb + (size_t)j * ldfb, (size_t)n * sizeof(double));
-        }
-    } else {
-        if ((rc = stage_buf(c, 0, need, &base))) return rc;
-        HIPCHK(hipMemcpy2DAsync(base + oZ, (size_t)n * sizeof(double), Z, (size_t)ldz * sizeof(double), (size_t)n * sizeof(double),
-                                k, hipMemcpyHostToDevice, c->stream));
-        if (vjp)
-            HIPCHK(hipMemcpy2DAsync(base + oFb, (size_t)n * sizeof(double), Fb, (size_t)ldfb * sizeof(double),
-                                    (size_t)n * sizeof(double), k, hipMemcpyHostToDevice, c->stream));
-    }
-    double *d = pinned ? c->h_pin_dev : base;
-    if ((rc = tri_core(c, model, l, d + oZ, k, n, vjp ? d + oFb : nullptr, n, F ? d + oF : nullptr, n, vjp ? d + oZb : nullptr, n,
-                       vjp ? d + oL : nullptr)))
+    // F, Zbar and lbar lie side by side: the staged path brings them down with ONE copy into the pinned buffer (a null
+    // Fbar, F, Zbar or lbar keeps its slot and is not copied)
+    PinCall pc(c);
+    const size_t Z_ = pc.in(Z, n, k, ldz), Fb_ = pc.in(Fb, n, k, ldfb), F_ = pc.out(F, n, k, ldf), Zb_ = pc.out(Zb, n, k, ldzb),
+                 lb_ = pc.out(lbar, 1, 1, 1);
+    StageCall sc(c);
+    static_cast<HbCall &>(sc) = pc;   // the same slots in device memory
+    const bool pinned = tri_vjp_one_launch(n, k);
+    if ((rc = pinned ? pc.pack() : sc.begin())) return rc;
+    double *d = pinned ? c->h_pin_dev : sc.d;
+    if ((rc = tri_core(c, model, l, d + Z_, k, n, vjp ? d + Fb_ : nullptr, n, F ? d + F_ : nullptr, n, vjp ? d + Zb_ : nullptr, n,
+                       vjp ? d + lb_ : nullptr)))
         return rc;
-    if (pinned) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-    } else {
-        double *h = nullptr;
-        if ((rc = pin_reserve(c, need))) return rc;
-        h = c->h_pin;
-        HIPCHK(hipMemcpyAsync(h + oF, base + oF, (2 * nk + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+    if (!pinned) {
+        if ((rc = pin_reserve(c, pc.used * sizeof(double)))) return rc;
+        HIPCHK(hipMemcpyAsync(pc.host(F_), sc.dev(F_), (lb_ + 1 - F_) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
-    const double *h = c->h_pin;
-    for (int j = 0; j < k; ++j) {
-        if (F) memcpy(F + (size_t)j * ldf, h + oF + (size_t)j * n, (size_t)n * sizeof(double));
-        if (vjp) memcpy(Zb + (size_t)j * ldzb, h + oZb + (size_t)j * n, (size_t)n * sizeof(double));
-    }
-    if (vjp) *lbar = h[oL];
+    HIPCHK(hipStreamSynchronize(c->stream));
+    pc.unpack();
     return 0;
 }
 
@@ -2372,15 +2447,20 @@ static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const 
 // host part: (d/dalpha, d/dell..., d/dsigma) from the contraction sums
 static void logml_grad_finish(const double *hs, int D, double alpha, const double *ell, int n_ell, double sigma, double *grad)
 {
-    grad[0] = 2.0 * hs[0] / alpha;
-    if (n_ell == 1) {
-        double t = 0.0;
-        for (int d = 0; d < D; ++d) t += hs[1 + d];
-        grad[1] = t / (ell[0] * ell[0] * ell[0]);
-    } else {
-        for (int d = 0; d < D; ++d) grad[1 + d] = hs[1 + d] / (ell[d] * ell[d] * ell[d]);
-    }
+    gpmi_grad_from_sums(hs, D, alpha, ell, n_ell, grad);
     grad[1 + n_ell] = 2.0 * sigma * hs[grad_ns(D) - 1];
+}
+
+// out3 and grad (2 + n_ell) of one evaluation from its result record (value triple, then the contraction sums) and its info:
+// not positive definite -> NaN gradient
+static void logml_grad_unpack(const double *res, int info, int D, double alpha, const double *ell, int n_ell, double sigma,
+                              double *out3, double *grad)
+{
+    for (int k = 0; k < 3; ++k) out3[k] = res[k];
+    if (info)
+        for (int k = 0; k < 2 + n_ell; ++k) grad[k] = NAN;
+    else
+        logml_grad_finish(res + 3, D, alpha, ell, n_ell, sigma, grad);
 }
 
 extern "C" int gpmi_logml_grad(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y,
@@ -2395,27 +2475,14 @@ extern "C" int gpmi_logml_grad(gpmi_ctx *c, const double *X, int n, int ldx, int
     if (c->tune.small_ng1 > 0 && n <= c->tune.small_ng1 && D <= GPMI_MAXD) {
         // the sizes the reference's fits run at: ONE launch of one workgroup; X, y go in and the 13 results come back
         // through a pinned, device-mapped buffer (no copy call), as in gpmi_logml
-        const size_t need = (16 + (size_t)n * (D + 1)) * sizeof(double);
-        if ((rc = pin_reserve(c, need))) return rc;
-        double *hX = c->h_pin + 16, *hy = hX + (size_t)n * D, *stage;
-        for (int d = 0; d < D; ++d) memcpy(hX + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        memcpy(hy, y, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, (size_t)n * (D + 1) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 2))) return rc;
-        double *pd = c->h_pin_dev;
-        const int seq = ++c->pin_seq;
-        launch_logml_grad_small(c->stream, pd + 16, n, n, pd + 16 + (size_t)n * D, p, sigma * sigma + jitter, c->W, pd,
-                                (int *)(pd + GPMI_SMALL_GRAD_RES), c->d_info, stage, (int *)(pd + 15), seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(c->h_pin + 15), seq))) return rc;
-        const int info = *(const int *)(c->h_pin + GPMI_SMALL_GRAD_RES);
-        for (int k = 0; k < 3; ++k) out3[k] = c->h_pin[k];
-        if (info) {
-            for (int k = 0; k < 2 + n_ell; ++k) grad[k] = NAN;
-            return info;
-        }
-        logml_grad_finish(c->h_pin + 3, D, alpha, ell, n_ell, sigma, grad);
-        return 0;
+        PinCall pc(c);
+        const size_t res_ = pc.mat(GPMI_SMALL_GRAD_RES), X_ = pc.in(X, n, D, ldx), y_ = pc.in(y, n, 1, n);
+        if ((rc = pc.begin((size_t)n * (D + 1), n, 2))) return rc;
+        launch_logml_grad_small(c->stream, pc.dev(X_), n, n, pc.dev(y_), p, sigma * sigma + jitter, c->W, pc.dev(res_), pc.info(),
+                                c->d_info, pc.stage, pc.flag(), pc.seq);
+        const int info = pc.finish();
+        if (info >= 0) logml_grad_unpack(pc.host(res_), info, D, alpha, ell, n_ell, sigma, out3, grad);
+        return info;
     }
     double *dX, *dy, *dres;
     if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
@@ -2423,18 +2490,10 @@ extern "C" int gpmi_logml_grad(gpmi_ctx *c, const double *X, int n, int ldx, int
     dres = c->d_fin + 4096;  // second half of the finalize scratch (64 KiB): GRAD_RES doubles
     if ((rc = logml_grad_core(c, dX, n, n, dy, p, sigma * sigma + jitter, dres, c->d_info + 1))) return rc;
     double hr[GRAD_RES];
-    int info = 0;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(hr, dres, sizeof(hr), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&info, c->d_info + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int k = 0; k < 3; ++k) out3[k] = hr[k];
-    if (info) {
-        for (int k = 0; k < 2 + n_ell; ++k) grad[k] = NAN;
-        return info;
-    }
-    logml_grad_finish(hr + 3, D, alpha, ell, n_ell, sigma, grad);
-    return 0;
+    if ((rc = d2h_matrix(c, dres, GRAD_RES, GRAD_RES, 1, hr, GRAD_RES))) return rc;
+    const int info = staged_finish(c, c->d_info + 1);
+    if (info >= 0) logml_grad_unpack(hr, info, D, alpha, ell, n_ell, sigma, out3, grad);
+    return info;
 }
 
 // ---- vector-Jacobian product of the latent exact GP's transform ---------------------------------------------------
@@ -2486,23 +2545,15 @@ __global__ __launch_bounds__(256) void k_vjp_suffix(const double *__restrict__ U
     }
 }
 
-struct VjpEll {
-    double ell[GPMI_MAXD_BIG];
-};
 // (d/dalpha, d/dell...) from the contraction sums (logml_grad_finish without the noise term); NaN when not PD
-__global__ void k_vjp_finish(const double *__restrict__ hs, int D, double alpha, VjpEll e, int n_ell, const int *__restrict__ info,
+__global__ void k_vjp_finish(const double *__restrict__ hs, int D, double alpha, GradEll e, int n_ell, const int *__restrict__ info,
                              double *__restrict__ grad)
 {
     if (threadIdx.x != 0) return;
-    const bool bad = *info != 0;
-    grad[0] = bad ? __builtin_nan("") : 2.0 * hs[0] / alpha;
-    if (n_ell == 1) {
-        double t = 0.0;
-        for (int d = 0; d < D; ++d) t += hs[1 + d];
-        grad[1] = bad ? __builtin_nan("") : t / (e.ell[0] * e.ell[0] * e.ell[0]);
-    } else {
-        for (int d = 0; d < D; ++d) grad[1 + d] = bad ? __builtin_nan("") : hs[1 + d] / (e.ell[d] * e.ell[d] * e.ell[d]);
-    }
+    if (*info != 0)
+        for (int q = 0; q <= n_ell; ++q) grad[q] = __builtin_nan("");
+    else
+        gpmi_grad_from_sums(hs, D, alpha, e.ell, n_ell, grad);
 }
 
 // A (rows x cols, ld) = NaN when *info != 0
@@ -2596,8 +2647,7 @@ static int exact_gp_vjp_core(gpmi_ctx *c, const double *dX, int n, int ldx, cons
     else
         hipLaunchKernelGGL(k_grad_partial_big<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, zero, c->W, ld, part, ns, 1, (size_t)0);
     hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, sums, ns);
-    VjpEll e;
-    for (int d = 0; d < GPMI_MAXD_BIG; ++d) e.ell[d] = d < n_ell ? ell[d] : 0.0;
+    const GradEll e = grad_ell(ell, n_ell);
     hipLaunchKernelGGL(k_vjp_finish, dim3(1), 64, 0, s, sums, p.D, alpha, e, n_ell, c->d_info, d_grad);
     if (dF) launch_nan_on_info(s, dF, (size_t)ldf, n, k, c->d_info);
     launch_nan_on_info(s, dZb, (size_t)ldzb, n, k, c->d_info);
@@ -2650,67 +2700,58 @@ extern "C" int gpmi_exact_gp_f_vjp(gpmi_ctx *c, const double *X, int n, int ldx,
     if (!X || !Z || !Fbar || !Zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    hipStream_t s = c->stream;
-    const size_t nk = (size_t)n * k;
     if (small_vjp(c, n, D, k)) {
-        // one launch of one workgroup; inputs in and results out through the pinned, device-mapped buffer:
-        // [info, flag | grad (1 + D) | F | Zbar | X | Z | Fbar]
-        const size_t o_g = 8, o_f = 16, o_zb = o_f + nk, o_x = o_zb + nk, o_z = o_x + (size_t)n * D, o_fb = o_z + nk;
-        if ((rc = pin_reserve(c, (o_fb + nk) * sizeof(double)))) return rc;
-        double *h = c->h_pin, *stage;
-        for (int d = 0; d < D; ++d) memcpy(h + o_x + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        for (int q = 0; q < k; ++q) {
-            memcpy(h + o_z + (size_t)q * n, Z + (size_t)q * ldz, (size_t)n * sizeof(double));
-            memcpy(h + o_fb + (size_t)q * n, Fbar + (size_t)q * ldfb, (size_t)n * sizeof(double));
-        }
-        if ((rc = scratch_buf(c, (size_t)n * (D + 2 * k) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 4))) return rc;
-        const int seq = ++c->pin_seq;
-        __atomic_store_n((int *)(h + 7), 0, __ATOMIC_RELEASE);   // armed before the launch: a stale word never reads as done
-        double *pd = c->h_pin_dev;
-        launch_exact_gp_vjp_small(s, pd + o_x, n, n, p, jitter, pd + o_z, k, n, pd + o_fb, n, F ? pd + o_f : nullptr, n, pd + o_zb, n, c->W,
-                                  alpha, ell, n_ell, pd + o_g, (int *)pd, c->d_info, stage, (int *)(pd + 7), seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
-        for (int q = 0; q < k; ++q) {
-            if (F) memcpy(F + (size_t)q * ldf, h + o_f + (size_t)q * n, (size_t)n * sizeof(double));
-            memcpy(Zbar + (size_t)q * ldzb, h + o_zb + (size_t)q * n, (size_t)n * sizeof(double));
-        }
-        memcpy(grad, h + o_g, (size_t)(1 + n_ell) * sizeof(double));
-        return *(const int *)h;
+        // one launch of one workgroup; inputs in and results out through the pinned, device-mapped buffer
+        PinCall pc(c);
+        const size_t g_ = pc.out(grad, 1 + n_ell, 1, 1 + n_ell), F_ = pc.out(F, n, k, ldf), Zb_ = pc.out(Zbar, n, k, ldzb),
+                     X_ = pc.in(X, n, D, ldx), Z_ = pc.in(Z, n, k, ldz), Fb_ = pc.in(Fbar, n, k, ldfb);
+        if ((rc = pc.begin((size_t)n * (D + 2 * k), n, 4))) return rc;
+        launch_exact_gp_vjp_small(c->stream, pc.dev(X_), n, n, p, jitter, pc.dev(Z_), k, n, pc.dev(Fb_), n, F ? pc.dev(F_) : nullptr, n,
+                                  pc.dev(Zb_), n, c->W, alpha, ell, n_ell, pc.dev(g_), pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
+        return pc.finish();
     }
-    // blocked chain: [X | Z | Fbar | F | Zbar | grad (65) | info] staged in device memory
-    double *d;
-    const size_t o_z = (size_t)n * D, o_fb = o_z + nk, o_f = o_fb + nk, o_zb = o_f + nk, o_g = o_zb + nk, o_i = o_g + 1 + GPMI_MAXD_BIG;
-    if ((rc = stage_buf(c, 0, (o_i + 1) * sizeof(double), &d))) return rc;
-    if ((rc = h2d_matrix(c, X, n, D, ldx, d))) return rc;
-    if ((rc = h2d_matrix(c, Z, n, k, ldz, d + o_z))) return rc;
-    if ((rc = h2d_matrix(c, Fbar, n, k, ldfb, d + o_fb))) return rc;
-    if ((rc = exact_gp_vjp_core(c, d, n, n, p, alpha, ell, n_ell, jitter, d + o_z, k, n, d + o_fb, n, F ? d + o_f : nullptr, n, d + o_zb,
-                                n, d + o_g, (int *)(d + o_i))))
+    // blocked chain, staged in device memory
+    StageCall sc(c);
+    const size_t X_ = sc.in(X, n, D, ldx), Z_ = sc.in(Z, n, k, ldz), Fb_ = sc.in(Fbar, n, k, ldfb), F_ = sc.out(F, n, k, ldf),
+                 Zb_ = sc.out(Zbar, n, k, ldzb), g_ = sc.out(grad, 1 + n_ell, 1, 1 + n_ell);
+    if ((rc = sc.begin())) return rc;
+    if ((rc = exact_gp_vjp_core(c, sc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, sc.dev(Z_), k, n, sc.dev(Fb_), n,
+                                F ? sc.dev(F_) : nullptr, n, sc.dev(Zb_), n, sc.dev(g_), sc.info())))
         return rc;
-    int info = 0;
-    if (F && (rc = d2h_matrix(c, d + o_f, (size_t)n, n, k, F, ldf))) return rc;
-    if ((rc = d2h_matrix(c, d + o_zb, (size_t)n, n, k, Zbar, ldzb))) return rc;
-    HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return info;
+    return sc.finish(sc.info());
 }
 
 // ---- latent GP: forward product, likelihood head, its adjoint and the reverse sweep with ONE factorisation -------------------
 // (models/exact_gp.stan, fit_full_gp.stan: NORMAL; westbrook_exact.stan: BERNOULLI_LOGIT; heteroscedastic.stan: NORMAL_LOGSD)
-static int latent_check(int n, int ldx, int D, double alpha, int k, int ldz, int family, int m, int ldy, double sigma, bool hasF,
-                        int ldf, bool hasFb, int ldfb, int ldzb)
+// a likelihood head's arguments: the family, its number of latent columns k, the m replicate columns of Y and sigma
+static int lik_head_check(int family, int k, int m, int ldy, int n, double sigma, bool allow_none)
 {
-    int rc;
-    if ((rc = exact_gp_vjp_check(n, ldx, D, alpha, k, ldz, hasFb ? ldfb : n, hasF, ldf, ldzb))) return rc;
+    if (allow_none && family == GPMI_LIK_NONE) return 0;
     if (family != GPMI_LIK_NORMAL && family != GPMI_LIK_BERNOULLI_LOGIT && family != GPMI_LIK_NORMAL_LOGSD)
         return gpmi_fail(GPMI_EARG, "unknown likelihood family");
     if (k != (family == GPMI_LIK_NORMAL_LOGSD ? 2 : 1)) return gpmi_fail(GPMI_EARG, "k must be 2 for NORMAL_LOGSD and 1 otherwise");
     if (m < 1 || ldy < n) return gpmi_fail(GPMI_EARG, "bad size or leading dimension of Y");
     if (family == GPMI_LIK_NORMAL && (!(sigma > 0.0) || !isfinite(sigma))) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
     return 0;
+}
+
+// host Y of the BERNOULLI_LOGIT head: outcomes are 0 or 1
+static int bernoulli_y_check(const double *Y, int n, int m, int ldy)
+{
+    for (int q = 0; q < m; ++q)
+        for (int i = 0; i < n; ++i) {
+            const double v = Y[(size_t)i + (size_t)q * ldy];
+            if (v != 0.0 && v != 1.0) return gpmi_fail(GPMI_EARG, "BERNOULLI_LOGIT: y must be 0 or 1");
+        }
+    return 0;
+}
+
+static int latent_check(int n, int ldx, int D, double alpha, int k, int ldz, int family, int m, int ldy, double sigma, bool hasF,
+                        int ldf, bool hasFb, int ldfb, int ldzb)
+{
+    int rc;
+    if ((rc = exact_gp_vjp_check(n, ldx, D, alpha, k, ldz, hasFb ? ldfb : n, hasF, ldf, ldzb))) return rc;
+    return lik_head_check(family, k, m, ldy, n, sigma, false);
 }
 
 extern "C" int gpmi_latent_gp_lp_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
@@ -2745,67 +2786,34 @@ extern "C" int gpmi_latent_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int l
     int rc;
     if ((rc = latent_check(n, ldx, D, alpha, k, ldz, family, m, ldy, sigma, F != nullptr, ldf, Fbar != nullptr, ldfb, ldzb))) return rc;
     if (!X || !Z || !Y || !out || !Zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
-    if (family == GPMI_LIK_BERNOULLI_LOGIT)
-        for (int q = 0; q < m; ++q)
-            for (int i = 0; i < n; ++i) {
-                const double v = Y[(size_t)i + (size_t)q * ldy];
-                if (v != 0.0 && v != 1.0) return gpmi_fail(GPMI_EARG, "BERNOULLI_LOGIT: y must be 0 or 1");
-            }
+    if (family == GPMI_LIK_BERNOULLI_LOGIT && (rc = bernoulli_y_check(Y, n, m, ldy))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    hipStream_t s = c->stream;
-    const size_t nk = (size_t)n * k, nm = (size_t)n * m;
+    const double log_sigma = family == GPMI_LIK_NORMAL ? log(sigma) : 0.0;
     if (small_vjp(c, n, D, k)) {
-        // one launch of one workgroup through the pinned, device-mapped buffer:
-        // [info, .., out (2), .., flag | grad (1 + D) | F | Fbar | Zbar | X | Z | Y]
-        const size_t o_out = 2, o_g = 8, o_f = 24, o_fb = o_f + nk, o_zb = o_fb + nk, o_x = o_zb + nk, o_z = o_x + (size_t)n * D,
-                     o_y = o_z + nk;
-        if ((rc = pin_reserve(c, (o_y + nm) * sizeof(double)))) return rc;
-        double *h = c->h_pin, *stage;
-        for (int d = 0; d < D; ++d) memcpy(h + o_x + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        for (int q = 0; q < k; ++q) memcpy(h + o_z + (size_t)q * n, Z + (size_t)q * ldz, (size_t)n * sizeof(double));
-        for (int q = 0; q < m; ++q) memcpy(h + o_y + (size_t)q * n, Y + (size_t)q * ldy, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, ((size_t)n * (D + k) + nm) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 4))) return rc;
-        const int seq = ++c->pin_seq;
-        __atomic_store_n((int *)(h + 7), 0, __ATOMIC_RELEASE);   // armed before the launch: a stale word never reads as done
-        double *pd = c->h_pin_dev;
-        const LatentHead lh{family, pd + o_y, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-        launch_latent_gp_small(s, pd + o_x, n, n, p, jitter, pd + o_z, k, n, lh, pd + o_out, Fbar ? pd + o_fb : nullptr, n,
-                               F ? pd + o_f : nullptr, n, pd + o_zb, n, c->W, alpha, ell, n_ell, pd + o_g, (int *)pd, c->d_info, stage,
-                               (int *)(pd + 7), seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
-        for (int q = 0; q < k; ++q) {
-            if (F) memcpy(F + (size_t)q * ldf, h + o_f + (size_t)q * n, (size_t)n * sizeof(double));
-            if (Fbar) memcpy(Fbar + (size_t)q * ldfb, h + o_fb + (size_t)q * n, (size_t)n * sizeof(double));
-            memcpy(Zbar + (size_t)q * ldzb, h + o_zb + (size_t)q * n, (size_t)n * sizeof(double));
-        }
-        memcpy(out, h + o_out, 2 * sizeof(double));
-        memcpy(grad, h + o_g, (size_t)(1 + n_ell) * sizeof(double));
-        return *(const int *)h;
+        // one launch of one workgroup through the pinned, device-mapped buffer
+        PinCall pc(c);
+        const size_t out_ = pc.out(out, 2, 1, 2), g_ = pc.out(grad, 1 + n_ell, 1, 1 + n_ell), F_ = pc.out(F, n, k, ldf),
+                     Fb_ = pc.out(Fbar, n, k, ldfb), Zb_ = pc.out(Zbar, n, k, ldzb), X_ = pc.in(X, n, D, ldx), Z_ = pc.in(Z, n, k, ldz),
+                     Y_ = pc.in(Y, n, m, ldy);
+        if ((rc = pc.begin((size_t)n * (D + k + m), n, 4))) return rc;
+        const LatentHead lh{family, pc.dev(Y_), m, n, sigma, log_sigma};
+        launch_latent_gp_small(c->stream, pc.dev(X_), n, n, p, jitter, pc.dev(Z_), k, n, lh, pc.dev(out_), Fbar ? pc.dev(Fb_) : nullptr, n,
+                               F ? pc.dev(F_) : nullptr, n, pc.dev(Zb_), n, c->W, alpha, ell, n_ell, pc.dev(g_), pc.info(), c->d_info,
+                               pc.stage, pc.flag(), pc.seq);
+        return pc.finish();
     }
-    // blocked chain: [X | Z | Y | F | Fbar | Zbar | grad (65) | out (2) | info] staged in device memory
-    double *d;
-    const size_t o_z = (size_t)n * D, o_y = o_z + nk, o_f = o_y + nm, o_fb = o_f + nk, o_zb = o_fb + nk, o_g = o_zb + nk,
-                 o_out = o_g + 1 + GPMI_MAXD_BIG, o_i = o_out + 2;
-    if ((rc = stage_buf(c, 0, (o_i + 1) * sizeof(double), &d))) return rc;
-    if ((rc = h2d_matrix(c, X, n, D, ldx, d))) return rc;
-    if ((rc = h2d_matrix(c, Z, n, k, ldz, d + o_z))) return rc;
-    if ((rc = h2d_matrix(c, Y, n, m, ldy, d + o_y))) return rc;
-    const LatentHead lh{family, d + o_y, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-    if ((rc = exact_gp_vjp_core(c, d, n, n, p, alpha, ell, n_ell, jitter, d + o_z, k, n, nullptr, n, F ? d + o_f : nullptr, n, d + o_zb, n,
-                                d + o_g, (int *)(d + o_i), &lh, d + o_fb, d + o_out)))
+    // blocked chain, staged in device memory
+    StageCall sc(c);
+    const size_t X_ = sc.in(X, n, D, ldx), Z_ = sc.in(Z, n, k, ldz), Y_ = sc.in(Y, n, m, ldy), F_ = sc.out(F, n, k, ldf),
+                 Fb_ = sc.out(Fbar, n, k, ldfb), Zb_ = sc.out(Zbar, n, k, ldzb), g_ = sc.out(grad, 1 + n_ell, 1, 1 + n_ell),
+                 out_ = sc.out(out, 2, 1, 2);
+    if ((rc = sc.begin())) return rc;
+    const LatentHead lh{family, sc.dev(Y_), m, n, sigma, log_sigma};
+    if ((rc = exact_gp_vjp_core(c, sc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, sc.dev(Z_), k, n, nullptr, n, F ? sc.dev(F_) : nullptr,
+                                n, sc.dev(Zb_), n, sc.dev(g_), sc.info(), &lh, sc.dev(Fb_), sc.dev(out_))))
         return rc;
-    int info = 0;
-    if (F && (rc = d2h_matrix(c, d + o_f, (size_t)n, n, k, F, ldf))) return rc;
-    if (Fbar && (rc = d2h_matrix(c, d + o_fb, (size_t)n, n, k, Fbar, ldfb))) return rc;
-    if ((rc = d2h_matrix(c, d + o_zb, (size_t)n, n, k, Zbar, ldzb))) return rc;
-    HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out, d + o_out, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return info;
+    return sc.finish(sc.info());
 }
 
 // ---- centred latent GP: the k latent columns are parameters, the GP their prior (models/heteroscedastic_centered.stan:24-34) ----
@@ -2852,7 +2860,7 @@ __global__ __launch_bounds__(256) void k_cen_value_part(const double *__restrict
 __global__ __launch_bounds__(256) void k_cen_finish(const double *__restrict__ A, const double *__restrict__ Fb, int n, int k,
                                                     double *__restrict__ Fg, size_t ldfg, const double *__restrict__ vpart, int nslice,
                                                     const double *__restrict__ lik2, const double *__restrict__ hs, int D, double alpha,
-                                                    VjpEll e, int n_ell, const int *__restrict__ info, double *__restrict__ out,
+                                                    GradEll e, int n_ell, const int *__restrict__ info, double *__restrict__ out,
                                                     double *__restrict__ grad, int *__restrict__ info_out)
 {
     const bool bad = *info != 0;
@@ -2874,14 +2882,10 @@ __global__ __launch_bounds__(256) void k_cen_finish(const double *__restrict__ A
     out[1] = bad ? nan : dsig;
     out[2] = bad ? nan : sl;
     out[3] = bad ? nan : zz;
-    grad[0] = bad ? nan : 2.0 * hs[0] / alpha;
-    if (n_ell == 1) {
-        double t = 0.0;
-        for (int d = 0; d < D; ++d) t += hs[1 + d];
-        grad[1] = bad ? nan : t / (e.ell[0] * e.ell[0] * e.ell[0]);
-    } else {
-        for (int d = 0; d < D; ++d) grad[1 + d] = bad ? nan : hs[1 + d] / (e.ell[d] * e.ell[d] * e.ell[d]);
-    }
+    if (bad)
+        for (int q = 0; q <= n_ell; ++q) grad[q] = nan;
+    else
+        gpmi_grad_from_sums(hs, D, alpha, e.ell, n_ell, grad);
     *info_out = *info;
 }
 }  // namespace
@@ -2942,8 +2946,7 @@ static int centered_gp_core(gpmi_ctx *c, const double *dX, int n, int ldx, const
                            (size_t)n);
     hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, sums, ns);
     if (head) launch_latent_head(s, dF, (size_t)ldf, n, k, lh, Fb, (size_t)n, hpart, lik2, c->d_info);
-    VjpEll e;
-    for (int d = 0; d < GPMI_MAXD_BIG; ++d) e.ell[d] = d < n_ell ? ell[d] : 0.0;
+    const GradEll e = grad_ell(ell, n_ell);
     const unsigned fblocks = (unsigned)((nk + 255) / 256 < 1024 ? (nk + 255) / 256 : 1024);
     hipLaunchKernelGGL(k_cen_finish, dim3(fblocks), 256, 0, s, Av, head ? Fb : nullptr, n, k, dFg, (size_t)ldfg, vpart, nslice,
                        head ? lik2 : nullptr, sums, p.D, alpha, e, n_ell, c->d_info, d_out, d_grad, d_info);
@@ -2955,13 +2958,7 @@ static int centered_check(int n, int ldx, int D, double alpha, int k, int ldf, i
 {
     if (n < 1 || k < 1 || D < 1 || ldx < n || ldf < n || ldfg < n) return gpmi_fail(GPMI_EARG, "bad size or leading dimension");
     if (!(alpha > 0.0) || !isfinite(alpha)) return gpmi_fail(GPMI_EARG, "alpha must be positive and finite");
-    if (family == GPMI_LIK_NONE) return 0;
-    if (family != GPMI_LIK_NORMAL && family != GPMI_LIK_BERNOULLI_LOGIT && family != GPMI_LIK_NORMAL_LOGSD)
-        return gpmi_fail(GPMI_EARG, "unknown likelihood family");
-    if (k != (family == GPMI_LIK_NORMAL_LOGSD ? 2 : 1)) return gpmi_fail(GPMI_EARG, "k must be 2 for NORMAL_LOGSD and 1 otherwise");
-    if (m < 1 || ldy < n) return gpmi_fail(GPMI_EARG, "bad size or leading dimension of Y");
-    if (family == GPMI_LIK_NORMAL && (!(sigma > 0.0) || !isfinite(sigma))) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
-    return 0;
+    return lik_head_check(family, k, m, ldy, n, sigma, true);
 }
 
 // one workgroup (k_centered_gp_small) up to n <= tune.small_cen
@@ -3001,59 +2998,51 @@ extern "C" int gpmi_centered_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int
     if ((rc = centered_check(n, ldx, D, alpha, k, ldf, family, m, ldy, sigma, ldfg))) return rc;
     const bool head = family != GPMI_LIK_NONE;
     if (!X || !F || (head && !Y) || !out || !Fgrad || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
-    if (family == GPMI_LIK_BERNOULLI_LOGIT)
-        for (int q = 0; q < m; ++q)
-            for (int i = 0; i < n; ++i) {
-                const double v = Y[(size_t)i + (size_t)q * ldy];
-                if (v != 0.0 && v != 1.0) return gpmi_fail(GPMI_EARG, "BERNOULLI_LOGIT: y must be 0 or 1");
-            }
+    if (family == GPMI_LIK_BERNOULLI_LOGIT && (rc = bernoulli_y_check(Y, n, m, ldy))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    hipStream_t s = c->stream;
     if (!head) m = 0;
-    const size_t nk = (size_t)n * k, nm = (size_t)n * m;
+    const double log_sigma = family == GPMI_LIK_NORMAL ? log(sigma) : 0.0;
     if (small_cen(c, n, D, k)) {
-        // one launch of one workgroup through the pinned, device-mapped buffer:
-        // [info, .., out (4), .., flag | grad (1 + D) | Fgrad | X | F | Y]
-        const size_t o_out = 2, o_g = 8, o_fg = 24, o_x = o_fg + nk, o_f = o_x + (size_t)n * D, o_y = o_f + nk;
-        if ((rc = pin_reserve(c, (o_y + nm) * sizeof(double)))) return rc;
-        double *h = c->h_pin, *stage;
-        for (int d = 0; d < D; ++d) memcpy(h + o_x + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        for (int q = 0; q < k; ++q) memcpy(h + o_f + (size_t)q * n, F + (size_t)q * ldf, (size_t)n * sizeof(double));
-        for (int q = 0; q < m; ++q) memcpy(h + o_y + (size_t)q * n, Y + (size_t)q * ldy, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, ((size_t)n * (D + k) + nm) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n + k - 1, 2))) return rc;
-        const int seq = ++c->pin_seq;
-        __atomic_store_n((int *)(h + 7), 0, __ATOMIC_RELEASE);   // armed before the launch: a stale word never reads as done
-        double *pd = c->h_pin_dev;
-        const LatentHead lh{family, head ? pd + o_y : nullptr, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-        launch_centered_gp_small(s, pd + o_x, n, n, p, jitter, pd + o_f, k, n, lh, pd + o_out, pd + o_fg, n, c->W, alpha, ell, n_ell,
-                                 pd + o_g, (int *)pd, c->d_info, stage, (int *)(pd + 7), seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
-        for (int q = 0; q < k; ++q) memcpy(Fgrad + (size_t)q * ldfg, h + o_fg + (size_t)q * n, (size_t)n * sizeof(double));
-        memcpy(out, h + o_out, 4 * sizeof(double));
-        memcpy(grad, h + o_g, (size_t)(1 + n_ell) * sizeof(double));
-        return *(const int *)h;
+        // one launch of one workgroup through the pinned, device-mapped buffer
+        PinCall pc(c);
+        const size_t out_ = pc.out(out, 4, 1, 4), g_ = pc.out(grad, 1 + n_ell, 1, 1 + n_ell), Fg_ = pc.out(Fgrad, n, k, ldfg),
+                     X_ = pc.in(X, n, D, ldx), F_ = pc.in(F, n, k, ldf), Y_ = pc.in(Y, n, m, ldy);
+        if ((rc = pc.begin((size_t)n * (D + k + m), n + k - 1, 2))) return rc;
+        const LatentHead lh{family, head ? pc.dev(Y_) : nullptr, m, n, sigma, log_sigma};
+        launch_centered_gp_small(c->stream, pc.dev(X_), n, n, p, jitter, pc.dev(F_), k, n, lh, pc.dev(out_), pc.dev(Fg_), n, c->W, alpha,
+                                 ell, n_ell, pc.dev(g_), pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
+        return pc.finish();
     }
-    // blocked chain: [X | F | Y | Fgrad | grad (65) | out (4) | info] staged in device memory
-    double *d;
-    const size_t o_f = (size_t)n * D, o_y = o_f + nk, o_fg = o_y + nm, o_g = o_fg + nk, o_out = o_g + 1 + GPMI_MAXD_BIG, o_i = o_out + 4;
-    if ((rc = stage_buf(c, 0, (o_i + 1) * sizeof(double), &d))) return rc;
-    if ((rc = h2d_matrix(c, X, n, D, ldx, d))) return rc;
-    if ((rc = h2d_matrix(c, F, n, k, ldf, d + o_f))) return rc;
-    if (head && (rc = h2d_matrix(c, Y, n, m, ldy, d + o_y))) return rc;
-    const LatentHead lh{family, head ? d + o_y : nullptr, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-    if ((rc = centered_gp_core(c, d, n, n, p, alpha, ell, n_ell, jitter, d + o_f, k, n, lh, d + o_out, d + o_fg, n, d + o_g,
-                               (int *)(d + o_i))))
+    // blocked chain, staged in device memory
+    StageCall sc(c);
+    const size_t X_ = sc.in(X, n, D, ldx), F_ = sc.in(F, n, k, ldf), Y_ = sc.in(Y, n, m, ldy), Fg_ = sc.out(Fgrad, n, k, ldfg),
+                 g_ = sc.out(grad, 1 + n_ell, 1, 1 + n_ell), out_ = sc.out(out, 4, 1, 4);
+    if ((rc = sc.begin())) return rc;
+    const LatentHead lh{family, head ? sc.dev(Y_) : nullptr, m, n, sigma, log_sigma};
+    if ((rc = centered_gp_core(c, sc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, sc.dev(F_), k, n, lh, sc.dev(out_), sc.dev(Fg_), n,
+                               sc.dev(g_), sc.info())))
         return rc;
-    int info = 0;
-    if ((rc = d2h_matrix(c, d + o_fg, (size_t)n, n, k, Fgrad, ldfg))) return rc;
-    HIPCHK(hipMemcpyAsync(grad, d + o_g, (size_t)(1 + n_ell) * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out, d + o_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&info, d + o_i, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return info;
+    return sc.finish(sc.info());
+}
+
+// the G result records (stride doubles apart) and info words of a value + gradient grid -> out3 and grad, 3 per point
+static void grad_grid_unpack(const double *res, size_t stride, const int *info, int G, int D, const double *alpha, const double *rho,
+                             const double *sigma, double *out3, double *grad)
+{
+    for (int g = 0; g < G; ++g) logml_grad_unpack(res + (size_t)g * stride, info[g], D, alpha[g], &rho[g], 1, sigma[g], out3 + 3 * g, grad + 3 * g);
+}
+// ... from device memory (the chains' tail): records and info words down, the stream drained
+static int grad_grid_down(gpmi_ctx *c, const double *dres, size_t stride, const int *dinfo, int G, int D, const double *alpha,
+                          const double *rho, const double *sigma, double *out3, double *grad, int *info)
+{
+    std::vector<double> hr((size_t)G * stride);
+    HIPCHK(hipMemcpyAsync(hr.data(), dres, hr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    grad_grid_unpack(hr.data(), stride, info, G, D, alpha, rho, sigma, out3, grad);
+    return 0;
 }
 
 // G independent (alpha[g], rho[g], sigma[g]) points: value AND gradient of each, concurrently on the lanes -- what
@@ -3075,33 +3064,16 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
         if ((rc = fill_params(&ps[g], D, alpha[g], &rho[g], 1))) return rc;
     if (D <= GPMI_MAXD && n <= (G >= 2 ? c->tune.small_ng : c->tune.small_ng1) && G <= 8) {
         // a sampler's handful of chains: ONE launch, X, y in and the results out through the pinned, device-mapped buffer
-        // (no copy call, no stream synchronisation): [res (G x 13) | info (G ints) | flag | X | y]
-        const size_t o_info = (size_t)G * GPMI_SMALL_GRAD_RES, o_flag = o_info + (G + 1) / 2, o_x = o_flag + 1;
-        const size_t need = (o_x + (size_t)n * (D + 1)) * sizeof(double);
-        if ((rc = pin_reserve(c, need))) return rc;
-        double *hX = c->h_pin + o_x, *hy = hX + (size_t)n * D, *stage;
-        for (int d = 0; d < D; ++d) memcpy(hX + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-        memcpy(hy, y, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, (size_t)G * n * (D + 1) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 2 * G))) return rc;
+        // (no copy call, no stream synchronisation); one info word per point in a slot of their own
+        PinCall pc(c);
+        const size_t res_ = pc.mat(GPMI_SMALL_GRAD_RES, G), info_ = pc.mat((G + 1) / 2), X_ = pc.in(X, n, D, ldx), y_ = pc.in(y, n, 1, n);
+        if ((rc = pc.begin((size_t)G * n * (D + 1), n, 2 * G))) return rc;
         if ((rc = reserve_small_par(c, G))) return rc;
-        double *pd = c->h_pin_dev;
-        const int seq = ++c->pin_seq;
-        launch_logml_grad_small_batch(c->stream, pd + o_x, n, n, D, pd + o_x + (size_t)n * D, alpha, rho, sigma, G, jitter, c->W, pd,
-                                      (int *)(pd + o_info), c->d_sinfo, stage, (int *)(pd + o_flag), seq, c->d_ctr + 40);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(c->h_pin + o_flag), seq))) return rc;
-        const int *hinfo = (const int *)(c->h_pin + o_info);
-        for (int g = 0; g < G; ++g) {
-            const double *r = c->h_pin + (size_t)g * GPMI_SMALL_GRAD_RES;
-            info[g] = hinfo[g];
-            for (int k = 0; k < 3; ++k) out3[3 * g + k] = r[k];
-            if (info[g]) {
-                for (int k = 0; k < 3; ++k) grad[3 * g + k] = NAN;
-            } else {
-                logml_grad_finish(r + 3, D, alpha[g], &rho[g], 1, sigma[g], grad + 3 * g);
-            }
-        }
+        launch_logml_grad_small_batch(c->stream, pc.dev(X_), n, n, D, pc.dev(y_), alpha, rho, sigma, G, jitter, c->W, pc.dev(res_),
+                                      (int *)pc.dev(info_), c->d_sinfo, pc.stage, pc.flag(), pc.seq, c->d_ctr + 40);
+        if ((rc = pc.wait())) return rc;
+        memcpy(info, pc.host(info_), (size_t)G * sizeof(int));
+        grad_grid_unpack(pc.host(res_), GPMI_SMALL_GRAD_RES, info, G, D, alpha, rho, sigma, out3, grad);
         return 0;
     }
     if (D <= GPMI_MAXD && n <= (G >= 2 ? c->tune.small_ng : c->tune.small_ng1)) {
@@ -3118,21 +3090,7 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
             launch_logml_grad_small_batch(c->stream, dX, n, n, D, dy, alpha + g0, rho + g0, sigma + g0, gc, jitter, c->W,
                                           dres + (size_t)g0 * GPMI_SMALL_GRAD_RES, dinfo + g0, c->d_sinfo);
         }
-        std::vector<double> hr((size_t)G * GPMI_SMALL_GRAD_RES);
-        HIPCHK(hipMemcpyAsync(hr.data(), dres, hr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipGetLastError());
-        for (int g = 0; g < G; ++g) {
-            const double *r = hr.data() + (size_t)g * GPMI_SMALL_GRAD_RES;
-            for (int k = 0; k < 3; ++k) out3[3 * g + k] = r[k];
-            if (info[g]) {
-                for (int k = 0; k < 3; ++k) grad[3 * g + k] = NAN;
-            } else {
-                logml_grad_finish(r + 3, D, alpha[g], &rho[g], 1, sigma[g], grad + 3 * g);
-            }
-        }
-        return 0;
+        return grad_grid_down(c, dres, GPMI_SMALL_GRAD_RES, dinfo, G, D, alpha, rho, sigma, out3, grad, info);
     }
     int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
     if (lanes > 8) lanes = 8;
@@ -3156,21 +3114,7 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
     }
     lanes_join(c, lanes, caller, la_saved);
     if (rc) return rc;
-    std::vector<double> hr((size_t)G * GRAD_RES);
-    HIPCHK(hipMemcpyAsync(hr.data(), dres, hr.size() * sizeof(double), hipMemcpyDeviceToHost, caller));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, caller));
-    HIPCHK(hipStreamSynchronize(caller));
-    HIPCHK(hipGetLastError());
-    for (int g = 0; g < G; ++g) {
-        const double *r = hr.data() + (size_t)g * GRAD_RES;
-        for (int k = 0; k < 3; ++k) out3[3 * g + k] = r[k];
-        if (info[g]) {
-            for (int k = 0; k < 3; ++k) grad[3 * g + k] = NAN;
-        } else {
-            logml_grad_finish(r + 3, D, alpha[g], &rho[g], 1, sigma[g], grad + 3 * g);
-        }
-    }
-    return 0;
+    return grad_grid_down(c, dres, GRAD_RES, dinfo, G, D, alpha, rho, sigma, out3, grad, info);
 }
 
 // ---- GP posterior ---------------------------------------------------------------
@@ -3186,26 +3130,16 @@ extern "C" int gpmi_gp_condition(gpmi_ctx *c, const double *t, int n, const doub
     int rc;
     const int nt = n + m, M = nt + 1;
     if (c->tune.small_gc > 0 && M <= c->tune.small_gc) {
-        // R/tests.R sizes: ONE launch of one workgroup; t, ts, y go in and mn, Kn, info come back through a pinned,
-        // device-mapped buffer (no copy call): layout [info | mn (m) | Kn (m x m) | t | ts | y]
-        const size_t need = (8 + (size_t)m + (size_t)m * m + 2 * (size_t)n + m) * sizeof(double);
-        if ((rc = pin_reserve(c, need))) return rc;
-        double *hmn = c->h_pin + 8, *hKn = hmn + m, *ht = hKn + (size_t)m * m, *hts = ht + n, *hy = hts + m, *stage;
-        memcpy(ht, t, (size_t)n * sizeof(double));
-        memcpy(hts, ts, (size_t)m * sizeof(double));
-        memcpy(hy, y, (size_t)n * sizeof(double));
-        if ((rc = scratch_buf(c, (2 * (size_t)n + m) * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, nt, 1))) return rc;
-        double *pd = c->h_pin_dev;
-        const size_t o_mn = 8, o_Kn = o_mn + m, o_t = o_Kn + (size_t)m * m, o_ts = o_t + n, o_y = o_ts + m;
-        launch_gp_condition_small(c->stream, pd + o_t, n, pd + o_ts, m, pd + o_y, kindK, kindS, kindSS, (flags & GPMI_COMPAT_RR) ? 1 : 0,
-                                  alpha * alpha, l * l, s2, jitter, c->W, pd + o_Kn, (size_t)m, pd + o_mn, (int *)pd, c->d_info, stage,
-                                  (int *)(pd + 7), ++c->pin_seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(c->h_pin + 7), c->pin_seq))) return rc;
-        memcpy(mn, hmn, (size_t)m * sizeof(double));
-        for (int j = 0; j < m; ++j) memcpy(Kn + (size_t)j * ldkn, hKn + (size_t)j * m, (size_t)m * sizeof(double));
-        return *(const int *)c->h_pin;
+        // R/tests.R sizes: ONE launch of one workgroup; t, ts, y go in and mn, Kn, info come back through the pinned,
+        // device-mapped buffer (no copy call)
+        PinCall pc(c);
+        const size_t mn_ = pc.out(mn, m, 1, m), Kn_ = pc.out(Kn, m, m, ldkn), t_ = pc.in(t, n, 1, n), ts_ = pc.in(ts, m, 1, m),
+                     y_ = pc.in(y, n, 1, n);
+        if ((rc = pc.begin(2 * (size_t)n + m, nt, 1))) return rc;
+        launch_gp_condition_small(c->stream, pc.dev(t_), n, pc.dev(ts_), m, pc.dev(y_), kindK, kindS, kindSS,
+                                  (flags & GPMI_COMPAT_RR) ? 1 : 0, alpha * alpha, l * l, s2, jitter, c->W, pc.dev(Kn_), (size_t)m,
+                                  pc.dev(mn_), pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
+        return pc.finish();
     }
     if ((rc = reserve_ws(c, M, nt))) return rc;
     const size_t ld = (size_t)c->ld;
@@ -3216,9 +3150,9 @@ extern "C" int gpmi_gp_condition(gpmi_ctx *c, const double *t, int n, const doub
     const int ldo = (m + 1) & ~1;
     if ((rc = stage_buf(c, 2, (size_t)ldo * (m + 1) * sizeof(double), &dKn))) return rc;
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(dt, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dts, ts, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = h2d_matrix(c, t, n, 1, n, dt))) return rc;
+    if ((rc = h2d_matrix(c, ts, m, 1, m, dts))) return rc;
+    if ((rc = h2d_matrix(c, y, n, 1, n, dy))) return rc;
     HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
     const double a2 = alpha * alpha;
     const int compat = (flags & GPMI_COMPAT_RR) ? 1 : 0;
@@ -3236,12 +3170,9 @@ extern "C" int gpmi_gp_condition(gpmi_ctx *c, const double *t, int n, const doub
     double *dmn = dKn + (size_t)ldo * m;  // spare column of the output staging
     launch_get_row(s, c->W, ld, nt, n, m, -1.0, dmn);
     HIPCHK(hipGetLastError());
-    int info = 0;
-    HIPCHK(hipMemcpyAsync(&info, c->d_info, sizeof(int), hipMemcpyDeviceToHost, s));
     if ((rc = d2h_matrix(c, dKn, (size_t)ldo, m, m, Kn, ldkn))) return rc;
-    HIPCHK(hipMemcpyAsync(mn, dmn, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return info;
+    if ((rc = d2h_matrix(c, dmn, (size_t)m, m, 1, mn, m))) return rc;
+    return staged_finish(c, c->d_info);
 }
 
 // ---- GP posterior at new D-dimensional inputs: pointwise mean and variance ---------------------------
@@ -3343,37 +3274,24 @@ extern "C" int gpmi_gp_predict(gpmi_ctx *c, const double *X, int n, int ldx, int
     const double diag_add = sigma * sigma + jitter;
     if (small_predict(c, n, m, D)) {
         // the reference's sizes: ONE launch; X, Xs, y go in and mean, var, info come back through the pinned, device-mapped
-        // buffer (no copy call): layout [info, flag | mean (m) | var (m) | X (n D) | Xs (m D) | y (n)]
-        const size_t o_mean = 8, o_var = o_mean + m, o_X = o_var + m, o_Xs = o_X + (size_t)n * D, o_y = o_Xs + (size_t)m * D;
-        if ((rc = pin_reserve(c, (o_y + n) * sizeof(double)))) return rc;
-        double *h = c->h_pin, *pd = c->h_pin_dev;
-        for (int d = 0; d < D; ++d) {
-            memcpy(h + o_X + (size_t)d * n, X + (size_t)d * ldx, (size_t)n * sizeof(double));
-            memcpy(h + o_Xs + (size_t)d * m, Xs + (size_t)d * ldxs, (size_t)m * sizeof(double));
-        }
-        memcpy(h + o_y, y, (size_t)n * sizeof(double));
-        if ((rc = reserve_ws_small(c, n + m, 1))) return rc;
-        const int seq = ++c->pin_seq;
-        launch_gp_predict_small(c->stream, pd + o_X, n, n, pd + o_Xs, m, m, pd + o_y, p, diag_add, c->W, pd + o_mean,
-                                var ? pd + o_var : nullptr, (int *)pd, c->d_info, (int *)(pd + 7), seq);
-        HIPCHK(hipGetLastError());
-        if ((rc = pin_wait(c, (const int *)(h + 7), seq))) return rc;
-        memcpy(mean, h + o_mean, (size_t)m * sizeof(double));
-        if (var) memcpy(var, h + o_var, (size_t)m * sizeof(double));
-        return *(const int *)h;
+        // buffer (no copy call; each input is read once: no staging scratch)
+        PinCall pc(c);
+        const size_t mean_ = pc.out(mean, m, 1, m), var_ = pc.out(var, m, 1, m), X_ = pc.in(X, n, D, ldx), Xs_ = pc.in(Xs, m, D, ldxs),
+                     y_ = pc.in(y, n, 1, n);
+        if ((rc = pc.begin(0, n + m, 1))) return rc;
+        launch_gp_predict_small(c->stream, pc.dev(X_), n, n, pc.dev(Xs_), m, m, pc.dev(y_), p, diag_add, c->W, pc.dev(mean_),
+                                var ? pc.dev(var_) : nullptr, pc.info(), c->d_info, pc.flag(), pc.seq);
+        return pc.finish();
     }
-    double *dX, *dy, *dXs;
-    if ((rc = stage_buf(c, 3, ((size_t)m * D + 2 * (size_t)m) * sizeof(double), &dXs))) return rc;
+    // the chain: Xs, mean and var in staging buffer 3 (X and y in 0 and 1, the core's own in 2)
+    StageCall sc(c);
+    const size_t Xs_ = sc.in(Xs, m, D, ldxs), mean_ = sc.out(mean, m, 1, m), var_ = sc.out(var, m, 1, m);
+    double *dX, *dy;
+    if ((rc = sc.begin(3))) return rc;
     if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = h2d_matrix(c, Xs, m, D, ldxs, dXs))) return rc;
-    double *dmean = dXs + (size_t)m * D, *dvar = var ? dmean + m : nullptr;
-    if ((rc = predict_core(c, dX, n, n, dy, p, diag_add, dXs, m, m, dmean, dvar, c->d_info + 1))) return rc;
-    int info = 0;
-    HIPCHK(hipMemcpyAsync(mean, dmean, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (var) HIPCHK(hipMemcpyAsync(var, dvar, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&info, c->d_info + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return info;
+    if ((rc = predict_core(c, dX, n, n, dy, p, diag_add, sc.dev(Xs_), m, m, sc.dev(mean_), var ? sc.dev(var_) : nullptr, c->d_info + 1)))
+        return rc;
+    return sc.finish(c->d_info + 1);
 }
 
 // ---- sample_derivs: one draw of the derivative process, fused on the device --------------------
@@ -3471,26 +3389,20 @@ extern "C" int gpmi_sample_derivs(gpmi_ctx *c, const double *t, int n, const dou
     ENTER(c);
     if (n <= 0 || m <= 0 || !t || !ts || !y || !z || !draw || !(l > 0.0)) return gpmi_fail(GPMI_EARG, "bad argument");
     int rc;
-    double *d;
     if ((rc = sample_derivs_reserve(c, n, m))) return rc;
-    if ((rc = stage_buf(c, 0, ((size_t)2 * n + 4 * (size_t)m + 8) * sizeof(double), &d))) return rc;
-    double *dt = d, *dy = d + n, *dts = dy + n, *dz = dts + m, *ddraw = dz + m, *dmu = ddraw + m;
-    int *dst = (int *)(dmu + m);
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(dt, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dts, ts, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dz, z, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
+    StageCall sc(c);
+    const size_t t_ = sc.in(t, n, 1, n), y_ = sc.in(y, n, 1, n), ts_ = sc.in(ts, m, 1, m), z_ = sc.in(z, m, 1, m),
+                 draw_ = sc.out(draw, m, 1, m), mu_ = sc.out(mu, m, 1, m);
+    if ((rc = sc.begin())) return rc;
     if (small_sample_derivs(c, n, m, 1)) {   // small enough that one workgroup beats the launch chain even for ONE draw
         const double par[3] = {l, a, sy};
-        if ((rc = sample_derivs_small(c, dt, n, dts, m, dy, par, 1, jitter, dz, ddraw, dmu, dst))) return rc;
-    } else if ((rc = sample_derivs_core(c, dt, n, dts, m, dy, a, l, sy * sy, jitter, dz, ddraw, dmu, dst))) return rc;
-    int st = 0;
-    HIPCHK(hipMemcpyAsync(draw, ddraw, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (mu) HIPCHK(hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&st, dst, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return st;
+        if ((rc = sample_derivs_small(c, sc.dev(t_), n, sc.dev(ts_), m, sc.dev(y_), par, 1, jitter, sc.dev(z_), sc.dev(draw_), sc.dev(mu_),
+                                      sc.info())))
+            return rc;
+    } else if ((rc = sample_derivs_core(c, sc.dev(t_), n, sc.dev(ts_), m, sc.dev(y_), a, l, sy * sy, jitter, sc.dev(z_), sc.dev(draw_),
+                                        sc.dev(mu_), sc.info())))
+        return rc;
+    return sc.finish(sc.info());
 }
 
 // B independent draws, draw b from (params[3 b .. 3 b + 2] = (l, a, sy), Y[:, b], Z[:, b]): the loop
@@ -3517,16 +3429,13 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
         for (int l = 0; l < lanes; ++l)
             if ((rc = sample_derivs_reserve(l ? c->lane[l - 1] : c, n, m))) return rc;
     }
-    double *d;
-    const size_t nb = (size_t)n * B, mb = (size_t)m * B;
-    if ((rc = stage_buf(c, 0, ((size_t)n + m + nb + 3 * mb + B + 8) * sizeof(double), &d))) return rc;
-    double *dt = d, *dts = dt + n, *dY = dts + m, *dZ = dY + nb, *dD = dZ + mb, *dM = dD + mb;
-    int *dst = (int *)(dM + mb);
+    StageCall sc(c);
+    const size_t t_ = sc.in(t, n, 1, n), ts_ = sc.in(ts, m, 1, m), Y_ = sc.in(Y, n, B, ldy), Z_ = sc.in(Z, m, B, ldz),
+                 D_ = sc.out(draws, m, B, ldd), M_ = sc.out(mus, m, B, ldmu), st_ = sc.mat((B + 1) / 2);   // one status word per draw
+    if ((rc = sc.begin())) return rc;
+    double *dt = sc.dev(t_), *dts = sc.dev(ts_), *dY = sc.dev(Y_), *dZ = sc.dev(Z_), *dD = sc.dev(D_), *dM = sc.dev(M_);
+    int *dst = (int *)sc.dev(st_);
     hipStream_t const caller = c->stream;
-    HIPCHK(hipMemcpyAsync(dt, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice, caller));
-    HIPCHK(hipMemcpyAsync(dts, ts, (size_t)m * sizeof(double), hipMemcpyHostToDevice, caller));
-    HIPCHK(hipMemcpy2DAsync(dY, (size_t)n * sizeof(double), Y, (size_t)ldy * sizeof(double), (size_t)n * sizeof(double), B, hipMemcpyHostToDevice, caller));
-    HIPCHK(hipMemcpy2DAsync(dZ, (size_t)m * sizeof(double), Z, (size_t)ldz * sizeof(double), (size_t)m * sizeof(double), B, hipMemcpyHostToDevice, caller));
     if (small) {
         if ((rc = sample_derivs_small(c, dt, n, dts, m, dY, params, B, jitter, dZ, dD, dM, dst))) return rc;
     } else {
@@ -3541,10 +3450,8 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
         lanes_join(c, lanes, caller, la_saved);
         if (rc) return rc;
     }
-    HIPCHK(hipMemcpy2DAsync(draws, (size_t)ldd * sizeof(double), dD, (size_t)m * sizeof(double), (size_t)m * sizeof(double), B, hipMemcpyDeviceToHost, caller));
-    if (mus) HIPCHK(hipMemcpy2DAsync(mus, (size_t)ldmu * sizeof(double), dM, (size_t)m * sizeof(double), (size_t)m * sizeof(double), B, hipMemcpyDeviceToHost, caller));
     HIPCHK(hipMemcpyAsync(info, dst, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, caller));
-    HIPCHK(hipStreamSynchronize(caller));
+    if ((rc = sc.finish(nullptr))) return rc;   // (one status word per draw, copied above)
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -20,6 +20,31 @@ struct SeParams {            // squared-exponential hyper-parameters, kernel-arg
     int D;
 };
 
+// The caller's length-scales as a kernel argument (n_ell of them, zero beyond)
+struct GradEll {
+    double ell[GPMI_MAXD_BIG];
+};
+inline GradEll grad_ell(const double *ell, int n_ell)
+{
+    GradEll e;
+    for (int d = 0; d < GPMI_MAXD_BIG; ++d) e.ell[d] = d < n_ell ? ell[d] : 0.0;
+    return e;
+}
+// grad[0 .. n_ell] = (d/dalpha, d/dell...) from the contraction sums hs[0 .. D] of the gradient kernels: the one statement of
+// every value + gradient entry point, on the host and in the finishing kernels.  Multiplications and one division, contraction
+// off: the operation order is part of the results.
+__host__ __device__ inline void gpmi_grad_from_sums(const double *hs, int D, double alpha, const double *ell, int n_ell, double *grad)
+{
+    grad[0] = 2.0 * hs[0] / alpha;
+    if (n_ell == 1) {
+        double t = 0.0;
+        for (int d = 0; d < D; ++d) t += hs[1 + d];
+        grad[1] = t / (ell[0] * ell[0] * ell[0]);
+    } else {
+        for (int d = 0; d < D; ++d) grad[1 + d] = hs[1 + d] / (ell[d] * ell[d] * ell[d]);
+    }
+}
+
 // Algorithm switches of one context (gpmi_set_option).  Per context, never process-global: two
 // contexts or two host threads do not change each other's algorithm; grid lanes copy their root's.
 struct gpmi_tuning {
