@@ -27,6 +27,7 @@ SYMBOLS = (
     "gpmi_joint_logml", "gpmi_joint_logml_dev", "gpmi_joint_logml_grid_dev", "gpmi_rbf_cov_chol", "gpmi_gp_condition", "gpmi_sample_derivs", "gpmi_sample_derivs_batch",
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
     "gpmi_interp_free", "gpmi_logml_grad", "gpmi_logml_grad_grid",
+    "gpmi_joint_logml_grad", "gpmi_joint_logml_grad_dev", "gpmi_joint_logml_grad_grid",
     "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
     "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy", "gpmi_seq_marginals",
@@ -442,6 +443,31 @@ class Context:
                                             _p(out), _p(g), _p(info)))
         return out, g, info
 
+    def joint_logml_grad(self, t, yy, alpha, l, sigma, jitter=1e-6):
+        """((logml, sum log L_ii, z'z), grad) of the joint [y; y'] model, grad = (d/dalpha, d/dl, d/dsigma) of logml;
+        raises NotPositiveDefinite."""
+        t = _vec(t); yy = _vec(yy)
+        if yy.size != 2 * t.size:
+            raise GpmiError(-1, "yy must stack [y; y'] (length 2N)")
+        out = np.empty(3); g = np.empty(3)
+        _chk(self._lib.gpmi_joint_logml_grad(self._h, _p(t), int(t.size), _p(yy), _d(alpha), _d(l), _d(sigma), _d(jitter),
+                                             _p(out), _p(g)))
+        return out, g
+
+    def joint_logml_grad_grid(self, t, yy, alpha, l, sigma, jitter=1e-6):
+        """(out (G, 3), grad (G, 3), info (G,)): joint_logml_grad at G points (alpha, l, sigma) on the same data, on the lanes;
+        a point that is not positive definite has info > 0 and a NaN gradient."""
+        t = _vec(t); yy = _vec(yy)
+        if yy.size != 2 * t.size:
+            raise GpmiError(-1, "yy must stack [y; y'] (length 2N)")
+        alpha, l, sigma = np.broadcast_arrays(np.asarray(alpha, float), np.asarray(l, float), np.asarray(sigma, float))
+        a = _vec(alpha); r = _vec(l); s = _vec(sigma)
+        G = a.size
+        out = np.empty((G, 3)); g = np.empty((G, 3)); info = np.zeros(G, dtype=np.int32)
+        _chk(self._lib.gpmi_joint_logml_grad_grid(self._h, _p(t), int(t.size), _p(yy), _p(a), _p(r), _p(s), G, _d(jitter),
+                                                  _p(out), _p(g), _p(info)))
+        return out, g, info
+
     # ---- Cholesky-factor interpolation over the length-scale ------------------
     def interp_build(self, x, lp):
         """Table of L(lp[p]), dL/dl(lp[p]) built and kept on the device (test_interpolate.R:9-19)."""
@@ -687,6 +713,13 @@ class Context:
     def joint_logml_dev(self, dt_ptr, n, dyy_ptr, alpha, l, sigma, jitter, dout_ptr, dinfo_ptr):
         _chk(self._lib.gpmi_joint_logml_dev(self._h, C.c_void_p(dt_ptr), int(n), C.c_void_p(dyy_ptr), _d(alpha),
                                             _d(l), _d(sigma), _d(jitter), C.c_void_p(dout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def joint_logml_grad_dev(self, dt_ptr, n, dyy_ptr, alpha, l, sigma, jitter, dout_ptr, dgrad_ptr, dinfo_ptr):
+        """Enqueued on the context's stream: d_out3 (3), d_grad (3) and d_info (1 int) are written by the device (NaN gradient and
+        info = k when the matrix is not positive definite); nothing is raised for that status."""
+        _chk(self._lib.gpmi_joint_logml_grad_dev(self._h, C.c_void_p(dt_ptr), int(n), C.c_void_p(dyy_ptr), _d(alpha), _d(l),
+                                                 _d(sigma), _d(jitter), C.c_void_p(dout_ptr), C.c_void_p(dgrad_ptr),
+                                                 C.c_void_p(dinfo_ptr)))
 
     def joint_logml_grid_dev(self, dt_ptr, n, dyy_ptr, alpha, l, sigma, jitter, dout_ptr, dinfo_ptr):
         a = _vec(alpha); r = _vec(l); s = _vec(sigma)

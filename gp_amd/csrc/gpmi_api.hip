@@ -2326,6 +2326,95 @@ __global__ __launch_bounds__(1024) void k_grad_final(const double *__restrict__ 
         __syncthreads();
     }
 }
+
+// The contraction of the joint [y; y'] model (gpmi_joint_logml_grad): S of order N = 2n over n time points, a = S^-1 yy (N
+// values; only products a_p a_q enter, so its sign is free), W the lower triangle of -S^-1, G = (a a' + W) / 2.  Per 64 x 64
+// tile of the lower triangle of the n x n PAIR grid, thread = one row i x 16 columns j <= i, one exp per pair for the four
+// blocks (as k_joint_cov, the same argument).  With r = t_i - t_j, u = r^2 / l^2, qq = a2 e, qr = qq r / l^2 (S[i, n + j];
+// S[n + i, j] = -qr), rr = qq (1 - u) / l^2 and w as in k_grad_partial, the slots per tile are
+//   [0] sum w G_ij qq + w G_{n+i,n+j} rr + 2 (G_{n+j,i} - G_{n+i,j}) qr                               (alpha / 2 times d/dalpha)
+//   [1] sum w G_ij qq u + w G_{n+i,n+j} qq (-u^2 + 5u - 2) / l^2 + 2 (G_{n+j,i} - G_{n+i,j}) qr (u - 2)    (l times d/dl)
+//   [2] sum_i G_ii over the first n diagonal entries                                           (d/dsigma over 2 sigma)
+// All four entries lie in the lower triangle of the order-N matrix.  Three of them are contiguous in i; (n + j, i) runs along
+// a row of W for the thread's i, so its 64 x 64 block (rows n + 64 tj, columns 64 ti) is read along columns into LDS and used
+// transposed; the row pitch of 65 doubles keeps both the column-wise writes and the transposed reads free of bank conflicts.
+constexpr int JGRAD_NS = 3, JGRAD_PITCH = 65;
+__global__ __launch_bounds__(256) void k_joint_grad_partial(const double *__restrict__ t, int n, double a2, double l2,
+                                                            const double *__restrict__ a, const double *__restrict__ W,
+                                                            size_t ld, double *__restrict__ part)
+{
+    __shared__ double xt[64 * JGRAD_PITCH], red[256];
+    const int ti = blockIdx.x, tj = blockIdx.y;
+    if (tj > ti) return;
+    const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    {   // xt[c][r] = W[n + 64 tj + r, 64 ti + c]: a wave reads 64 consecutive rows of one column
+        const int jr = tj * 64 + lane;
+        for (int cc = grp; cc < 64; cc += 4) {
+            const int ic = ti * 64 + cc;
+            xt[cc * JGRAD_PITCH + lane] = (jr < n && ic < n) ? W[(size_t)(n + jr) + (size_t)ic * ld] : 0.0;
+        }
+    }
+    __syncthreads();
+    const int i = ti * 64 + lane;
+    const int jl0 = grp * 16;
+    double acc[JGRAD_NS] = {0.0, 0.0, 0.0};
+    if (i < n) {
+        const double xi = t[i], ai = a[i], adi = a[n + i];
+        const double il2 = 1.0 / l2;
+        for (int q = 0; q < 16; ++q) {
+            const int j = tj * 64 + jl0 + q;
+            if (j >= n || j > i) break;
+            const double r = xi - t[j];
+            const double qq = a2 * exp(-(r * r / (2 * l2)));
+            const double u = r * r * il2, qr = qq * r * il2;
+            const double aj = a[j], adj = a[n + j];
+            const double gqq = 0.5 * (ai * aj + W[(size_t)i + (size_t)j * ld]);
+            const double grr = 0.5 * (adi * adj + W[(size_t)(n + i) + (size_t)(n + j) * ld]);
+            const double grq = 0.5 * (adi * aj + W[(size_t)(n + i) + (size_t)j * ld]);
+            const double gx = 0.5 * (adj * ai + xt[lane * JGRAD_PITCH + jl0 + q]);
+            const double w = (i == j) ? 1.0 : 2.0;
+            const double cx = 2.0 * (gx - grq) * qr;
+            acc[0] += w * gqq * qq + w * grr * (qq * (1.0 - u) * il2) + cx;
+            acc[1] += w * gqq * qq * u + w * grr * (qq * ((5.0 - u) * u - 2.0) * il2) + cx * (u - 2.0);
+            if (i == j) acc[2] += gqq;
+        }
+    }
+    const size_t slot = ((size_t)ti * (ti + 1) / 2 + tj) * JGRAD_NS;
+    for (int s = 0; s < JGRAD_NS; ++s) {  // fixed-shape tree per quantity: deterministic
+        red[threadIdx.x] = acc[s];
+        __syncthreads();
+        for (int h = 128; h > 0; h >>= 1) {
+            if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) part[slot + s] = red[0];
+        __syncthreads();
+    }
+}
+
+// k_grad_final for the joint model, finished on the device: grad[s] = scale[s] x (the tile slots of s summed in a fixed order),
+// NaN when the factorisation failed (*d_info != 0)
+struct JointGradScale {
+    double v[JGRAD_NS];
+};
+__global__ __launch_bounds__(1024) void k_joint_grad_final(const double *__restrict__ part, size_t ntiles, JointGradScale scale,
+                                                           const int *__restrict__ d_info, double *__restrict__ grad)
+{
+    __shared__ double red[1024];
+    const bool bad = *d_info != 0;
+    for (int s = 0; s < JGRAD_NS; ++s) {
+        double acc = 0.0;
+        for (size_t t = threadIdx.x; t < ntiles; t += 1024) acc += part[t * (size_t)JGRAD_NS + s];
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        for (int h = 512; h > 0; h >>= 1) {
+            if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) grad[s] = bad ? __builtin_nan("") : scale.v[s] * red[0];
+        __syncthreads();
+    }
+}
 }  // namespace
 
 // Mid sizes (n <= tune.grad_aug_n): K^-1 and a = K^-1 y from ONE augmented partial factorisation instead of a second and a
@@ -2357,21 +2446,26 @@ static bool grad_augmented(const gpmi_ctx *c, int n, bool many)
     return lim > 0 && n <= lim;
 }
 
-// every buffer logml_grad_core(c, ., n, ...) uses, at its final size
-static int logml_grad_reserve(gpmi_ctx *c, int n, int D, bool many = false)
+// One value + gradient chain for every model of the form out3 = logml(S(theta), obs), grad = <(a a' - S^-1) / 2, dS/dtheta>.
+// A model M names its matrix and its contraction:
+//   order()                       the order n of S;  ns(), ntiles(): slots per tile and tiles of its contraction
+//   obs()                         the n observations (the augmented row)
+//   build(c, s, W, ld)            writes the lower triangle of S
+//   contract(s, a, Wk, ld, part)  reduces the tile slots into part (ns() x ntiles() doubles) and finishes them; a = +-S^-1 obs
+//                                 (only products a_p a_q may enter), Wk the lower triangle of -S^-1, both in device memory
+
+// every buffer grad_chain_core(c, model of order n, ...) uses, at its final size
+static int grad_chain_reserve(gpmi_ctx *c, int n, int ns, size_t ntiles, bool many)
 {
-    const int ns = grad_ns(D);
     int rc;
     if (grad_augmented(c, n, many)) {
         if ((rc = reserve_ws(c, 2 * n + 1, 2 * n + 1))) return rc;
-        const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
         double *b;
         return stage_buf(c, 3, ((size_t)GRAD_NS_MAX + ntiles * ns) * sizeof(double), &b);
     }
     if ((rc = reserve_ws(c, n + 1, n))) return rc;
     const size_t ldu = (size_t)(((n + 15) / 16) * 16 + 16);
     const int npan = (n + GPMI_NB - 1) / GPMI_NB;
-    const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
     const int nchunk = (n + UMV_COLS - 1) / UMV_COLS;
     double *b;
     if ((rc = stage_buf(c, 2, ldu * (size_t)(n + 1) * sizeof(double), &b))) return rc;
@@ -2380,52 +2474,48 @@ static int logml_grad_reserve(gpmi_ctx *c, int n, int D, bool many = false)
 }
 
 // Device part of one value + gradient evaluation, enqueued on c->stream without synchronisation:
-// d_res[0..2] = (logml, sum log L_ii, z'z), d_res[3 .. 3 + grad_ns(D)) = the contraction sums, *d_info = status
-constexpr int GRAD_RES = 3 + GRAD_NS_MAX;
-static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
-                           double *d_res, int *d_info, bool many = false)
+// d_out3[0..2] = (logml, sum log L_ii, z'z), *d_info = status; the gradient is the model's (contract)
+template <class M>
+static int grad_chain_core(gpmi_ctx *c, const M &m, double *d_out3, int *d_info, bool many)
 {
     int rc;
-    if ((rc = logml_grad_reserve(c, n, p.D, many))) return rc;
-    const int ns = grad_ns(p.D);
+    const int n = m.order(), ns = m.ns();
+    const size_t ntiles = m.ntiles();
+    if ((rc = grad_chain_reserve(c, n, ns, ntiles, many))) return rc;
     if (grad_augmented(c, n, many)) {
         const int M2 = 2 * n + 1;
         const size_t ld = (size_t)c->ld;
-        const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
+        // the first GRAD_NS_MAX doubles of the buffer stay free (the layout of the three-chain route, where they follow z and a):
+        // the finished sums go wherever the model's contraction writes them
         double *sums = c->stage[3], *part = sums + GRAD_NS_MAX;
         hipStream_t s = c->stream;
         HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
-        launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, diag_add, 1, c->W, ld);
-        launch_set_row(s, c->W, ld, n, dy, n, n);
+        m.build(c, s, c->W, ld);
+        launch_set_row(s, c->W, ld, n, m.obs(), n, n);
         hipLaunchKernelGGL(k_aug_identity, dim3((n + 63) / 64, (n + 15) / 16), 256, 0, s, c->W + n + 1, ld, n);
         HIPCHK(hipMemsetAsync(c->W + (size_t)n * ld, 0, ld * (size_t)(n + 1) * sizeof(double), s));   // columns n .. 2n
         if ((rc = launch_potrf_partial(c, c->W, ld, M2, M2, n, c->d_info, nullptr))) return rc;
-        launch_logml_finalize(s, c->W, ld, n, n, c->d_info, d_res, d_info, c->d_fin);
+        launch_logml_finalize(s, c->W, ld, n, n, c->d_info, d_out3, d_info, c->d_fin);
         // trailing block at (n, n): [[-z'z, .], [-a, -K^-1]]; the products a_i a_j do not see a's sign
         const double *av = c->W + (size_t)(n + 1) + (size_t)n * ld;
         const double *Wk = c->W + (size_t)(n + 1) + (size_t)(n + 1) * ld;
-        if (p.D <= GPMI_MAXD)
-            hipLaunchKernelGGL(k_grad_partial<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, 1, (size_t)0);
-        else
-            hipLaunchKernelGGL(k_grad_partial_big<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, ns, 1, (size_t)0);
-        hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, d_res + 3, ns);
+        m.contract(s, av, Wk, ld, part);
         HIPCHK(hipGetLastError());
         return 0;
     }
-    const int M = n + 1;
+    const int M1 = n + 1;
     const size_t ld = (size_t)c->ld;
     const size_t ldu = (size_t)(((n + 15) / 16) * 16 + 16);
-    const size_t T = (size_t)((n + 63) / 64), ntiles = T * (T + 1) / 2;
     const int nchunk = (n + UMV_COLS - 1) / UMV_COLS;
     double *U = c->stage[2], *vec = c->stage[3], *Fall = c->scratch;
     double *zv = vec, *av = vec + n, *sums = vec + 2 * (size_t)n, *part = sums + GRAD_NS_MAX, *mvpart = part + ntiles * ns;
     hipStream_t s = c->stream;
     // factorisation with the augmented row, all panel factors kept
     HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
-    launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, diag_add, 1, c->W, ld);
-    launch_set_row(s, c->W, ld, n, dy, n, n);
-    if ((rc = launch_potrf_partial(c, c->W, ld, M, n, n, c->d_info, Fall))) return rc;
-    launch_logml_finalize(s, c->W, ld, n, n, c->d_info, d_res, d_info, c->d_fin);
+    m.build(c, s, c->W, ld);
+    launch_set_row(s, c->W, ld, n, m.obs(), n, n);
+    if ((rc = launch_potrf_partial(c, c->W, ld, M1, n, n, c->d_info, Fall))) return rc;
+    launch_logml_finalize(s, c->W, ld, n, n, c->d_info, d_out3, d_info, c->d_fin);
     launch_get_row(s, c->W, ld, n, 0, n, 1.0, zv);
     // U = L^-T, a = U z = K^-1 y
     hipLaunchKernelGGL(k_set_identity, dim3((n + 63) / 64, (n + 15) / 16), 256, 0, s, U, ldu, n);
@@ -2435,13 +2525,51 @@ static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const 
     // W(lower) = -U U^T = -K^-1
     HIPCHK(hipMemsetAsync(c->W, 0, ld * (size_t)n * sizeof(double), s));
     launch_syrk_uut(c, s, U, ldu, c->W, ld, n);
-    if (p.D <= GPMI_MAXD)   // register-resident coordinates
-        hipLaunchKernelGGL(k_grad_partial<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, c->W, ld, part, 1, (size_t)0);
-    else                    // any D: LDS-staged coordinates, one pass for the distances and one per dimension
-        hipLaunchKernelGGL(k_grad_partial_big<false>, dim3((unsigned)T, (unsigned)T), 256, 0, s, dX, n, ldx, p, av, c->W, ld, part, ns, 1, (size_t)0);
-    hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles, d_res + 3, ns);
+    m.contract(s, av, c->W, ld, part);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// the SE model of fit_hyperparameters.stan: S = K(X; alpha, ell) + diag_add I, the sums of k_grad_partial[_big] to `sums`
+struct SeGradModel {
+    const double *dX;
+    int n, ldx;
+    const double *dy;
+    const SeParams &p;   // the caller's: the model lives for one grad_chain_core call only; the kernels take p by value
+    double diag_add;
+    double *sums;
+    int order() const { return n; }
+    int ns() const { return grad_ns(p.D); }
+    size_t ntiles() const
+    {
+        const size_t T = (size_t)((n + 63) / 64);
+        return T * (T + 1) / 2;
+    }
+    const double *obs() const { return dy; }
+    void build(gpmi_ctx *c, hipStream_t s, double *W, size_t ld) const { launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, diag_add, 1, W, ld); }
+    void contract(hipStream_t s, const double *av, const double *Wk, size_t ld, double *part) const
+    {
+        const unsigned T = (unsigned)((n + 63) / 64);
+        if (p.D <= GPMI_MAXD)   // register-resident coordinates
+            hipLaunchKernelGGL(k_grad_partial<false>, dim3(T, T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, 1, (size_t)0);
+        else                    // any D: LDS-staged coordinates, one pass for the distances and one per dimension
+            hipLaunchKernelGGL(k_grad_partial_big<false>, dim3(T, T), 256, 0, s, dX, n, ldx, p, av, Wk, ld, part, ns(), 1, (size_t)0);
+        hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles(), sums, ns());
+    }
+};
+
+static int logml_grad_reserve(gpmi_ctx *c, int n, int D, bool many = false)
+{
+    const size_t T = (size_t)((n + 63) / 64);
+    return grad_chain_reserve(c, n, grad_ns(D), T * (T + 1) / 2, many);
+}
+
+// d_res[0..2] = (logml, sum log L_ii, z'z), d_res[3 .. 3 + grad_ns(D)) = the contraction sums, *d_info = status
+constexpr int GRAD_RES = 3 + GRAD_NS_MAX;
+static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
+                           double *d_res, int *d_info, bool many = false)
+{
+    return grad_chain_core(c, SeGradModel{dX, n, ldx, dy, p, diag_add, d_res + 3}, d_res, d_info, many);
 }
 
 // host part: (d/dalpha, d/dell..., d/dsigma) from the contraction sums
@@ -3115,6 +3243,143 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
     lanes_join(c, lanes, caller, la_saved);
     if (rc) return rc;
     return grad_grid_down(c, dres, GRAD_RES, dinfo, G, D, alpha, rho, sigma, out3, grad, info);
+}
+
+// ---- value and gradient of the joint [y; y'] model -------------------------------------------------------------------
+// grad_chain_core at order N = 2n with gpmi_joint_logml's matrix (launch_joint_cov, compat = 0), yy as the augmented row,
+// k_joint_grad_partial as the contraction and k_joint_grad_final writing (d/dalpha, d/dl, d/dsigma) -- or NaN -- on the
+// device.  grad_aug_n / grad_aug_ng apply to N.  Every size takes this blocked chain (no one-workgroup form).
+struct JointGradModel {
+    const double *dt;
+    int n;
+    const double *dyy;
+    double alpha, l, sigma, jitter;
+    double *d_grad;
+    const int *d_info;
+    int order() const { return 2 * n; }
+    int ns() const { return JGRAD_NS; }
+    size_t ntiles() const
+    {
+        const size_t T = (size_t)((n + 63) / 64);
+        return T * (T + 1) / 2;
+    }
+    const double *obs() const { return dyy; }
+    void build(gpmi_ctx *, hipStream_t s, double *W, size_t ld) const
+    {
+        launch_joint_cov(s, dt, n, alpha * alpha, l, sigma * sigma, jitter, 0, 1, W, ld);
+    }
+    void contract(hipStream_t s, const double *av, const double *Wk, size_t ld, double *part) const
+    {
+        const unsigned T = (unsigned)((n + 63) / 64);
+        hipLaunchKernelGGL(k_joint_grad_partial, dim3(T, T), 256, 0, s, dt, n, alpha * alpha, l * l, av, Wk, ld, part);
+        hipLaunchKernelGGL(k_joint_grad_final, dim3(1), 1024, 0, s, part, ntiles(), JointGradScale{{2.0 / alpha, 1.0 / l, 2.0 * sigma}},
+                           d_info, d_grad);
+    }
+};
+
+static int joint_grad_check(int n, double alpha, double l)
+{
+    if (n < 1) return gpmi_fail(GPMI_EARG, "n must be positive");
+    if (!(l > 0.0) || !std::isfinite(l)) return gpmi_fail(GPMI_EARG, "length-scale must be positive and finite");
+    if (!(alpha > 0.0)) return gpmi_fail(GPMI_EARG, "alpha must be positive");
+    return 0;
+}
+
+static int joint_logml_grad_reserve(gpmi_ctx *c, int n, bool many = false)
+{
+    const size_t T = (size_t)((n + 63) / 64);
+    return grad_chain_reserve(c, 2 * n, JGRAD_NS, T * (T + 1) / 2, many);
+}
+
+static int joint_logml_grad_core(gpmi_ctx *c, const double *dt, int n, const double *dyy, double alpha, double l, double sigma,
+                                 double jitter, double *d_out3, double *d_grad, int *d_info, bool many = false)
+{
+    return grad_chain_core(c, JointGradModel{dt, n, dyy, alpha, l, sigma, jitter, d_grad, d_info}, d_out3, d_info, many);
+}
+
+extern "C" int gpmi_joint_logml_grad_dev(gpmi_ctx *c, const double *dt, int n, const double *dyy, double alpha, double l,
+                                         double sigma, double jitter, double *d_out3, double *d_grad, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = joint_grad_check(n, alpha, l))) return rc;
+    if (!dt || !dyy || !d_out3 || !d_grad || !d_info) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    return joint_logml_grad_core(c, dt, n, dyy, alpha, l, sigma, jitter, d_out3, d_grad, d_info);
+}
+
+// t and yy into staging buffers 0 and 1 (2 and 3 belong to the chain)
+static int upload_joint(gpmi_ctx *c, const double *t, int n, const double *yy, double **dt, double **dyy)
+{
+    int rc;
+    if ((rc = stage_buf(c, 0, (size_t)n * sizeof(double), dt))) return rc;
+    if ((rc = stage_buf(c, 1, (size_t)2 * n * sizeof(double), dyy))) return rc;
+    if ((rc = h2d_matrix(c, t, n, 1, n, *dt))) return rc;
+    return h2d_matrix(c, yy, 2 * n, 1, 2 * n, *dyy);
+}
+
+extern "C" int gpmi_joint_logml_grad(gpmi_ctx *c, const double *t, int n, const double *yy, double alpha, double l, double sigma,
+                                     double jitter, double *out3, double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = joint_grad_check(n, alpha, l))) return rc;
+    if (!t || !yy || !out3 || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    double *dt, *dyy;
+    if ((rc = upload_joint(c, t, n, yy, &dt, &dyy))) return rc;
+    if ((rc = joint_logml_grad_reserve(c, n))) return rc;
+    double *dres = c->d_fin + 4096;  // second half of the finalize scratch: out3, then the gradient
+    if ((rc = joint_logml_grad_core(c, dt, n, dyy, alpha, l, sigma, jitter, dres, dres + 3, c->d_info + 1))) return rc;
+    double hr[6];
+    if ((rc = d2h_matrix(c, dres, 6, 6, 1, hr, 6))) return rc;
+    const int info = staged_finish(c, c->d_info + 1);
+    if (info >= 0) {
+        for (int k = 0; k < 3; ++k) out3[k] = hr[k], grad[k] = hr[3 + k];
+    }
+    return info;
+}
+
+// G points on the same data, on the lanes as gpmi_logml_grad_grid: six doubles per point behind the root's panel factors
+extern "C" int gpmi_joint_logml_grad_grid(gpmi_ctx *c, const double *t, int n, const double *yy, const double *alpha,
+                                          const double *l, const double *sigma, int G, double jitter, double *out3, double *grad,
+                                          int *info)
+{
+    ENTER(c);
+    if (G < 0) return gpmi_fail(GPMI_EARG, "negative grid size");
+    if (G == 0) return 0;
+    if (n < 1 || !t || !yy || !alpha || !l || !sigma || !out3 || !grad || !info) return gpmi_fail(GPMI_EARG, "bad argument");
+    int rc;
+    for (int g = 0; g < G; ++g)
+        if ((rc = joint_grad_check(n, alpha[g], l[g]))) return rc;
+    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
+    if (lanes > 8) lanes = 8;
+    if (lanes > G) lanes = G;
+    if ((rc = lanes_prepare(c, lanes))) return rc;
+    for (int k = 0; k < lanes; ++k)
+        if ((rc = joint_logml_grad_reserve(k ? c->lane[k - 1] : c, n, G > 1))) return rc;
+    double *dt, *dyy, *dres;
+    if ((rc = upload_joint(c, t, n, yy, &dt, &dyy))) return rc;
+    const int npan = (2 * n + GPMI_NB - 1) / GPMI_NB;
+    if ((rc = scratch_buf(c, ((size_t)npan * GPMI_FPACK + (size_t)G * 7 + 8) * sizeof(double), &dres))) return rc;
+    dres += (size_t)npan * GPMI_FPACK;
+    int *dinfo = (int *)(dres + (size_t)G * 6);
+    const int la_saved = c->lookahead;
+    hipStream_t const caller = c->stream;
+    lanes_fork(c, lanes, caller);
+    for (int g = 0; g < G && !rc; ++g) {
+        gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
+        double *r = dres + (size_t)g * 6;
+        rc = joint_logml_grad_core(lc, dt, n, dyy, alpha[g], l[g], sigma[g], jitter, r, r + 3, dinfo + g, G > 1);
+    }
+    lanes_join(c, lanes, caller, la_saved);
+    if (rc) return rc;
+    std::vector<double> hr((size_t)G * 6);
+    HIPCHK(hipMemcpyAsync(hr.data(), dres, hr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    for (int g = 0; g < G; ++g)
+        for (int k = 0; k < 3; ++k) out3[3 * g + k] = hr[6 * (size_t)g + k], grad[3 * g + k] = hr[6 * (size_t)g + 3 + k];
+    return 0;
 }
 
 // ---- GP posterior ---------------------------------------------------------------

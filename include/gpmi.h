@@ -285,6 +285,26 @@ GPMI_API int gpmi_joint_logml_grid_dev(gpmi_ctx *ctx, const double *dt, int n, c
                                        const double *l, const double *sigma, int G, double jitter, double *d_out3,
                                        int *d_info);
 
+/* Value AND gradient of gpmi_joint_logml through one factorisation of its order-2n matrix: out3 as there,
+ * grad[0..2] = d out3[0] / d(alpha, l, sigma) = 1/2 tr((a a' - S^-1) dS/dtheta), a = S^-1 yy, with S^-1 formed on the device and
+ * the four derivative blocks contracted from one exp per pair of time points.  Returns 0, or the order k of the first
+ * non-positive leading minor (out3 as gpmi_joint_logml returns it, grad = NaN).  The options "grad_aug_n" / "grad_aug_ng" apply to
+ * the order 2n.  All sums run in a fixed order: repeated calls give identical bits.  GPMI_EARG: n < 1, a NULL pointer, l <= 0 or
+ * not finite, alpha <= 0. */
+GPMI_API int gpmi_joint_logml_grad(gpmi_ctx *ctx, const double *t, int n, const double *yy, double alpha, double l, double sigma,
+                          double jitter, double *out3, double *grad /* 3 */);
+/* device-resident t, yy, d_out3 (3), d_grad (3), d_info (1 int): enqueued on the context's stream, no synchronisation; the
+ * device itself writes the NaN gradient of a matrix that is not positive definite */
+GPMI_API int gpmi_joint_logml_grad_dev(gpmi_ctx *ctx, const double *dt, int n, const double *dyy, double alpha, double l,
+                              double sigma, double jitter, double *d_out3, double *d_grad, int *d_info);
+/* G points (alpha[g], l[g], sigma[g]) on the same data, concurrently on the context's lanes: out3 3 G, grad 3 G, info G
+ * (a point that is not positive definite: NaN gradient, info[g] = k, and the grid continues).  Every point is bit-identical to
+ * the single call with its parameters wherever both take the same route (orders between grad_aug_ng and grad_aug_n do not, for
+ * G > 1).  GPMI_EARG also for G < 0; G = 0 returns 0. */
+GPMI_API int gpmi_joint_logml_grad_grid(gpmi_ctx *ctx, const double *t, int n, const double *yy, const double *alpha,
+                               const double *l, const double *sigma, int G, double jitter, double *out3, double *grad,
+                               int *info);
+
 /* ---- Rcpp export ------------------------------------------------------ */
 
 /* rbf_cov_chol(x1, l): Sigma_ij = exp(-(xi-xj)^2/(2 l^2)) + 1e-10 I, L = chol,

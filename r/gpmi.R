@@ -144,6 +144,18 @@ gp_log_marginal_grad_chains <- function(X, y, alpha, rho, sigma, jitter = 0) {
         rep_len(as.double(sigma), G), jitter)
 }
 
+# the joint [y; y'] model of ode_gp_library.R:29-30: value and gradient w.r.t. (alpha, l, sigma) of the log marginal likelihood
+# of yy = c(y, dy) at the times t, through one factorisation; feeds optim() as gp_log_marginal_grad does
+gpmi_joint_logml_grad <- function(t, y, dy, alpha, l, sigma, jitter = 1e-6)
+  .Call("gpmi_R_joint_logml_grad", as.double(t), c(as.double(y), as.double(dy)), alpha, l, sigma, jitter)
+
+# the same for several chains' (alpha, l, sigma) at once, concurrently on the GPU
+gpmi_joint_logml_grad_chains <- function(t, y, dy, alpha, l, sigma, jitter = 1e-6) {
+  G <- max(length(alpha), length(l), length(sigma))
+  .Call("gpmi_R_joint_logml_grad_grid", as.double(t), c(as.double(y), as.double(dy)), rep_len(as.double(alpha), G),
+        rep_len(as.double(l), G), rep_len(as.double(sigma), G), jitter)
+}
+
 gp_log_marginal_grid <- function(X, y, alpha, rho_vec, sigma_vec, jitter = 0) {
   g <- expand.grid(rho = rho_vec, sigma = sigma_vec)
   r <- .Call("gpmi_R_logml_grid", as.matrix(X), as.double(y), rep_len(as.double(alpha), nrow(g)), as.double(g$rho),

@@ -398,6 +398,42 @@ SEXP gpmi_R_logml_grad_grid(SEXP X, SEXP y, SEXP alpha, SEXP rho, SEXP sigma, SE
     return out;
 }
 
+/* the joint [y; y'] model (R/ode_gp_library.R:29-30): list(value = c(logml, sum log L_ii, z'z), grad = c(d/dalpha, d/dl,
+ * d/dsigma) of logml) through one factorisation of the order-2n matrix; yy = c(y, y') */
+SEXP gpmi_R_joint_logml_grad(SEXP t, SEXP yy, SEXP alpha, SEXP l, SEXP sigma, SEXP jitter)
+{
+    int n = Rf_length(t);
+    need(is_real(t) && is_real(yy), "t and yy must be double");
+    need(Rf_length(yy) == 2 * n, "yy must stack c(y, y'): length 2 * length(t)");
+    SEXP val = PROTECT(Rf_allocVector(REALSXP, 3)), g = PROTECT(Rf_allocVector(REALSXP, 3));
+    int rc = gpmi_joint_logml_grad(ctx(), REAL(t), n, REAL(yy), Rf_asReal(alpha), Rf_asReal(l), Rf_asReal(sigma), Rf_asReal(jitter),
+                                   REAL(val), REAL(g));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2)), names = PROTECT(Rf_allocVector(STRSXP, 2));
+    SET_VECTOR_ELT(out, 0, val); SET_VECTOR_ELT(out, 1, g);
+    SET_STRING_ELT(names, 0, Rf_mkChar("value")); SET_STRING_ELT(names, 1, Rf_mkChar("grad"));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
+/* ... at G points (one per chain): an unnamed list of value (3 x G), grad (3 x G) and info (G), as gpmi_R_logml_grad_grid */
+SEXP gpmi_R_joint_logml_grad_grid(SEXP t, SEXP yy, SEXP alpha, SEXP l, SEXP sigma, SEXP jitter)
+{
+    int n = Rf_length(t), G = Rf_length(l);
+    need(is_real(t) && is_real(yy) && is_real(alpha) && is_real(l) && is_real(sigma), "t, yy, alpha, l, sigma must be double");
+    need(Rf_length(yy) == 2 * n, "yy must stack c(y, y'): length 2 * length(t)");
+    need(Rf_length(alpha) == G && Rf_length(sigma) == G, "alpha, l and sigma must have one entry per grid point (recycle in R)");
+    SEXP val = PROTECT(Rf_allocMatrix(REALSXP, 3, G)), g = PROTECT(Rf_allocMatrix(REALSXP, 3, G)), info = PROTECT(Rf_allocVector(INTSXP, G));
+    int rc = gpmi_joint_logml_grad_grid(ctx(), REAL(t), n, REAL(yy), REAL(alpha), REAL(l), REAL(sigma), G, Rf_asReal(jitter),
+                                        REAL(val), REAL(g), INTEGER(info));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, val); SET_VECTOR_ELT(out, 1, g); SET_VECTOR_ELT(out, 2, info);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
 /* G x 3 matrix + info for a hyper-parameter grid (non-PD points NaN, grid continues) */
 SEXP gpmi_R_logml_grid(SEXP X, SEXP y, SEXP alpha, SEXP rho, SEXP sigma, SEXP jitter)
 {
