@@ -1,12 +1,13 @@
 """Build libgpmi.so (HIP, gfx950) in-tree with hipcc.  No torch involvement: the
 library is a plain C-ABI shared object (include/gpmi.h)."""
+import glob
 import os
 import shutil
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["se_kernels.hip", "chol_kernels.hip", "interp_kernels.hip", "latent_kernels.hip", "predict_kernels.hip", "gpmi_api.hip"]
+SOURCES = ["se_kernels.hip", "chol_kernels.hip", "small_kernels.hip", "interp_kernels.hip", "latent_kernels.hip", "predict_kernels.hip", "gpmi_api.hip"]
 LIB = os.path.join(CSRC, "libgpmi.so")
 PROBES_LIB = os.path.join(CSRC, "libgpmi_probes.so")  # -DGPMI_PROBES: tools/ only, never loaded by the product
 
@@ -22,14 +23,8 @@ def needs_build(lib=LIB):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [
-        os.path.join(CSRC, "gpmi_internal.h"),
-        os.path.join(CSRC, "factor16.h"),
-        os.path.join(CSRC, "se_device.h"),
-        os.path.join(CSRC, "interp_device.h"),
-        os.path.join(CSRC, "latent_device.h"),
-        os.path.join(HERE, "..", "include", "gpmi.h"),
-    ]
+    # every header and source under csrc/ and the public header: a hand-kept list needed an edit with each new header
+    deps = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")) + [os.path.join(HERE, "..", "include", "gpmi.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -37,8 +32,10 @@ def build(force=False, verbose=False, probes=False):
     lib = PROBES_LIB if probes else LIB
     if not force and not needs_build(lib):
         return lib
-    # the translation units are compiled side by side (chol_kernels.hip alone takes minutes: every one-workgroup kernel
-    # inlines the whole diagonal-block body and the tile functions), then linked
+    # the translation units are compiled side by side, then linked.  small_kernels.hip sets the wall time: every one-workgroup
+    # kernel inlines the whole diagonal-block body and the tile functions (device code alone: about 8 min 45 s on the
+    # development machine; chol_kernels.hip, the blocked kernels, under 1 min).  A forced build took 9 min 03 s when both
+    # halves were one file and 8 min 38 s since (same machine, once each, other compilations running both times)
     flags = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++20", "-fPIC", "-fvisibility=hidden"] + (
         ["-DGPMI_PROBES"] if probes else [])
     objdir = os.path.join(CSRC, "build", "probes" if probes else "product")

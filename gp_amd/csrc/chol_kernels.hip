@@ -20,44 +20,15 @@
 //   k_gemm_nt     C -= A B^T / C = A B^T, 128x128 tiles, LDS-staged with
 //                 global_load_lds, 2-stage pipeline; SYRK mode walks only the
 //                 lower-triangular tiles of the trailing matrix
+// The device functions behind these kernels (potrf_diag4_body, trsm_panel_body, gemm_tile, gemm_quad64) live in
+// chol_device.h: the one-workgroup kernels of small_kernels.hip inline them too.  This file keeps the blocked kernels,
+// the triangular helpers (k_trsv_wave, k_trmv_*, k_logml_partial / finalize, k_get_row, k_pack_factors, ...), the
+// probe-only A/B kernels, gpmi_tuning_defaults and the panel scheduler.
 // Reference: Stan cholesky_decompose (models/fit_hyperparameters.stan:25),
 // multi_normal_cholesky (:31), L*z (models/exact_gp.stan:25).
-#include "gpmi_internal.h"
-#include <math.h>
-#include <type_traits>
+#include "chol_device.h"
 
 namespace {
-
-__device__ __forceinline__ d4 mfma(double a, double b, d4 c)
-{
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// C-tile accesses of the update kernels: dbg bit 3 (probe) makes them non-temporal so that the
-// streamed C tiles do not displace the panel operands, which every tile re-reads, from L2
-__device__ __forceinline__ double ld_c(const double *p, bool nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void st_c(double *p, double v, bool nt)
-{
-    if (nt) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
-__device__ __forceinline__ double readlane64(double v, int l)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, l);
-    hi = __builtin_amdgcn_readlane(hi, l);
-    return __hiloint2double(hi, lo);
-}
-
-// Fpack tile slots (256 doubles each): negated L block (jb,kb), kb<jb, then Linv16 of block jb
-__device__ __host__ constexpr int fp_l(int jb, int kb) { return jb * (jb - 1) / 2 + kb; }
-__device__ __host__ constexpr int fp_inv(int jb) { return 28 + jb; }
-
-
-#include "factor16.h"
-#include "se_device.h"
-#include "latent_device.h"
 
 #ifdef GPMI_PROBES  // the 5-wave / 3-barrier diagonal-block kernel of round 1 (diag_waves = 5): A/B material only
 // ---------------------------------------------------------------------------
@@ -179,345 +150,12 @@ __global__ __launch_bounds__(320) void k_potrf_diag(double *__restrict__ A, size
 
 #endif  // GPMI_PROBES
 
-// ---------------------------------------------------------------------------
-// Diagonal block, 4-wave variant: the same algorithm with THREE tile waves (block-rows
-// {7,2,0}, {6,3,1}, {5,4}: 12 / 13 / 11 register tiles) and the factor wave.  One wave per
-// SIMD and ~50 KB of LDS: the workgroup fits into the half of a CU that a retiring
-// trailing-update workgroup leaves behind, so next to a running SYRK it starts within
-// microseconds instead of waiting for a whole CU to drain by chance (5 waves need two wave
-// slots with ~200 registers each on one SIMD, which a resident SYRK wave rules out).
-// ---------------------------------------------------------------------------
-#ifdef GPMI_PROBES
-// where a diagonal-block body spends its cycles (accumulated over all bodies since the last read): [0] block loads
-// (drained), [1] the 8-step loop, [2] stores, [3] factor wave inside factor16, [4] factor wave waiting at B1 for the
-// next diagonal tile, [5] bodies
-__device__ unsigned long long g_body[8];
-#define GPMI_BSTAMP(v) const unsigned long long v = __builtin_amdgcn_s_memtime();
-#define GPMI_BADD(i, d) atomicAdd(&g_body[i], (unsigned long long)(d));
-#else
-#define GPMI_BSTAMP(v)
-#define GPMI_BADD(i, d)
-#endif
-template <bool COH>
-__device__ __forceinline__ double ld_blk(const double *p)
-{
-    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-constexpr int DIAG4_LDS = 2 * 8 * 256 + 8 * 256 + 2 * 16 * 17 + 2;  // doubles of workgroup memory the body needs (52 KB; the last two: the tile waves' arrival counter)
-// COH: the block was written by other workgroups of the same launch with agent-scope stores; read it
-// with agent-scope loads (they do not trust this XCD's L2) instead of invalidating caches with a fence
-// FULL: the block has all 128 rows and columns (every panel but a ragged last one): the tiles below the
-// diagonal are loaded and stored unconditionally -- the guarded form costs a compare, an exec-mask
-// save / restore and a branch per ELEMENT (60 per lane), ~3 us per block
-// nblk (ragged blocks only): number of 16-column pivot blocks to run, ceil(nb_act / 16) -- a small matrix does not
-// pay for the identity padding's pivots (n = 21: 2 of 8 block columns); Fpack slots of the skipped blocks are then
-// never read by the consumers, which loop over the same count
-template <bool COH = false, bool FULL = false>
-__device__ __forceinline__ void potrf_diag4_body(double *__restrict__ sm, double *__restrict__ A, size_t lda, int nb_act,
-                                                 double *__restrict__ Fpack, int *info, int col0, int nblk = 8,
-                                                 int tid = (int)threadIdx.x)
-{
-    if (FULL) nblk = 8;
-    // ragged blocks: block-rows >= nblk are identity padding -- not loaded, solved, updated or stored (at n = 21 two of
-    // eight block-rows exist; carrying the padding through every step was half of the body's time there)
-#define GPMI_ACT(br) (FULL || (br) < nblk)
-    double (*s_pub)[8][256] = reinterpret_cast<double (*)[8][256]>(sm);
-    double (*s_inv)[256] = reinterpret_cast<double (*)[256]>(sm + 2 * 8 * 256);
-    // the diagonal tile travels to the factor wave and comes back as L16 through s_d16[kb & 1]: two
-    // buffers, so that the owner of block-row kb + 1 can hand over the NEXT diagonal tile while the
-    // owner of block-row kb still reads L16 of this step
-    double (*s_d16)[16][17] = reinterpret_cast<double (*)[16][17]>(sm + 2 * 8 * 256 + 8 * 256);
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 15, lq = lane >> 4;
-
-    // TWO workgroup barriers per block column.  The chain factor16(kb) -> solve of block-row kb + 1 ->
-    // update of its diagonal tile -> factor16(kb + 1) crosses B2 and B1 only: the update of the next
-    // diagonal tile needs nothing but its owner's own solve result (register r of X is, lane for lane,
-    // the A and the B operand of X X^T), so no barrier stands between the solve and that update (the
-    // third barrier of the earlier form cost ~2 k of the ~7.7 k cycles per step).
-    // The barriers order LDS traffic only (the waves talk through s_d16 / s_inv / s_pub): they are raw
-    // s_waitcnt lgkmcnt(0) + s_barrier, NOT __syncthreads(), whose release fence also drains vmcnt -- so the block's
-    // global loads may still be in flight at the first barriers (they are issued in the order they are needed: block
-    // column 0 of every row first) and the finished tiles are stored from inside the loop, under the factor wave's
-    // time, instead of in a ~6 k-cycle tail behind it.  Nothing in the body reads global memory another wave of the
-    // workgroup has written.
-#define GPMI_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-    if (w == 3) {
-#pragma unroll 1
-        for (int kb = 0; kb < nblk; ++kb) {
-            GPMI_BSTAMP(f0)
-            GPMI_LDS_BARRIER();  // B1: the owner's diagonal tile is in s_d16[kb & 1]; -X tiles of step kb - 1 published
-            GPMI_BSTAMP(f1)
-            const int bad = factor16(s_d16[kb & 1], s_inv[kb], lane);
-            if (bad && lane == 0) atomicCAS(info, 0, col0 + kb * 16 + bad);
-            GPMI_BSTAMP(f2)
-#ifdef GPMI_PROBES
-            if (lane == 0) {
-                GPMI_BADD(3, f2 - f1)
-                GPMI_BADD(4, f1 - f0)
-            }
-#endif
-            GPMI_LDS_BARRIER();  // B2: L16 in s_d16[kb & 1], L16^-1 in s_inv[kb]
-        }
-        return;
-    }
-    GPMI_BSTAMP(b0)
-
-    // block-rows of this wave, ra > rb > rc (rc = -1: none); array sizes cover the largest row of each class
-    const int ra = 7 - w, rb = 2 + w, rc = w < 2 ? w : -1;
-    d4 TA[8], TB[5], TC[2];
-#define GPMI_CL(jb, NJ) ((jb) < (NJ) ? (jb) : 0)  // keeps compile-time indices of never-taken branches in range
-    // per block-row: A + (16 br + lr) + lq lda -- element (i) of tile jb is then a wave-uniform multiple of lda away
-    // (the general form costs a max / min / 64-bit multiply-add per element: 4.5 k cycles of pure address arithmetic
-    // for the 60 loads of a lane)
-    const double *const pra = A + (size_t)(ra * 16 + lr) + (size_t)lq * lda;
-    const double *const prb = A + (size_t)(rb * 16 + lr) + (size_t)lq * lda;
-    const double *const prc = A + (size_t)((rc < 0 ? 0 : rc) * 16 + lr) + (size_t)lq * lda;
-#define GPMI_LOAD_TILE(T, br, jb, PR)                                                                  \
-    {                                                                                                  \
-        T[jb] = d4{0.0, 0.0, 0.0, 0.0};                                                                \
-        if (!GPMI_ACT(br)) {                                                                           \
-        } else if (FULL && (jb) < (br)) {                                                              \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i) T[jb][i] = ld_blk<COH>(PR + (size_t)((jb) * 16 + 4 * i) * lda); \
-        } else if ((jb) <= (br)) {                                                                     \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
-                const int col = (jb) * 16 + lq + 4 * i, row = (br) * 16 + lr;                          \
-                const int rr = row > col ? row : col, cc = row > col ? col : row;                      \
-                if (FULL) T[jb][i] = ld_blk<COH>(A + (size_t)rr + (size_t)cc * lda);                   \
-                else T[jb][i] = (rr < nb_act) ? ld_blk<COH>(A + (size_t)rr + (size_t)cc * lda) : (row == col ? 1.0 : 0.0); \
-            }                                                                                          \
-        }                                                                                              \
-    }
-    // block column by block column, lowest rows first: tile (0, 0) and then the tiles of block column 0 are what the
-    // first steps wait for
-#pragma unroll
-    for (int jb = 0; jb < 8; ++jb) {
-        if (jb < 2) GPMI_LOAD_TILE(TC, rc, jb, prc)
-        if (jb < 5) GPMI_LOAD_TILE(TB, rb, jb, prb)
-        GPMI_LOAD_TILE(TA, ra, jb, pra)
-    }
-
-    // step k of block-row br: the diagonal tile comes back from the factor wave as L16; a row below is solved against
-    // L16^-1 (4 chained MFMAs), keeps X as its final tile and publishes -X for the other rows' updates
-#define GPMI_SOLVE_ROW(T, NJ, br, X, k)                                                                \
-    if ((br) == (k)) {                                                                                 \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) T[GPMI_CL(k, NJ)][i] = s_d16[(k) & 1][lr][lq + 4 * i]; \
-    } else if ((br) > (k) && GPMI_ACT(br)) {                                                           \
-        X = d4{0.0, 0.0, 0.0, 0.0};                                                                    \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                               \
-            X = mfma(s_inv[k][kg * 64 + lane], T[GPMI_CL(k, NJ)][kg], X);                              \
-        T[GPMI_CL(k, NJ)] = X;                                                                         \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg) s_pub[(k) & 1][br][kg * 64 + lane] = -X[kg];  \
-    }
-
-    // The only tile the next pivot block waits for is the diagonal tile of block-row kb + 1: its
-    // owner updates it first (EARLY), straight from the registers of its own solve, and hands it to
-    // the factor wave; every other update of step kb (REST) runs in the next iteration between B1
-    // and B2, i.e. under the factor wave's 4.4 k cycles.
-#define GPMI_UPDATE_EARLY(T, NJ, br, X)                                                                \
-    {                                                                                                  \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                               \
-            T[GPMI_CL(kb + 1, NJ)] = mfma(-X[kg], X[kg], T[GPMI_CL(kb + 1, NJ)]);                      \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) s_d16[(kb + 1) & 1][lr][lq + 4 * i] = T[GPMI_CL(kb + 1, NJ)][i]; \
-    }
-#define GPMI_UPDATE_REST(T, NJ, br, X)                                                                 \
-    _Pragma("unroll") for (int jb = kb; jb < (NJ); ++jb) {                                             \
-        if (jb <= (br) && !(jb == kb && (br) == kb)) {                                                 \
-            _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                           \
-                T[jb] = mfma(s_pub[(kb - 1) & 1][jb][kg * 64 + lane], X[kg], T[jb]);                   \
-        }                                                                                              \
-    }
-    // Block column k of block-row br is final once step k has solved it: L tile (from the solve's registers) and its
-    // packed negative below the diagonal; on the diagonal the factor's tile and the inverse the factor wave left in
-    // s_inv[k].  Issued one step later, behind B1, so that the stores do not sit between B2 and B1 (the critical path).
-#define GPMI_STORE_STEP(T, NJ, br, k, PR)                                                              \
-    if ((br) > (k) && !GPMI_ACT(br)) {                                                                 \
-    } else if ((br) > (k)) {                                                                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
-            if (FULL || (br) * 16 + lr < nb_act)                                                       \
-                const_cast<double *>(PR)[(size_t)((k) * 16 + 4 * i) * lda] = T[GPMI_CL(k, NJ)][i];     \
-        }                                                                                              \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                               \
-            Fpack[(size_t)fp_l(br, k) * 256 + kg * 64 + lane] = -T[GPMI_CL(k, NJ)][kg];                \
-    } else if ((br) == (k)) {                                                                          \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
-            const int col = (k) * 16 + lq + 4 * i, row = (br) * 16 + lr;                               \
-            if (col <= row && (FULL || row < nb_act)) A[(size_t)row + (size_t)col * lda] = T[GPMI_CL(k, NJ)][i]; \
-        }                                                                                              \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                               \
-            Fpack[(size_t)fp_inv(k) * 256 + kg * 64 + lane] = s_inv[k][kg * 64 + lane];                \
-    }
-
-    GPMI_BSTAMP(b1)
-    // Between B2 (factor16 of step kb done) and B1 (the next diagonal tile handed over) -- the critical path -- ONLY the
-    // owner of block-row kb + 1 works: it solves that row (4 MFMAs), updates the next diagonal tile from its own
-    // registers (4 MFMAs) and hands it to the factor wave.  Every other solve of step kb, the publication of the -X
-    // tiles, the stores and the REST updates run behind B1, under factor16(kb + 1); the REST updates read the other
-    // rows' -X tiles, so the three tile waves meet once more in between, on an arrival counter in LDS (the factor
-    // wave, busy on the chain, takes no part).  Before: all solves of a step stood between B2 and B1 (~2.0 k cycles
-    // per step against ~0.9 k now).
-    // (explicitly an LDS pointer: through a generic one the accesses become FLAT operations, whose completion the
-    // compiler can only await with vmcnt(0) -- which would drain the block loads still in flight)
-    typedef __attribute__((address_space(3))) int lds_int;
-    lds_int *const s_cnt = (lds_int *)(sm + DIAG4_LDS - 2);
-    if (tid == 0) *s_cnt = 0;   // ordered before every arrival by the first B1
-    auto tile_waves_meet = [&](int target) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's -X tiles are in LDS
-        if (lane == 0) __hip_atomic_fetch_add(s_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        while (__hip_atomic_load(s_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-    };
-    d4 XA[8], XB[8], XC[8];
-    if (rc == 0) {  // block-row 0 hands tile (0, 0) to the factor wave in matrix order
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_d16[0][lr][lq + 4 * i] = TC[0][i];
-    }
-    int last = -1;  // last step whose non-critical solves and stores are still due
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb) {
-        if (!FULL && kb >= nblk) break;  // workgroup-uniform
-        GPMI_LDS_BARRIER();  // B1: diagonal tile kb is in s_d16[kb & 1] (factor16(kb) starts)
-        if (kb > 0) {
-            // the rest of step kb - 1: its other rows' solves (row kb was solved before B1) ...
-            if (ra != kb) { GPMI_SOLVE_ROW(TA, 8, ra, XA[kb - 1], kb - 1) }
-            if (rb != kb) { GPMI_SOLVE_ROW(TB, 5, rb, XB[kb - 1], kb - 1) }
-            if (rc != kb) { GPMI_SOLVE_ROW(TC, 2, rc, XC[kb - 1], kb - 1) }
-            tile_waves_meet(3 * kb);   // ... every row's -X tile of step kb - 1 is published ...
-            GPMI_STORE_STEP(TA, 8, ra, kb - 1, pra)
-            GPMI_STORE_STEP(TB, 5, rb, kb - 1, prb)
-            GPMI_STORE_STEP(TC, 2, rc, kb - 1, prc)
-            // ... and REST: tiles jb >= kb of the rows below, except tile (kb, kb) (updated EARLY)
-            if (ra >= kb && GPMI_ACT(ra)) { GPMI_UPDATE_REST(TA, 8, ra, XA[kb - 1]) }
-            if (rb >= kb && GPMI_ACT(rb)) { GPMI_UPDATE_REST(TB, 5, rb, XB[kb - 1]) }
-            if (rc >= kb && GPMI_ACT(rc)) { GPMI_UPDATE_REST(TC, 2, rc, XC[kb - 1]) }
-        }
-        GPMI_LDS_BARRIER();  // B2: factor16(kb) done: L16 in s_d16[kb & 1], its inverse in s_inv[kb]
-        if (kb < 7 && GPMI_ACT(kb + 1)) {     // the critical row kb + 1: solve, EARLY update of the next diagonal tile, hand-over
-            if (ra == kb + 1) { GPMI_SOLVE_ROW(TA, 8, ra, XA[kb], kb) GPMI_UPDATE_EARLY(TA, 8, ra, XA[kb]) }
-            else if (rb == kb + 1) { GPMI_SOLVE_ROW(TB, 5, rb, XB[kb], kb) GPMI_UPDATE_EARLY(TB, 5, rb, XB[kb]) }
-            else if (rc == kb + 1) { GPMI_SOLVE_ROW(TC, 2, rc, XC[kb], kb) GPMI_UPDATE_EARLY(TC, 2, rc, XC[kb]) }
-        }
-        last = kb;
-    }
-#undef GPMI_UPDATE_EARLY
-#undef GPMI_UPDATE_REST
-    GPMI_BSTAMP(b2)
-    // the last step: its diagonal tile back from the factor wave (rows below it are padding: nothing to solve), its stores
-    // (compile-time step index: one copy per possible last step of a ragged block)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (k == last) {
-            if (ra == k) { GPMI_SOLVE_ROW(TA, 8, ra, XA[k], k) }
-            if (rb == k) { GPMI_SOLVE_ROW(TB, 5, rb, XB[k], k) }
-            if (rc == k) { GPMI_SOLVE_ROW(TC, 2, rc, XC[k], k) }
-            GPMI_STORE_STEP(TA, 8, ra, k, pra)
-            GPMI_STORE_STEP(TB, 5, rb, k, prb)
-            GPMI_STORE_STEP(TC, 2, rc, k, prc)
-        }
-    }
-#ifdef GPMI_PROBES
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (w == 0 && lane == 0) {
-        GPMI_BSTAMP(b3)
-        GPMI_BADD(0, b1 - b0)
-        GPMI_BADD(1, b2 - b1)
-        GPMI_BADD(2, b3 - b2)
-        GPMI_BADD(5, 1)
-    }
-#endif
-#undef GPMI_CL
-#undef GPMI_ACT
-#undef GPMI_LOAD_TILE
-#undef GPMI_SOLVE_ROW
-#undef GPMI_STORE_STEP
-#undef GPMI_LDS_BARRIER
-}
-
 __global__ __launch_bounds__(256, 2) void k_potrf_diag4(double *__restrict__ A, size_t lda, int nb_act,
                                                      double *__restrict__ Fpack, int *info, int col0)
 {
     __shared__ double sm[DIAG4_LDS];
     if (nb_act == GPMI_NB) potrf_diag4_body<false, true>(sm, A, lda, nb_act, Fpack, info, col0);
     else potrf_diag4_body<false, false>(sm, A, lda, nb_act, Fpack, info, col0);
-}
-
-// ---------------------------------------------------------------------------
-// Panel solve: rows [row0, M) of the nb_act columns starting at Acol.
-// X L11^T = A21 by block forward substitution over the 8 block columns; each
-// wave carries its 16 rows through all steps in registers.
-// ---------------------------------------------------------------------------
-// FULL: all 64 rows of the workgroup and all 128 columns exist -- unconditional, batched loads and
-// stores from one running column pointer (the guarded form predicates and branches per element)
-// kb0 (wave-uniform): the strip's columns left of block kb0 are zero (rows of the identity / of an upper-triangular
-// operand): those block steps produce zeros and are skipped
-template <bool FULL>
-__device__ __forceinline__ void trsm_panel_body(const double *__restrict__ s_F, double *__restrict__ Acol, size_t lda,
-                                                int r, bool rok, int nb_act, int tid = (int)threadIdx.x, int kb0 = 0)
-{
-    const int lane = tid & 63;
-    const int lq = lane >> 4;
-    const int nblk = FULL ? 8 : (nb_act + 15) >> 4;
-    d4 T[8];
-    if constexpr (FULL) {
-        const double *p = Acol + (size_t)r + (size_t)lq * lda;
-#pragma unroll
-        for (int jb = 0; jb < 8; ++jb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                T[jb][i] = *p;
-                p += 4 * lda;
-            }
-    } else {
-#pragma unroll
-        for (int jb = 0; jb < 8; ++jb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int col = jb * 16 + lq + 4 * i;
-                T[jb][i] = (rok && col < nb_act) ? Acol[(size_t)r + (size_t)col * lda] : 0.0;
-            }
-        }
-    }
-    __syncthreads();  // packed factors are in s_F
-
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb) {
-        if (kb >= kb0 && kb < nblk) {
-            d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kg = 0; kg < 4; ++kg) acc = mfma(s_F[fp_inv(kb) * 256 + kg * 64 + lane], T[kb][kg], acc);
-            T[kb] = acc;
-#pragma unroll
-            for (int jb = kb + 1; jb < 8; ++jb) {
-                if (jb < nblk) {
-#pragma unroll
-                    for (int kg = 0; kg < 4; ++kg)
-                        T[jb] = mfma(s_F[fp_l(jb, kb) * 256 + kg * 64 + lane], T[kb][kg], T[jb]);
-                }
-            }
-        }
-    }
-
-    if constexpr (FULL) {
-        double *p = Acol + (size_t)r + (size_t)lq * lda;
-#pragma unroll
-        for (int jb = 0; jb < 8; ++jb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                *p = T[jb][i];
-                p += 4 * lda;
-            }
-    } else {
-#pragma unroll
-        for (int jb = 0; jb < 8; ++jb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int col = jb * 16 + lq + 4 * i;
-                if (rok && col < nb_act) Acol[(size_t)r + (size_t)col * lda] = T[jb][i];
-            }
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void k_trsm_panel(double *__restrict__ Acol, size_t lda, int row0,
@@ -539,16 +177,6 @@ __global__ __launch_bounds__(256) void k_trsm_panel(double *__restrict__ Acol, s
     else
         trsm_panel_body<false>(s_F, Acol, lda, r, r < M, nb_act);
 }
-
-// ---------------------------------------------------------------------------
-// GEMM NT on 128x128 tiles.  A: M x K, B: N x K (both with the tile index
-// contiguous), C: M x N.  MODE 0: C -= A B^T; 1: same, A == B panel, lower
-// tiles only (SYRK); 2: C = A B^T.
-// LDS image per stage and operand: [16 k][144] doubles -- each k-row is one
-// 1-KiB global_load_lds write; the 128-B row pad puts k and k+1 on opposite
-// halves of the 64 banks so the ds_read_b64 fragment reads are conflict-free.
-// ---------------------------------------------------------------------------
-constexpr int GT = 128, GK = 16, GP = 144;
 
 // SYRK tile order.  Workgroups are dealt round-robin to the 8 XCDs (observed dispatch
 // behaviour; performance only), so block b runs on XCD-group b % 8 as that group's (b / 8)-th
@@ -636,350 +264,6 @@ __device__ __forceinline__ void syrk_tile_bands(int c, int T, int TN, int &ti, i
         c -= cnt;
     }
 }
-
-// One 128 x 128 output tile (ti, tj); smem is the workgroup's staging buffer (free on entry:
-// every wave has finished reading it).
-// MODE 3: the product A B^T is not stored, its elements are consumed where they are (the accumulators never leave their
-// registers; C is unused): epi.row(tm, m, ok) announces the lane's four rows, then per column epi.col(n, ok) and
-// epi.elem(v, tm) for its four elements -- so that the consumer loads what depends on a row or a column once.
-struct NoEpi {
-    __device__ void row(int, int, bool) const {}
-    __device__ void col(int, bool) const {}
-    __device__ void elem(double, int) const {}
-};
-template <class R, class C, class E>
-struct Epi3 {
-    R row;
-    C col;
-    E elem;
-};
-template <class R, class C, class E>
-__device__ __forceinline__ Epi3<R, C, E> make_epi3(R r, C c, E e)
-{
-    return Epi3<R, C, E>{r, c, e};
-}
-template <int MODE, bool WHOLE, class EPI = NoEpi>
-__device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const double *__restrict__ A, size_t lda,
-                                            const double *__restrict__ B, size_t ldb, double *__restrict__ C,
-                                            size_t ldc, int M, int N, int K, int ti, int tj, int dbg, int tid, EPI &&epi = EPI{})
-{
-    const int m0 = ti * GT, n0 = tj * GT;
-    if (MODE == 1 && n0 >= N) return;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 15, lq = lane >> 4;
-    const int wm = w & 1, wn = w >> 1;
-
-    // staging: waves 0,1 stream the A tile (m index), waves 2,3 the B tile (n index); 8 k-rows each
-    const int op = w >> 1;
-    const double *gsrc = (op ? B + n0 : A + m0) + 2 * lane;
-    const size_t gld = op ? ldb : lda;
-    const int krow0 = (w & 1) * 8;
-
-    d4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-
-    const int nk = (K + GK - 1) / GK;
-    auto issue = [&](int stage, int k0) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int kr = krow0 + q;
-            int kc = k0 + kr;
-            kc = kc < K ? kc : K - 1;  // clamp: never read a column past the operand
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(gsrc + (size_t)kc * gld),
-                (__attribute__((address_space(3))) void *)&smem[stage][op][kr][0], 16, 0, 0);
-        }
-    };
-    // Fragments of sub-step kk+1 are requested before the 16 MFMAs of sub-step kk are issued
-    // (two register sets), so the LDS latency sits under ~1k cycles of matrix work.  MASK
-    // (zeroing of columns past K) is compiled only into the last, possibly partial, k-step:
-    // a select on a just-loaded fragment forces the wait in front of the MFMAs.
-    auto ldfrag = [&](auto mk, int st, int kk, int klim, double (&af)[4], double (&bf)[4]) {
-        constexpr bool MASK = decltype(mk)::value != 0;
-        const int kr = kk * 4 + lq;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            af[t] = smem[st][1][kr][wn * 64 + t * 16 + lr];
-            bf[t] = smem[st][0][kr][wm * 64 + t * 16 + lr];
-        }
-        if constexpr (MASK) {
-            const bool kv = kr < klim;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                af[t] = kv ? af[t] : 0.0;
-                bf[t] = kv ? bf[t] : 0.0;
-            }
-        }
-    };
-    auto mm16 = [&](const double (&af)[4], const double (&bf)[4]) {
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(af[tn], bf[tm], acc[tn][tm]);
-    };
-    // mid(): issued between the first fragment reads and the first MFMAs (the DMA of the next stage:
-    // its instructions then run under the LDS latency instead of in front of it)
-    auto compute = [&](auto mk, int st, int klim, auto &&mid) {
-        double a0[4], b0[4], a1[4], b1[4];
-        ldfrag(mk, st, 0, klim, a0, b0);
-        ldfrag(mk, st, 1, klim, a1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-        mid();
-        __builtin_amdgcn_sched_barrier(0);
-        mm16(a0, b0);
-        __builtin_amdgcn_sched_barrier(0);
-        ldfrag(mk, st, 2, klim, a0, b0);
-        __builtin_amdgcn_sched_barrier(0);
-        mm16(a1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-        ldfrag(mk, st, 3, klim, a1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-        mm16(a0, b0);
-        mm16(a1, b1);
-    };
-
-    if constexpr (WHOLE) {
-        const double *g0 = gsrc + (size_t)krow0 * gld;
-#pragma unroll
-        for (int q = 0; q < 8; ++q)  // stage 0, same lean addressing as the loop
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g0 + (size_t)q * gld),
-                                             (__attribute__((address_space(3))) void *)&smem[0][op][krow0 + q][0], 16, 0, 0);
-    } else {
-        issue(0, 0);
-    }
-    double a0[4], b0[4];  // whole-k-step form: the fragments of sub-step 0 cross the k-step boundary
-    if constexpr (WHOLE) {
-        // Whole k-steps only (every launch of a factorisation whose order is a multiple of 16): no
-        // clamp, and the eight row addresses of a stage are one running per-lane pointer plus
-        // loop-invariant uniform offsets -- one VALU add per DMA instead of the ~12 scalar
-        // instructions (min, 64-bit multiply, ...) of the general form.
-        // The k-step boundary is software-pipelined (round 3): the barrier that publishes stage t + 1 sits BEFORE the
-        // last 16 MFMAs of step t, and the DMA of step t + 2 and the first fragment reads of step t + 1 are issued
-        // between those MFMAs -- so what a k-step exposes is the barrier itself, not barrier + DMA issue + LDS latency
-        // in front of its first MFMA (4970 cycles per 4096 of MFMA issue for a workgroup alone on a CU before).
-        // Stage t & 1 is free for the DMA of step t + 2 at that barrier: every wave has its last fragments of step t
-        // in registers (lgkmcnt(0) in front of the barrier).
-        const double *gp = gsrc + (size_t)krow0 * gld;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (nk > 1 && !(dbg & 2)) {
-            gp += (size_t)GK * gld;
-            asm volatile("" : "+v"(gp));
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gp + (size_t)q * gld),
-                                                 (__attribute__((address_space(3))) void *)&smem[1][op][krow0 + q][0], 16, 0, 0);
-        }
-        ldfrag(ic<0>{}, 0, 0, GK, a0, b0);
-        // one k-step that has a successor; DMA: the step after that exists and is requested here
-        auto kstep = [&](auto dma, int st) {
-            constexpr bool DMA = decltype(dma)::value != 0;
-            double a1[4], b1[4];
-            // the first reads of a1, b1 go out BEHIND the first four MFMAs: the wait in front of those then covers a0, b0
-            // only (issued a quarter of a k-step ago), not an LDS round trip
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm) acc[0][tm] = mfma(a0[0], b0[tm], acc[0][tm]);
-            __builtin_amdgcn_sched_barrier(0);
-            ldfrag(ic<0>{}, st, 1, GK, a1, b1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int tn = 1; tn < 4; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(a0[tn], b0[tm], acc[tn][tm]);
-            __builtin_amdgcn_sched_barrier(0);
-            ldfrag(ic<0>{}, st, 2, GK, a0, b0);
-            __builtin_amdgcn_sched_barrier(0);
-            mm16(a1, b1);
-            __builtin_amdgcn_sched_barrier(0);
-            ldfrag(ic<0>{}, st, 3, GK, a1, b1);
-            __builtin_amdgcn_sched_barrier(0);
-            mm16(a0, b0);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            // keep ONE running per-lane pointer (opaque to the optimiser, which otherwise turns the
-            // eight invariant offsets into eight running scalar pointers: 16 SALU per k-step)
-            gp += (size_t)GK * gld;
-            asm volatile("" : "+v"(gp));
-#pragma unroll
-            for (int tn = 0; tn < 4; ++tn) {
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(a1[tn], b1[tm], acc[tn][tm]);
-                __builtin_amdgcn_sched_barrier(0);
-                a0[tn] = smem[st ^ 1][1][lq][wn * 64 + tn * 16 + lr];
-                b0[tn] = smem[st ^ 1][0][lq][wm * 64 + tn * 16 + lr];
-                if constexpr (DMA) if (tn < 2) {  // all eight requests behind the first eight MFMAs: they have until the next barrier
-#pragma unroll
-                    for (int q = 4 * tn; q < 4 * tn + 4; ++q)
-                        __builtin_amdgcn_global_load_lds(
-                            (const __attribute__((address_space(1))) void *)(gp + (size_t)q * gld),
-                            (__attribute__((address_space(3))) void *)&smem[st][op][krow0 + q][0], 16, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        if (dbg & 2) {
-#pragma unroll 1
-            for (int kt = 0; kt < nk - 1; ++kt) kstep(ic<0>{}, kt & 1);
-        } else {
-#pragma unroll 1
-            for (int kt = 0; kt < nk - 2; ++kt) kstep(ic<1>{}, kt & 1);
-            if (nk > 1) kstep(ic<0>{}, nk & 1);  // step nk - 2: nothing left to request
-        }
-    } else {
-#pragma unroll 1
-        for (int kt = 0; kt < nk - 1; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (!(dbg & 2)) issue((kt + 1) & 1, (kt + 1) * GK);
-            compute(ic<0>{}, kt & 1, GK, []() {});
-        }
-    }
-
-    // Last k-step peeled.  For a tile wholly inside the matrix the first half of the C tile
-    // (32 loads per lane, uniform offsets from one base) is issued under that step -- the
-    // staging loads are all retired by then -- and the second half right after the first
-    // half's stores: one memory round trip is exposed per tile instead of four.  For SYRK the
-    // diagonal tiles are computed in full (their strictly-upper outputs land in the unused
-    // upper triangle of the workspace).
-    const bool interior = (m0 + GT <= M) && (n0 + GT <= N);
-    double *const cbase = C + (size_t)(m0 + wm * 64 + lr) + (size_t)(n0 + wn * 64 + lq) * ldc;
-    double ch[2][4][4];
-    const bool cnt = (dbg & 8) != 0;
-    if constexpr (!WHOLE) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    if (MODE != 2 && MODE != 3 && interior) {
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ch[tn][tm][i] = ld_c(cbase + tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc, cnt);
-    }
-    if constexpr (WHOLE) {  // the fragments of sub-step 0 of the last stage are in registers
-        const int st = (nk - 1) & 1;
-        double a1[4], b1[4];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int tm = 0; tm < 4; ++tm) acc[0][tm] = mfma(a0[0], b0[tm], acc[0][tm]);
-        __builtin_amdgcn_sched_barrier(0);
-        ldfrag(ic<0>{}, st, 1, GK, a1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int tn = 1; tn < 4; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(a0[tn], b0[tm], acc[tn][tm]);
-        __builtin_amdgcn_sched_barrier(0);
-        ldfrag(ic<0>{}, st, 2, GK, a0, b0);
-        __builtin_amdgcn_sched_barrier(0);
-        mm16(a1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-        ldfrag(ic<0>{}, st, 3, GK, a1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-        mm16(a0, b0);
-        mm16(a1, b1);
-    } else {
-        compute(ic<1>{}, (nk - 1) & 1, K - (nk - 1) * GK, []() {});
-    }
-    if (dbg & 1) {
-        double sacc = 0.0;
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sacc += acc[tn][tm][i];
-        if (sacc == 1.2345e300) cbase[0] = sacc;
-        return;
-    }
-    if constexpr (MODE == 3) {
-#pragma unroll
-        for (int tm = 0; tm < 4; ++tm) {
-            const int m = m0 + wm * 64 + tm * 16 + lr;
-            epi.row(tm, m, m < M);
-        }
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = n0 + wn * 64 + tn * 16 + lq + 4 * i;
-                epi.col(n, n < N);
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm) epi.elem(acc[tn][tm][i], tm);
-            }
-        return;
-    }
-    if (interior) {
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    st_c(cbase + tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc,
-                         (MODE == 2) ? acc[tn][tm][i] : ch[tn][tm][i] - acc[tn][tm][i], cnt);
-        if (MODE != 2) {
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        ch[tn][tm][i] = ld_c(cbase + tm * 16 + (size_t)((tn + 2) * 16 + 4 * i) * ldc, cnt);
-        }
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    st_c(cbase + tm * 16 + (size_t)((tn + 2) * 16 + 4 * i) * ldc,
-                         (MODE == 2) ? acc[tn + 2][tm][i] : ch[tn][tm][i] - acc[tn + 2][tm][i], cnt);
-        return;
-    }
-
-    // edge tile: per tn, 16 loads from clamped (always valid) addresses, then guarded stores
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
-        double ce[4][4];
-#pragma unroll
-        for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                int n = n0 + wn * 64 + tn * 16 + lq + 4 * i, m = m0 + wm * 64 + tm * 16 + lr;
-                n = n < N ? n : N - 1;
-                m = m < M ? m : M - 1;
-                if (MODE != 2) ce[tm][i] = C[(size_t)m + (size_t)n * ldc];
-            }
-#pragma unroll
-        for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = n0 + wn * 64 + tn * 16 + lq + 4 * i, m = m0 + wm * 64 + tm * 16 + lr;
-                if (m < M && n < N && (MODE != 1 || n <= m))
-                    C[(size_t)m + (size_t)n * ldc] = (MODE == 2) ? acc[tn][tm][i] : ce[tm][i] - acc[tn][tm][i];
-            }
-    }
-}
-
-
-// Whole k-steps (every launch of a factorisation whose order is a multiple of 16) take the software-pipelined form;
-// the two forms are separate instantiations so that neither's live ranges weigh on the other's register allocation.
-template <int MODE, class EPI = NoEpi>
-__device__ __forceinline__ void gemm_tile(double (&smem)[2][2][GK][GP], const double *__restrict__ A, size_t lda,
-                                          const double *__restrict__ B, size_t ldb, double *__restrict__ C,
-                                          size_t ldc, int M, int N, int K, int ti, int tj, int dbg, int tid, EPI &&epi = EPI{})
-{
-    if (K % GK == 0 && !(dbg & 16)) gemm_tile_k<MODE, true>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, tid, epi);  // workgroup-uniform
-    else gemm_tile_k<MODE, false>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, tid, epi);
-}
-
 
 // Two workgroups share a CU and its matrix pipes.  All tiles cost the same, so workgroups that
 // start together stay in lock-step: both reach their memory-bound epilogue at the same time
@@ -1074,96 +358,6 @@ __device__ __forceinline__ void gemm_sub16(const double *__restrict__ A, size_t 
         if constexpr (COH) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *q = v;
     }
-}
-
-// 64 x 64 tile of C -= A B^T, LDS-staged: the quadrant kernel of the SYRK tail split.  Four waves
-// x (2 x 2 MFMA tiles), k-step 16, two LDS stages filled through registers (16-B global loads,
-// ds_write_b128; row pad 16 doubles: k and k + 1 on opposite bank halves as in the big tile).
-// A, B point at the quadrant's first operand rows; mv / nv valid rows from there (clamped loads,
-// dropped outputs).  K % 16 == 0.
-constexpr int QP = 80;  // padded row of the quadrant's LDS image
-__device__ __forceinline__ void gemm_quad64(double *__restrict__ sm, const double *__restrict__ A, size_t lda,
-                                            const double *__restrict__ B, size_t ldb, double *__restrict__ C,
-                                            size_t ldc, int K, int mv, int nv, int tid)
-{
-    double (*q)[2][GK][QP] = reinterpret_cast<double (*)[2][GK][QP]>(sm);  // [stage][op][k][row]
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 15, lq = lane >> 4;
-    const int mb = (w & 1) * 32, nb = (w >> 1) * 32;
-    // staging: thread handles the row pair r2 of k-rows kr and kr + 8 of both operands
-    const int r2 = tid & 31, kr = tid >> 5;
-    const bool fast = (mv >= 64) && (nv >= 64);
-    int ra0 = 2 * r2, ra1 = 2 * r2 + 1, rb0 = ra0, rb1 = ra1;
-    ra0 = ra0 < mv ? ra0 : mv - 1;
-    ra1 = ra1 < mv ? ra1 : mv - 1;
-    rb0 = rb0 < nv ? rb0 : nv - 1;
-    rb1 = rb1 < nv ? rb1 : nv - 1;
-    double2 va[2], vb[2];
-    auto gload = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const size_t ca = (size_t)(k0 + kr + 8 * j) * lda, cb = (size_t)(k0 + kr + 8 * j) * ldb;
-            if (fast) {
-                va[j] = *reinterpret_cast<const double2 *>(A + 2 * r2 + ca);
-                vb[j] = *reinterpret_cast<const double2 *>(B + 2 * r2 + cb);
-            } else {
-                va[j] = make_double2(A[ra0 + ca], A[ra1 + ca]);
-                vb[j] = make_double2(B[rb0 + cb], B[rb1 + cb]);
-            }
-        }
-    };
-    auto swrite = [&](int st) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            *reinterpret_cast<double2 *>(&q[st][0][kr + 8 * j][2 * r2]) = va[j];
-            *reinterpret_cast<double2 *>(&q[st][1][kr + 8 * j][2 * r2]) = vb[j];
-        }
-    };
-    d4 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-    const int nk = K / GK;
-    gload(0);
-    swrite(0);
-    __syncthreads();
-#pragma unroll 1
-    for (int kt = 0; kt < nk; ++kt) {
-        const int st = kt & 1;
-        if (kt + 1 < nk) gload((kt + 1) * GK);
-        if (mb < mv && nb < nv) {  // wave-uniform: a wave whose block lies outside the matrix only stages
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                double af[2], bf[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    af[t] = q[st][1][kk * 4 + lq][nb + t * 16 + lr];
-                    bf[t] = q[st][0][kk * 4 + lq][mb + t * 16 + lr];
-                }
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm)
-                        if (mb + tm * 16 < mv && nb + tn * 16 < nv) acc[tn][tm] = mfma(af[tn], bf[tm], acc[tn][tm]);
-            }
-        }
-        if (kt + 1 < nk) swrite(st ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = mb + tm * 16 + lr, n = nb + tn * 16 + lq + 4 * i;
-                if (m < mv && n < nv) {
-                    double *c = C + (size_t)m + (size_t)n * ldc;
-                    *c = *c - acc[tn][tm][i];
-                }
-            }
 }
 
 // Tail split of a SYRK launch: the R < slots tiles of the last, partial round would hold R
@@ -1730,1681 +924,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm9(const double *__restrict__ A, 
 
 #endif  // GPMI_PROBES
 
-// ---------------------------------------------------------------------------
-// Small problems: ONE workgroup does a whole evaluation.
-//
-// The reference's drivers call the path at N = 21 (R/tests.R:5-19), 79 .. 199 (pendulum_fit*.R:206-214) and
-// 256 (BASELINE c1); there the chain of launches of the blocked code (build, row, diagonal block, panel solve,
-// update, ..., two finalize kernels) is pure launch latency.  Here one workgroup of 4 waves runs the same
-// device functions back to back on a matrix that never leaves its CU's L2:
-//   build (se_cov_tile: the arithmetic of k_se_cov, bit-identical K)  ->  for every 128-column panel:
-//   potrf_diag4_body (packed factors to LDS)  ->  rows below by trsm_panel_body strips  ->  trailing tiles by
-//   gemm_tile<1> / gemm_quad64  ->  log-det and quadratic form, reduced in the order of k_logml_partial.
-// The right-hand side y rides along as row n; when it is the only row below the last panel
-// its solve is a VALU forward substitution from the packed factors in LDS (two barriers per 16 pivots) instead
-// of a 144-MFMA strip.  Phase boundaries are __syncthreads(): global memory written by one wave of a workgroup
-// is visible to the others behind the barrier (one CU, one L1).  A grid of G hyper-parameter points is G
-// workgroups of ONE launch (k_logml_small_batch), each with its own workspace slice.
-// ---------------------------------------------------------------------------
-#ifdef GPMI_PROBES  // phase stamps of the small kernels (block 0, thread 0): g_fz[0] build, [1] diagonal blocks, [2] rows below, [3] launches, [4] trailing tiles, [5] finalize
-#define GPMI_STAMP(v) const unsigned long long v = __builtin_amdgcn_s_memtime();
-#define GPMI_STAMP_ADD(i, d) if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(&g_fz[i], (unsigned long long)(d));
-#else
-#define GPMI_STAMP(v)
-#define GPMI_STAMP_ADD(i, d)
-#endif
-constexpr int FIN_SLICE = 256;  // slice of the diagonal one workgroup of k_logml_partial reduces
-struct SmallSe {            // hyper-parameters of one point, in registers
-    double a2;
-    double inv_ell[GPMI_MAXD];
-    int D;
-};
-
-// z = L11^-1 r for ONE right-hand row (W[row, 0 .. nb), stride ld) against the packed factors of a <= 128-order
-// block in LDS: per 16-pivot block, z_kb = Linv16[kb] r_kb by 16 threads, then every row below subtracts
-// L[r][kb] z_kb -- -L tiles and inverses in the fragment order potrf_diag4_body packs them in.
-__device__ __forceinline__ void small_row_solve(const double *__restrict__ s_F, double *__restrict__ s_r,
-                                                double *__restrict__ s_z, double *__restrict__ Wrow, size_t ld, int nb, int t)
-{
-    const int nblk = (nb + 15) >> 4;
-    if (t < 128) s_r[t] = (t < nb) ? Wrow[(size_t)t * ld] : 0.0;
-    __syncthreads();
-    // every LDS read of a step is issued before its first use (fully unrolled, two accumulators): a loop with a
-    // per-lane trip count made each of the 16 products wait for its own pair of reads (3 k cycles per step)
-    for (int kb = 0; kb < nblk; ++kb) {
-        if (t < 16) {
-            double f[16], r[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                f[c] = s_F[fp_inv(kb) * 256 + (c >> 2) * 64 + (c & 3) * 16 + t];  // Linv16[t][c], zero above the diagonal
-                r[c] = s_r[kb * 16 + c];
-            }
-            double z0 = 0.0, z1 = 0.0;
-#pragma unroll
-            for (int c = 0; c < 16; c += 2) {
-                z0 = fma(f[c], r[c], z0);
-                z1 = fma(f[c + 1], r[c + 1], z1);
-            }
-            s_z[kb * 16 + t] = z0 + z1;
-        }
-        __syncthreads();
-        if (t < 128 && t >= (kb + 1) * 16 && t < nblk * 16) {
-            const int jb = t >> 4, lr = t & 15;
-            double f[16], z[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                f[c] = s_F[fp_l(jb, kb) * 256 + (c >> 2) * 64 + (c & 3) * 16 + lr];  // -L[t][16 kb + c]
-                z[c] = s_z[kb * 16 + c];
-            }
-            double a0 = s_r[t], a1 = 0.0;
-#pragma unroll
-            for (int c = 0; c < 16; c += 2) {
-                a0 = fma(f[c], z[c], a0);
-                a1 = fma(f[c + 1], z[c + 1], a1);
-            }
-            s_r[t] = a0 + a1;
-        }
-        __syncthreads();
-    }
-    if (t < nb) Wrow[(size_t)t * ld] = s_z[t];
-}
-
-// Right-looking partial factorisation by ONE workgroup: the first nfac columns of the M x ncol lower trapezoid in
-// W are factored, rows below / the trailing block updated (launch_potrf_partial's contract).  one_row: the caller
-// promises M == ncol + 1 == nfac + 1 (one augmented row), which lets the last panel use small_row_solve.
-// WITH_U (value + gradient kernels): U (same leading dimension, holds the identity on entry) becomes L^-T, block column
-// by block column while that panel's packed factors are in LDS: column block k of U holds I - sum_{j < k} U[:, j] L[k, j]^T
-// in its rows [0, k + nb) when panel k has been factored; the panel's strips apply L_kk^-T, and the panel's rows below
-// (solved next) take the block out of the later column blocks in one product each.
-template <bool WITH_U = false>
-__device__ __forceinline__ void small_potrf_partial(double (&smem)[2][2][GK][GP], double *__restrict__ s_F,
-                                                    double *__restrict__ s_aux, double *__restrict__ W, size_t ld, int M,
-                                                    int ncol, int nfac, int *info, bool one_row, double *__restrict__ U = nullptr)
-{
-    const size_t ld0 = ld;
-    // thread index, re-read behind an optimisation barrier in front of every phase: everything a phase derives from it
-    // (LDS addresses, lane masks, column offsets: hundreds of values) is then computed where it is used instead of
-    // being hoisted in front of the panel loop and kept in scratch memory across all phases
-    auto fresh_tid = []() {
-        int t = (int)threadIdx.x;
-        asm volatile("" : "+v"(t));
-        return t;
-    };
-    for (int k = 0; k < nfac; k += GPMI_NB) {
-        const int nb = (nfac - k < GPMI_NB) ? nfac - k : GPMI_NB;
-        // the leading dimension is made opaque per panel: otherwise every per-element offset of every phase (hundreds of
-        // 64-bit values) is hoisted out of this loop and stays live across all phases -- the kernel then needs 512
-        // registers, copies values through AGPRs around factor16's hand-scheduled DPP chain and breaks its hazard
-        // assumptions (the hazard recogniser cannot see into the asm statements)
-        size_t ld = ld0;
-        asm volatile("" : "+s"(ld));
-        double *Akk = W + (size_t)k + (size_t)k * ld;
-        GPMI_STAMP(ts0)
-        if (nb == GPMI_NB) potrf_diag4_body<false, true>(&smem[0][0][0][0], Akk, ld, nb, s_F, info, k, 8, fresh_tid());
-        else potrf_diag4_body<false, false>(&smem[0][0][0][0], Akk, ld, nb, s_F, info, k, (nb + 15) >> 4, fresh_tid());
-        __syncthreads();
-        GPMI_STAMP(ts1)
-        GPMI_STAMP_ADD(1, ts1 - ts0)
-        if constexpr (WITH_U) {
-            for (int rb = 0; rb < k + nb; rb += 64) {
-                const int tid = fresh_tid();
-                const int r = rb + (tid >> 6) * 16 + (tid & 15);
-                // rows inside this panel are rows of the identity: zero left of their own 16-column block
-                const int rw = rb + (tid >> 6) * 16 - k;
-                const int kb0 = __builtin_amdgcn_readfirstlane(rw > 0 ? rw >> 4 : 0);
-                if (nb == GPMI_NB && rb + 64 <= k + nb) trsm_panel_body<true>(s_F, U + (size_t)k * ld, ld, r, true, nb, tid, kb0);
-                else trsm_panel_body<false>(s_F, U + (size_t)k * ld, ld, r, r < k + nb, nb, tid, kb0);
-            }
-            __syncthreads();
-        }
-        const int r0 = k + nb;
-        if (r0 >= M) break;
-        if (one_row && M - r0 == 1) {
-            small_row_solve(s_F, s_aux, s_aux + 128, W + (size_t)r0 + (size_t)k * ld, ld, nb, fresh_tid());
-            __syncthreads();
-            GPMI_STAMP(ts2)
-            GPMI_STAMP_ADD(2, ts2 - ts1)
-            break;
-        }
-        // rows [r0, M): 16-row strips, one per wave, 64 rows per round
-        for (int rb = r0; rb < M; rb += 64) {
-            const int tid = fresh_tid();
-            const int r = rb + (tid >> 6) * 16 + (tid & 15);
-            if (nb == GPMI_NB && rb + 64 <= M) trsm_panel_body<true>(s_F, W + (size_t)k * ld, ld, r, true, nb, tid);
-            else trsm_panel_body<false>(s_F, W + (size_t)k * ld, ld, r, r < M, nb, tid);
-        }
-        __syncthreads();
-        GPMI_STAMP(ts2)
-        GPMI_STAMP_ADD(2, ts2 - ts1)
-        // trailing block: C[r0.., r0..ncol) -= X X^T, lower tiles
-        const int mt = M - r0, nt = ncol - r0;
-        if constexpr (WITH_U) {
-            if (nt > 0) {  // U[0 : r0, r0 : ncol) -= U[0 : r0, k : r0) L[r0 : ncol, k : r0)^T
-                for (int ti = 0; ti * GT < r0; ++ti)
-                    for (int tj = 0; tj * GT < nt; ++tj) {
-                        gemm_tile<0>(smem, U + (size_t)k * ld, ld, W + (size_t)r0 + (size_t)k * ld, ld, U + (size_t)r0 * ld, ld, r0, nt,
-                                     nb, ti, tj, 0, fresh_tid());
-                        __syncthreads();
-                    }
-            }
-        }
-        if (nt <= 0) continue;
-        const double *X = W + (size_t)r0 + (size_t)k * ld;
-        double *C = W + (size_t)r0 + (size_t)r0 * ld;
-        const int T = (mt + GT - 1) / GT, TN = (nt + GT - 1) / GT;
-        for (int ti = 0; ti < T; ++ti) {
-            const int vr = (mt - ti * GT < GT) ? mt - ti * GT : GT;  // valid rows of this tile row
-            if (vr == 1) {
-                // ONE row below the square part (the augmented row y^T when the order is a multiple of 128): its update is
-                // nt dot products of length nb -- thread = column, the row's panel entries from LDS, eight loads in flight --
-                // instead of a 64 x 64 MFMA quadrant per 64 columns (8 k cycles each for one useful row)
-                const int tid = fresh_tid(), row = ti * GT;
-                __syncthreads();
-                if (tid < nb) s_aux[tid] = X[(size_t)row + (size_t)tid * ld];
-                __syncthreads();
-                for (int j = tid; j < nt && j <= row; j += 256) {
-                    double a0 = 0.0, a1 = 0.0;
-                    for (int k0 = 0; k0 < nb; k0 += 8) {
-                        double u[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) u[q] = X[(size_t)j + (size_t)(k0 + q < nb ? k0 + q : nb - 1) * ld];
-#pragma unroll
-                        for (int q = 0; q < 8; q += 2) {
-                            a0 = fma(u[q], (k0 + q < nb) ? s_aux[k0 + q] : 0.0, a0);
-                            a1 = fma(u[q + 1], (k0 + q + 1 < nb) ? s_aux[k0 + q + 1] : 0.0, a1);
-                        }
-                    }
-                    C[(size_t)row + (size_t)j * ld] -= a0 + a1;
-                }
-                __syncthreads();
-                continue;
-            }
-            for (int tj = 0; tj <= ti && tj < TN; ++tj) {
-                if (vr <= 64 && nb % GK == 0) {  // thin tile row (e.g. the augmented row alone): 64-row quadrants
-                    for (int qn = 0; qn < 2; ++qn) {
-                        const int m0 = ti * GT, n0 = tj * GT + qn * 64;
-                        if (n0 >= nt || (ti == tj && qn > 0)) continue;
-                        gemm_quad64(&smem[0][0][0][0], X + m0, ld, X + n0, ld, C + (size_t)m0 + (size_t)n0 * ld, ld, nb, mt - m0,
-                                    nt - n0, fresh_tid());
-                        __syncthreads();
-                    }
-                } else {
-                    gemm_tile<1>(smem, X, ld, X, ld, C, ld, mt, nt, nb, ti, tj, 0, fresh_tid());
-                    __syncthreads();
-                }
-            }
-        }
-        GPMI_STAMP(ts3)
-        GPMI_STAMP_ADD(4, ts3 - ts2)
-    }
-}
-
-// One evaluation of models/fit_hyperparameters.stan:18-32 at n <= SMALL_N_MAX by one workgroup.
-__device__ __forceinline__ void logml_small_body(double (&smem)[2][2][GK][GP], double *__restrict__ s_F, double *__restrict__ s_aux,
-                                                 const double *__restrict__ X, int n, int ldx, const double *__restrict__ y,
-                                                 const SmallSe &se, double diag_add, double *__restrict__ W, size_t ld,
-                                                 double *__restrict__ out3, int *info_out, int *info_w, const ExpC &ec)
-{
-    const int tid = threadIdx.x;
-    GPMI_STAMP(tb0)
-    if (tid == 0) *info_w = 0;
-    // covariance, lower 64 x 64 tiles, from the scaled coordinates staged ONCE in LDS (the staging buffer of the later
-    // phases is free): one global round trip instead of one per tile and operand; y^T as row n
-    {
-        double *xs = &smem[0][0][0][0];
-#pragma unroll
-        for (int d = 0; d < GPMI_MAXD; ++d)
-            if (d < se.D)
-                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-        __syncthreads();
-        for (int row0 = 0; row0 < n; row0 += SE_TR)
-            for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
-                switch (se.D) {
-                case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                }
-            }
-    }
-    for (int j = tid; j < n; j += 256) W[(size_t)n + (size_t)j * ld] = y[j];
-    __syncthreads();
-    GPMI_STAMP(tb1)
-    GPMI_STAMP_ADD(0, tb1 - tb0)
-    GPMI_STAMP_ADD(3, 1)
-    small_potrf_partial(smem, s_F, s_aux, W, ld, n + 1, n, n, info_w, true);
-    GPMI_STAMP(tb2)
-    // sum log L_ii, z'z: the reduction tree of k_logml_partial (slices of 256, thread `slice` keeps its sum) and, for more
-    // than one slice, of k_logml_finalize over the slice sums -- the same additions in the same order as the blocked path
-    double *s_a = s_aux, *s_b = s_aux + 256;
-    const int nslice = (n + FIN_SLICE - 1) / FIN_SLICE;
-    double pa = 0.0, pb = 0.0;
-    for (int sl = 0; sl < nslice; ++sl) {
-        const int i = sl * FIN_SLICE + tid;
-        double a = 0.0, b = 0.0;
-        if (i < n) {
-            a = log(W[(size_t)i * (ld + 1)]);
-            const double z = W[(size_t)n + (size_t)i * ld];
-            b = z * z;
-        }
-        s_a[tid] = a;
-        s_b[tid] = b;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if (tid < st) {
-                s_a[tid] += s_a[tid + st];
-                s_b[tid] += s_b[tid + st];
-            }
-            __syncthreads();
-        }
-        if (nslice > 1) {
-            if (tid == sl) {
-                pa = s_a[0];
-                pb = s_b[0];
-            }
-            __syncthreads();
-        }
-    }
-    if (nslice > 1) {
-        s_a[tid] = pa;
-        s_b[tid] = pb;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if (tid < st) {
-                s_a[tid] += s_a[tid + st];
-                s_b[tid] += s_b[tid + st];
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) {
-        const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (info_out) *info_out = info;
-        if (info) {
-            out3[0] = out3[1] = out3[2] = __builtin_nan("");
-        } else {
-            out3[1] = s_a[0];
-            out3[2] = s_b[0];
-            out3[0] = -0.5 * s_b[0] - s_a[0] - 0.5 * (double)n * 1.8378770664093454835606594728112;  // log(2 pi)
-        }
-    }
-    GPMI_STAMP(tb3)
-    GPMI_STAMP_ADD(5, tb3 - tb2)
-}
-
-// Value AND gradient sums of models/fit_hyperparameters.stan:18-32 by ONE workgroup (n <= 256, D <= GPMI_MAXD): what one
-// leapfrog step of NUTS asks for at the sizes the reference's fits run (R/tests.R:5 N = 21, pendulum_fit.R 79 .. 199), where
-// the launch chain of gpmi_logml_grad (factorisation, identity, L^-T, K^-1, contraction: ~25 launches + 4 copies) costs 150 us.
-// d logml / d theta = 1/2 tr((a a' - K^-1) dK/dtheta): U = L^-T rides along in the factorisation (small_potrf_partial<true>),
-// a = U z, K^-1 = U U^T by gemm_tile<2> over the lower tiles (only the columns >= the tile row's first: U is upper
-// triangular), and the contraction re-evaluates the kernel from the scaled coordinates in LDS, thread = row.
-// res: [0..2] logml, sum log L_ii, z'z; [3 + s] the contraction sums in the layout of k_grad_partial (GRAD_NS = 10 slots:
-// [0] sum c, [1 + d] sum c (x_id - x_jd)^2, [9] sum_i g_ii) -- the host turns them into the gradient as for the chain.
-constexpr int SMALL_GRAD_NS = 2 + GPMI_MAXD, SMALL_GRAD_RES = 3 + SMALL_GRAD_NS;
-__device__ __forceinline__ void logml_grad_small_body(double (&smem)[2][2][GK][GP], double *__restrict__ s_F, double *__restrict__ s_aux,
-                                                      const double *__restrict__ X, int n, int ldx, const double *__restrict__ y,
-                                                      const SmallSe &se, double diag_add, double *__restrict__ W, size_t ld,
-                                                      double *__restrict__ U, double *__restrict__ res, int *info_out, int *info_w,
-                                                      const ExpC &ec)
-{
-    const int tid = threadIdx.x;
-    GPMI_STAMP(tg0)
-    if (tid == 0) *info_w = 0;
-    double *xs = &smem[0][0][0][0];
-    auto stage_x = [&]() {
-#pragma unroll
-        for (int d = 0; d < GPMI_MAXD; ++d)
-            if (d < se.D)
-                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-        __syncthreads();
-    };
-    stage_x();
-    for (int row0 = 0; row0 < n; row0 += SE_TR)
-        for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
-            switch (se.D) {
-            case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-            case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-            case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-            default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-            }
-        }
-    for (int j = tid; j < n; j += 256) W[(size_t)n + (size_t)j * ld] = y[j];
-    {   // U = I: 16-byte stores (row pair of a thread; ld is even and the slice 16-byte aligned), then the diagonal
-        const int rp = 2 * (tid & 127), cp = tid >> 7;
-        if (rp < n)
-            for (int j = cp; j < n; j += 2) *reinterpret_cast<double2 *>(U + (size_t)rp + (size_t)j * ld) = make_double2(0.0, 0.0);
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) U[(size_t)i * (ld + 1)] = 1.0;
-    }
-    __syncthreads();
-    GPMI_STAMP(tg1)
-    GPMI_STAMP_ADD(0, tg1 - tg0)
-    GPMI_STAMP_ADD(3, 1)
-    small_potrf_partial<true>(smem, s_F, s_aux, W, ld, n + 1, n, n, info_w, true, U);
-    __syncthreads();
-    GPMI_STAMP(tg2)
-    // value: one slice (n <= 256), the tree of k_logml_partial
-    double *s_a = s_aux, *s_b = s_aux + 256, *s_z = s_aux + 512, *s_av = s_aux + 768;
-    {
-        double a = 0.0, b = 0.0, z = 0.0;
-        if (tid < n) {
-            a = log(W[(size_t)tid * (ld + 1)]);
-            z = W[(size_t)n + (size_t)tid * ld];
-            b = z * z;
-        }
-        s_a[tid] = a;
-        s_b[tid] = b;
-        s_z[tid] = z;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if (tid < st) {
-                s_a[tid] += s_a[tid + st];
-                s_b[tid] += s_b[tid + st];
-            }
-            __syncthreads();
-        }
-    }
-    const double sum_log = s_a[0], zz = s_b[0];
-    // a = U z = K^-1 y (U upper triangular: the columns left of a wave's first row are zero); sixteen loads in flight per
-    // round trip -- a loop with one load per iteration is a chain of n memory latencies
-    {
-        double acc0 = 0.0, acc1 = 0.0;
-        const int ir = tid < n ? tid : n - 1;
-        for (int j0 = tid & ~63; j0 < n; j0 += 16) {
-            double u[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int j = j0 + q < n ? j0 + q : n - 1;
-                u[q] = U[(size_t)ir + (size_t)j * ld];
-            }
-#pragma unroll
-            for (int q = 0; q < 16; q += 2) {
-                acc0 = fma(u[q], (j0 + q < n) ? s_z[j0 + q] : 0.0, acc0);
-                acc1 = fma(u[q + 1], (j0 + q + 1 < n) ? s_z[j0 + q + 1] : 0.0, acc1);
-            }
-        }
-        s_av[tid] = acc0 + acc1;
-    }
-    // scaled coordinates for the contraction: in the packed-factor buffer (free now; the staging buffer is the product's)
-    double *xg = s_F;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d)
-        if (d < se.D)
-            for (int i = tid; i < n; i += 256) xg[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-    __syncthreads();
-    GPMI_STAMP(tg3)
-    GPMI_STAMP_ADD(5, tg3 - tg2)
-    // K^-1 = U U^T tile by tile (lower tiles; only the columns >= the tile row's first), contracted where it is produced:
-    // every element (m, n <= m) of a tile goes from its accumulator register into the sums -- K^-1 is never stored
-    double acc[SMALL_GRAD_NS];
-#pragma unroll
-    for (int q = 0; q < SMALL_GRAD_NS; ++q) acc[q] = 0.0;
-    const double a2 = se.a2;
-    auto kinv_tiles = [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;   // compile-time dimension count (0: se.D at run time, <= GPMI_MAXD)
-        const int Dn = DT ? DT : se.D;
-        constexpr int DH = DT ? DT : 1;        // coordinates kept in registers per row / column (run-time D: re-read from LDS)
-        double xm[4][DH], am[4], xn[DH], an = 0.0;
-        int mm[4], ncur = 0;
-        bool okn = false;
-        auto contract = make_epi3(
-            [&](int tm, int m, bool ok) {
-                mm[tm] = ok ? m : -1;           // a row outside the matrix lies above every column: weight 0
-                const int mc = ok ? m : 0;
-                am[tm] = s_av[mc];
-                if constexpr (DT != 0) {
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) xm[tm][d] = xg[mc + d * n];
-                }
-            },
-            [&](int nn, bool ok) {
-                ncur = ok ? nn : 0;
-                okn = ok;
-                an = s_av[ncur];
-                if constexpr (DT != 0) {
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) xn[d] = xg[ncur + d * n];
-                }
-            },
-            [&](double kinv, int tm) {
-                double e = 0.0, r2[GPMI_MAXD];
-                const int mc = mm[tm] < 0 ? 0 : mm[tm];
-#pragma unroll
-                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) {
-                    double r;
-                    if constexpr (DT != 0) r = xm[tm][d] - xn[d];
-                    else r = d < Dn ? xg[mc + d * n] - xg[ncur + d * n] : 0.0;
-                    r2[d] = r * r;
-                    e += r2[d];
-                }
-                const double kse = a2 * exp_nonpos(-0.5 * e, ec);
-                const double g = 0.5 * (am[tm] * an - kinv);
-                const bool lower = okn && ncur <= mm[tm];
-                const double c = lower ? ((ncur == mm[tm]) ? 1.0 : 2.0) * g * kse : 0.0;
-                acc[0] += c;
-#pragma unroll
-                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) acc[1 + d] += c * r2[d];
-                acc[1 + GPMI_MAXD] += (lower && ncur == mm[tm]) ? g : 0.0;
-            });
-        for (int ti = 0; ti * GT < n; ++ti)
-            for (int tj = 0; tj <= ti; ++tj) {
-                const int k0 = ti * GT;
-                gemm_tile<3>(smem, U + (size_t)k0 * ld, ld, U + (size_t)k0 * ld, ld, W, ld, n, n, n - k0, ti, tj, 0, (int)threadIdx.x,
-                             contract);
-                __syncthreads();
-            }
-    };
-    switch (se.D) {
-    case 1: kinv_tiles(ic<1>{}); break;
-    case 2: kinv_tiles(ic<2>{}); break;
-    case 3: kinv_tiles(ic<3>{}); break;
-    default: kinv_tiles(ic<0>{}); break;
-    }
-    GPMI_STAMP(tg4)
-    GPMI_STAMP_ADD(6, tg4 - tg3)
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d)   // the sums are over UNSCALED squared differences (layout of k_grad_partial)
-        acc[1 + d] = (d < se.D) ? acc[1 + d] / (se.inv_ell[d] * se.inv_ell[d]) : 0.0;
-    __syncthreads();
-    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // fixed-shape reduction (deterministic): butterfly inside every wave, the four wave sums added in wave order
-#pragma unroll
-    for (int q = 0; q < SMALL_GRAD_NS; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((tid & 63) == 0) s_a[(tid >> 6) * SMALL_GRAD_NS + q] = v;
-    }
-    __syncthreads();
-    if (tid < SMALL_GRAD_NS) {
-        const double v = ((s_a[tid] + s_a[SMALL_GRAD_NS + tid]) + s_a[2 * SMALL_GRAD_NS + tid]) + s_a[3 * SMALL_GRAD_NS + tid];
-        res[3 + tid] = info ? __builtin_nan("") : v;
-    }
-    GPMI_STAMP(tg5)
-    GPMI_STAMP_ADD(7, tg5 - tg4)
-    if (tid == 0) {
-        if (info_out) *info_out = info;
-        if (info) {
-            res[0] = res[1] = res[2] = __builtin_nan("");
-        } else {
-            res[1] = sum_log;
-            res[2] = zz;
-            res[0] = -0.5 * zz - sum_log - 0.5 * (double)n * 1.8378770664093454835606594728112;  // log(2 pi)
-        }
-    }
-}
-
-// Completion flag of the one-launch host-buffer calls: the results lie in pinned, device-mapped host memory; every thread
-// makes its stores visible system-wide, the workgroup meets, and thread 0 publishes `seq` -- the host polls the flag instead of
-// paying a stream synchronisation (~8 us of a 30 us call).  done == nullptr: no flag.
-__device__ __forceinline__ void small_signal_done(int *done, int seq)
-{
-    if (!done) return;   // kernel argument: workgroup-uniform
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-constexpr int SMALL_PTS = 128;  // grid points per launch: their hyper-parameters travel as kernel arguments
-struct SmallBatch {
-    double a2[SMALL_PTS], inv_rho[SMALL_PTS], diag[SMALL_PTS];
-};
-
-// Workgroup memory of the small kernels: staging buffer of gemm_tile / workspace of the diagonal-block body, the
-// packed factors of the current panel, reduction / substitution scratch.  DYNAMIC: with 148 KB of static LDS the
-// compiler knows that one workgroup fits per CU, hands the kernel all 512 registers and moves values through AGPRs
-// around factor16's hand-scheduled DPP chain -- whose hazard spacing (the recogniser cannot see into asm statements)
-// it thereby breaks (v_accvgpr_read directly in front of a DPP read of the same register: wrong numbers).  With
-// the size unknown at compile time __launch_bounds__(256, 2) holds and the kernel is allocated like k_gemm_nt<0>:
-// <= 256 registers, no AGPR traffic.
-constexpr int SMALL_LDS_DOUBLES = 2 * 2 * GK * GP + GPMI_FPACK + 512;
-extern __shared__ __attribute__((aligned(16))) double small_lds[];
-#define GPMI_SMALL_LDS                                                                                   \
-    double (&smem)[2][2][GK][GP] = *reinterpret_cast<double (*)[2][2][GK][GP]>(small_lds);               \
-    double *s_F = small_lds + 2 * 2 * GK * GP;                                                           \
-    double *s_aux = s_F + GPMI_FPACK;
-
-// stage (nullable): X and y are host-mapped memory (the host-buffer entry point): they are first copied, one
-// coalesced pass with every load in flight (one PCIe round trip), to `stage` in device memory; out3 / info_out
-// may likewise be host-mapped -- nothing is copied around the launch
-__global__ __launch_bounds__(256, 2) void k_logml_small(const double *__restrict__ X, int n, int ldx, const double *__restrict__ y,
-                                                     SeParams p, double diag_add, double *__restrict__ W, size_t ld,
-                                                     double *__restrict__ out3, int *info_out, int *info_w, ExpC ec,
-                                                     double *__restrict__ stage, int *done, int seq)
-{
-    GPMI_SMALL_LDS
-    if (stage) {
-        const int nx = n * p.D;
-        for (int e = threadIdx.x; e < nx + n; e += 256) {
-            const int d = e / n, i = e - d * n;
-            stage[e] = (e < nx) ? X[(size_t)i + (size_t)d * ldx] : y[e - nx];
-        }
-        __syncthreads();
-        X = stage;
-        y = stage + nx;
-        ldx = n;
-    }
-    SmallSe se;
-    se.a2 = p.a2;
-    se.D = p.D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
-    logml_small_body(smem, s_F, s_aux, X, n, ldx, y, se, diag_add, W, ld, out3, info_out, info_w, ec);
-    small_signal_done(done, seq);
-}
-
-// workgroup g = point g of the batch: isotropic (alpha, rho, sigma) as in gpmi_logml_grid; workspace slice g
-__global__ __launch_bounds__(256, 2) void k_logml_small_batch(const double *__restrict__ X, int n, int ldx, int D,
-                                                           const double *__restrict__ y, SmallBatch b, double *__restrict__ Wall,
-                                                           size_t wstride, size_t ld, double *__restrict__ out3, int *info_out,
-                                                           int *info_w, ExpC ec)
-{
-    GPMI_SMALL_LDS
-    const int g = blockIdx.x;
-    SmallSe se;
-    se.a2 = b.a2[g];
-    se.D = D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = b.inv_rho[g];
-    logml_small_body(smem, s_F, s_aux, X, n, ldx, y, se, b.diag[g], Wall + (size_t)g * wstride, ld, out3 + 3 * (size_t)g,
-                     info_out + g, info_w + g, ec);
-}
-
-// the same with one length-scale PER DIMENSION and point (ARD grids: QQard takes a vector phi[[2]], R/kernels.R:11-19);
-// 32 points per launch (their D <= 8 inverse length-scales travel as kernel arguments too)
-constexpr int SMALL_PTS_ARD = 32;
-struct SmallBatchArd {
-    double a2[SMALL_PTS_ARD], diag[SMALL_PTS_ARD], inv_ell[SMALL_PTS_ARD][GPMI_MAXD];
-};
-__global__ __launch_bounds__(256, 2) void k_logml_small_batch_ard(const double *__restrict__ X, int n, int ldx, int D,
-                                                               const double *__restrict__ y, SmallBatchArd b,
-                                                               double *__restrict__ Wall, size_t wstride, size_t ld,
-                                                               double *__restrict__ out3, int *info_out, int *info_w, ExpC ec)
-{
-    GPMI_SMALL_LDS
-    const int g = blockIdx.x;
-    SmallSe se;
-    se.a2 = b.a2[g];
-    se.D = D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = b.inv_ell[g][d];
-    logml_small_body(smem, s_F, s_aux, X, n, ldx, y, se, b.diag[g], Wall + (size_t)g * wstride, ld, out3 + 3 * (size_t)g,
-                     info_out + g, info_w + g, ec);
-}
-
-// Points whose hyper-parameters lie in DEVICE memory -- any number per launch, isotropic or ARD: par[g] = {alpha^2,
-// sigma^2 + jitter, 1 / ell_0 .. 1 / ell_7}.  Used for grids of more than GPMI_SMALL_PTS points and for the mid sizes
-// (n <= 1024) at which a grid large enough to give every CU a problem of its own beats the four lanes of the blocked path.
-constexpr int SMALL_PAR = 2 + GPMI_MAXD;
-__global__ __launch_bounds__(256, 2) void k_logml_small_batch_dev(const double *__restrict__ X, int n, int ldx, int D,
-                                                               const double *__restrict__ y, const double *__restrict__ par,
-                                                               double *__restrict__ Wall, size_t wstride, size_t ld,
-                                                               double *__restrict__ out3, int *info_out, int *info_w, ExpC ec)
-{
-    GPMI_SMALL_LDS
-    const int g = blockIdx.x;
-    const double *pg = par + (size_t)g * SMALL_PAR;
-    SmallSe se;
-    se.a2 = pg[0];
-    se.D = D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = pg[2 + d];
-    logml_small_body(smem, s_F, s_aux, X, n, ldx, y, se, pg[1], Wall + (size_t)g * wstride, ld, out3 + 3 * (size_t)g,
-                     info_out + g, info_w + g, ec);
-}
-
-// value + gradient sums: one evaluation (host-mapped X, y staged as in k_logml_small) ...
-constexpr int SMALL_GRAD_LDS_DOUBLES = SMALL_LDS_DOUBLES + 512;   // s_aux: two reduction arrays + z + a
-__global__ __launch_bounds__(256, 2) void k_logml_grad_small(const double *__restrict__ X, int n, int ldx, const double *__restrict__ y,
-                                                          SeParams p, double diag_add, double *__restrict__ W, size_t ld,
-                                                          double *__restrict__ U, double *__restrict__ res, int *info_out, int *info_w,
-                                                          ExpC ec, double *__restrict__ stage, int *done, int seq)
-{
-    GPMI_SMALL_LDS
-    if (stage) {
-        const int nx = n * p.D;
-        for (int e = threadIdx.x; e < nx + n; e += 256) {
-            const int d = e / n, i = e - d * n;
-            stage[e] = (e < nx) ? X[(size_t)i + (size_t)d * ldx] : y[e - nx];
-        }
-        __syncthreads();
-        X = stage;
-        y = stage + nx;
-        ldx = n;
-    }
-    SmallSe se;
-    se.a2 = p.a2;
-    se.D = p.D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
-    logml_grad_small_body(smem, s_F, s_aux, X, n, ldx, y, se, diag_add, W, ld, U, res, info_out, info_w, ec);
-    small_signal_done(done, seq);
-}
-
-// ... and G isotropic points (the chains of a sampler: rstan's default is four), one workgroup each; slice g of Wall holds
-// W and, ustride doubles behind it, U
-__global__ __launch_bounds__(256, 2) void k_logml_grad_small_batch(const double *__restrict__ X, int n, int ldx, int D,
-                                                                const double *__restrict__ y, SmallBatch b,
-                                                                double *__restrict__ Wall, size_t wstride, size_t ustride, size_t ld,
-                                                                double *__restrict__ res, int *info_out, int *info_w, ExpC ec,
-                                                                double *__restrict__ stage, int *done, int seq, int *arrive)
-{
-    GPMI_SMALL_LDS
-    const int g = blockIdx.x;
-    if (stage) {   // X, y host-mapped (few chains: every workgroup stages its own copy, one PCIe round trip, side by side)
-        double *st = stage + (size_t)g * n * (D + 1);
-        const int nx = n * D;
-        for (int e = threadIdx.x; e < nx + n; e += 256) {
-            const int d = e / n, i = e - d * n;
-            st[e] = (e < nx) ? X[(size_t)i + (size_t)d * ldx] : y[e - nx];
-        }
-        __syncthreads();
-        X = st;
-        y = st + nx;
-        ldx = n;
-    }
-    SmallSe se;
-    se.a2 = b.a2[g];
-    se.D = D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = b.inv_rho[g];
-    double *W = Wall + (size_t)g * wstride;
-    logml_grad_small_body(smem, s_F, s_aux, X, n, ldx, y, se, b.diag[g], W, ld, W + ustride, res + (size_t)g * SMALL_GRAD_RES,
-                          info_out + g, info_w + g, ec);
-    if (done) {   // the LAST workgroup to finish publishes the completion flag (device counter `arrive`, re-armed by it)
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int k = __hip_atomic_fetch_add(arrive, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == (int)gridDim.x - 1) {
-                __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
-}
-
-// One posterior draw of the derivative process (sample_derivs, pendulum_fit.R:227-255) per workgroup: the loop
-// mclapply(s_list[1:100], sample_derivs_both_states, mc.cores = 2) (:261-268) is B independent draws, each with its own
-// (l, a, sy) and noisy series, at n = m = 199 -- a chain of ~25 latency-bound launches per draw on the blocked path.  Here
-// draw b builds [[a^2 QQ + sy^2 I, .], [a^2 RQ, a^2 RR]] with the row [y^T, 0] (the arithmetic of k_deriv_cov: deriv_val),
-// factors the first n columns (Schur complement = cov - jitter I in the trailing block, -mu^T in the last row), adds the
-// jitter, factors the m x m block in place and forms mu + chol(cov) z -- the composition of sample_derivs_core.
-// par[3 g ..] = (l, a, sy) of draw g, in device memory (any number of draws per launch).
-// status: 0, k (K + sy^2 I not PD at order k), n + k (cov).
-__global__ __launch_bounds__(256, 2) void k_sample_derivs_small_batch(const double *__restrict__ t, int n, const double *__restrict__ ts,
-                                                                   int m, const double *__restrict__ Y, const double *__restrict__ par,
-                                                                   double jitter, const double *__restrict__ Z, double *__restrict__ Wall,
-                                                                   size_t wstride, size_t ld, double *__restrict__ draws,
-                                                                   double *__restrict__ mus, int *__restrict__ status,
-                                                                   int *__restrict__ info_w)
-{
-    GPMI_SMALL_LDS
-    const int g = blockIdx.x, tid = threadIdx.x;
-    const int nt = n + m;
-    double *W = Wall + (size_t)g * wstride;
-    const double a2 = par[3 * g + 1] * par[3 * g + 1], l2 = par[3 * g] * par[3 * g], s2 = par[3 * g + 2] * par[3 * g + 2];
-    const double *y = Y + (size_t)g * n, *z = Z + (size_t)g * m;
-    int *iw = info_w + 2 * g;
-    if (tid < 2) iw[tid] = 0;
-    // lower triangle of the joint matrix, thread = row, and the augmented row
-    for (int i = tid; i < nt; i += 256) {
-        const bool star = i >= n;
-        const double xi = star ? ts[i - n] : t[i];
-        const int jn = i < n ? i + 1 : n;
-        for (int j = 0; j < jn; ++j) {
-            double v = a2 * deriv_val(star ? GPMI_RQ : GPMI_QQ, xi, t[j], l2);
-            if (i == j) v += s2;
-            W[(size_t)i + (size_t)j * ld] = v;
-        }
-        for (int j = n; j <= i; ++j) W[(size_t)i + (size_t)j * ld] = a2 * deriv_val(GPMI_RR, xi, ts[j - n], l2);
-    }
-    for (int j = tid; j < nt; j += 256) W[(size_t)nt + (size_t)j * ld] = j < n ? y[j] : 0.0;
-    __syncthreads();
-    small_potrf_partial(smem, s_F, s_aux, W, ld, nt + 1, nt, n, iw, false);
-    __syncthreads();
-    double *S = W + (size_t)n + (size_t)n * ld;
-    for (int j = tid; j < m; j += 256) {
-        S[(size_t)j * (ld + 1)] += jitter;
-        const double mu = -W[(size_t)nt + (size_t)(n + j) * ld];
-        mus[(size_t)g * m + j] = mu;
-    }
-    __syncthreads();
-    small_potrf_partial(smem, s_F, s_aux, S, ld, m, m, m, iw + 1, false);
-    __syncthreads();
-    // draw = mu + L z: row i, columns 0 .. i in order (the order of k_trmv_lower_part within a chunk), sixteen loads in flight
-    for (int i0 = 0; i0 < m; i0 += 256) {
-        const int i = i0 + tid, ic = i < m ? i : m - 1;
-        double acc = 0.0;
-        const int jend = (i0 + 255 < m ? i0 + 255 : m - 1);   // workgroup-uniform bound; columns > i contribute exact zeros
-        for (int j0 = 0; j0 <= jend; j0 += 16) {
-            double u[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int j = j0 + q <= ic ? j0 + q : ic;
-                u[q] = S[(size_t)ic + (size_t)j * ld];
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (j0 + q <= ic) acc = fma(u[q], z[j0 + q], acc);
-        }
-        if (i < m) draws[(size_t)g * m + i] = acc + mus[(size_t)g * m + i];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int i1 = __hip_atomic_load(iw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int i2 = __hip_atomic_load(iw + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        status[g] = i1 ? i1 : (i2 ? n + i2 : 0);
-    }
-}
-
-// gpmi_gp_condition (p_Xn / p_dotXn, R/ode_gp.R:1-32; the moments of sample_derivs) at the sizes R/tests.R runs it by ONE
-// workgroup: joint matrix [[K + s2 I, .], [Ks, Kss]] with the row [y^T, 0] (deriv_cov_val: the arithmetic of k_deriv_cov),
-// partial factorisation of the first n columns, then Kn = Schur complement mirrored + jitter I and mn = minus the last row --
-// the launch chain's nine kernels and six copies in one launch.  stage (nullable): t, ts, y are host-mapped and are copied
-// to device memory first; Kn / mn / info_out may be host-mapped as well.
-struct CondArgs {
-    int kindK, kindS, kindSS, compat;
-    double a2, l2, s2, jitter;
-};
-__global__ __launch_bounds__(256, 2) void k_gp_condition_small(const double *__restrict__ t, int n, const double *__restrict__ ts, int m,
-                                                            const double *__restrict__ y, CondArgs q, double *__restrict__ W, size_t ld,
-                                                            double *__restrict__ Kn, size_t ldo, double *__restrict__ mn, int *info_out,
-                                                            int *info_w, double *__restrict__ stage, int *done, int seq)
-{
-    GPMI_SMALL_LDS
-    const int tid = threadIdx.x, nt = n + m;
-    if (stage) {
-        for (int e = tid; e < 2 * n + m; e += 256) stage[e] = e < n ? t[e] : (e < nt ? ts[e - n] : y[e - nt]);
-        __syncthreads();
-        t = stage;
-        ts = stage + n;
-        y = stage + nt;
-    }
-    if (tid == 0) *info_w = 0;
-    for (int i = tid; i < nt; i += 256) {
-        const bool star = i >= n;
-        const double xi = star ? ts[i - n] : t[i];
-        const int jn = i < n ? i + 1 : n;
-        for (int j = 0; j < jn; ++j) {
-            double v = deriv_cov_val(star ? q.kindS : q.kindK, q.compat, q.a2, xi, t[j], q.l2);
-            if (i == j) v += q.s2;
-            W[(size_t)i + (size_t)j * ld] = v;
-        }
-        for (int j = n; j <= i; ++j) W[(size_t)i + (size_t)j * ld] = deriv_cov_val(q.kindSS, q.compat, q.a2, xi, ts[j - n], q.l2);
-    }
-    for (int j = tid; j < nt; j += 256) W[(size_t)nt + (size_t)j * ld] = j < n ? y[j] : 0.0;
-    __syncthreads();
-    small_potrf_partial(smem, s_F, s_aux, W, ld, nt + 1, nt, n, info_w, false);
-    __syncthreads();
-    const double *S = W + (size_t)n + (size_t)n * ld;
-    for (int r = tid; r < m; r += 256) {
-        for (int c = 0; c < m; ++c) {
-            double v = (r >= c) ? S[(size_t)r + (size_t)c * ld] : S[(size_t)c + (size_t)r * ld];
-            if (r == c) v += q.jitter;
-            Kn[(size_t)r + (size_t)c * ldo] = v;
-        }
-        mn[r] = -W[(size_t)nt + (size_t)(n + r) * ld];
-    }
-    if (tid == 0) *info_out = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    small_signal_done(done, seq);
-}
-
-// gpmi_gp_predict (pointwise posterior mean and variance at m new D-dimensional inputs; what the sweep of R/tests.R:89-97 asks
-// of create_p_dotXnS, R/ode_gp_library.R:43-93) at the reference's sizes by ONE workgroup: joint matrix
-// [[K + diag_add I, .], [Ks, alpha^2 on the diagonal]] of the n + m points [X; Xs] built with se_cov_tile (the arithmetic of
-// gpmi_se_cov), the row [y^T, 0], partial factorisation of the first n columns; the Schur block's diagonal is then var and the
-// last row -mean.  X, Xs, y are read exactly once each (into LDS / the workspace), so host-mapped inputs need no staging copy;
-// mean / var (nullable) / info_out may be host-mapped as well.
-__global__ __launch_bounds__(256, 2) void k_gp_predict_small(const double *__restrict__ X, int n, int ldx, const double *__restrict__ Xs,
-                                                          int m, int ldxs, const double *__restrict__ y, SeParams p, double diag_add,
-                                                          double *__restrict__ W, size_t ld, double *__restrict__ mean,
-                                                          double *__restrict__ var, int *info_out, int *info_w, ExpC ec, int *done,
-                                                          int seq)
-{
-    GPMI_SMALL_LDS
-    const int tid = threadIdx.x, nt = n + m;
-    if (tid == 0) *info_w = 0;
-    SmallSe se;
-    se.a2 = p.a2;
-    se.D = p.D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
-    {
-        double *xs = &smem[0][0][0][0];   // nt * D <= 1024 * GPMI_MAXD doubles fit the tile staging buffer
-#pragma unroll
-        for (int d = 0; d < GPMI_MAXD; ++d)
-            if (d < se.D)
-                for (int i = tid; i < nt; i += 256)
-                    xs[i + d * nt] = __dmul_rn(i < n ? X[(size_t)i + (size_t)d * ldx] : Xs[(size_t)(i - n) + (size_t)d * ldxs], se.inv_ell[d]);
-        __syncthreads();
-        for (int row0 = 0; row0 < nt; row0 += SE_TR)
-            for (int col0 = 0; col0 < row0 + SE_TR && col0 < nt; col0 += SE_TC) {
-                switch (se.D) {
-                case 1: se_cov_tile<1, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 2: se_cov_tile<2, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 3: se_cov_tile<3, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                default: se_cov_tile<0, true>(xs, nt, nt, xs, nt, nt, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                }
-            }
-    }
-    __syncthreads();
-    // the new points carry the latent function's prior variance: no noise term on their diagonal
-    for (int i = n + tid; i < nt; i += 256) W[(size_t)i * (ld + 1)] = se.a2;
-    for (int j = tid; j < nt; j += 256) W[(size_t)nt + (size_t)j * ld] = j < n ? y[j] : 0.0;
-    __syncthreads();
-    small_potrf_partial(smem, s_F, s_aux, W, ld, nt + 1, nt, n, info_w, false);
-    __syncthreads();
-    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int r = tid; r < m; r += 256) {
-        const size_t c = (size_t)(n + r);
-        mean[r] = info ? __builtin_nan("") : -W[(size_t)nt + c * ld];
-        if (var) var[r] = info ? __builtin_nan("") : W[c * (ld + 1)];
-    }
-    if (tid == 0) *info_out = info;
-    small_signal_done(done, seq);
-}
-
-// f = chol(cov_exp_quad(X, alpha, ell) + diag_add I) z (models/exact_gp.stan:17-25: the latent exact GP's transform, once per
-// leapfrog step with a new length-scale) by ONE workgroup for n <= 256: build (se_cov_tile), factorisation, and the row sums
-// f_i = sum_{j <= i} L_ij z_j in column order (the order of k_trmv_lower_part inside its first chunk).  stage (nullable): X, z
-// host-mapped -> copied to device memory first; f / info_out may be host-mapped.
-__global__ __launch_bounds__(256, 2) void k_exact_gp_small(const double *__restrict__ X, int n, int ldx, const double *__restrict__ z,
-                                                        SeParams p, double diag_add, double *__restrict__ W, size_t ld,
-                                                        double *__restrict__ f, int *info_out, int *info_w, ExpC ec,
-                                                        double *__restrict__ stage, int *done, int seq)
-{
-    GPMI_SMALL_LDS
-    const int tid = threadIdx.x;
-    if (stage) {
-        const int nx = n * p.D;
-        for (int e = tid; e < nx + n; e += 256) {
-            const int d = e / n, i = e - d * n;
-            stage[e] = (e < nx) ? X[(size_t)i + (size_t)d * ldx] : z[e - nx];
-        }
-        __syncthreads();
-        X = stage;
-        z = stage + nx;
-        ldx = n;
-    }
-    if (tid == 0) *info_w = 0;
-    SmallSe se;
-    se.a2 = p.a2;
-    se.D = p.D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
-    {
-        double *xs = &smem[0][0][0][0];
-#pragma unroll
-        for (int d = 0; d < GPMI_MAXD; ++d)
-            if (d < se.D)
-                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-        __syncthreads();
-        for (int row0 = 0; row0 < n; row0 += SE_TR)
-            for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
-                switch (se.D) {
-                case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                }
-            }
-    }
-    __syncthreads();
-    small_potrf_partial(smem, s_F, s_aux, W, ld, n, n, n, info_w, false);
-    __syncthreads();
-    if (tid < n) s_aux[tid] = z[tid];
-    __syncthreads();
-    if (tid < n) {
-        const int i = tid;
-        double acc = 0.0;
-        for (int j0 = 0; j0 <= i; j0 += 16) {
-            double u[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int j = j0 + q <= i ? j0 + q : i;
-                u[q] = W[(size_t)i + (size_t)j * ld];
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (j0 + q <= i) acc = fma(u[q], s_aux[j0 + q], acc);
-        }
-        const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        f[i] = info ? __builtin_nan("") : acc;
-    }
-    if (tid == 0) *info_out = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    small_signal_done(done, seq);
-}
-
-// The vector-Jacobian product of the same transform for k <= GPMI_VJP_KMAX columns (F = L Z; adjoint Fbar), what NUTS asks of
-// models/exact_gp.stan:17-25 (and, k = 2, of models/heteroscedastic.stan:23-32) at every leapfrog step, by ONE workgroup for
-// n <= 256.  The chain of gpmi_api.hip (exact_gp_vjp_core) states the algebra; here:
-//   build, factorisation with U = L^-T riding along (small_potrf_partial<true>, as k_logml_grad_small);
-//   F column by column with the loop of k_exact_gp_small (bit-identical to the value call);
-//   Zbar = W = L^T Fbar, thread = column of L;
-//   V = U Phi(W Z^T) by the suffix sums along the rows of U o w_c, thread = row;
-//   2 Sbar = V U^T + U V^T = [V U] [U V]^T by gemm_tile<3> with K = 2n (V, U, V stored side by side, so that ONE product per
-//   tile forms it) and contracted in registers against dK/dtheta as logml_grad_small_body contracts K^-1.
-// R: 3 n columns of leading dimension ld, [V | U | V]; the gradient (1 + n_ell) is finished on the device.
-constexpr int VJP_KMAX = GPMI_VJP_KMAX;
-// HEAD: Fbar is not an input but the adjoint of a likelihood head evaluated on F (gpmi_latent_gp_lp_grad): F is formed
-// unconditionally, thread = row evaluates latent_head_row (k <= 2), lik and d lik / d sigma are reduced in a fixed order into
-// out[0..1], and Fb (nullable) receives the Fbar the sweep then uses.  Everything else is the same statement for both instances.
-template <bool HEAD>
-__device__ __forceinline__ void exact_gp_vjp_small_body(const double *__restrict__ X, int n, int ldx, const SeParams &p,
-                                                        double diag_add, const double *__restrict__ Z, int k, int ldz,
-                                                        std::conditional_t<HEAD, double, const double> *__restrict__ Fb, int ldfb,
-                                                        double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
-                                                        double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                        const GradEll &el, int n_ell, double *__restrict__ grad, int *info_out,
-                                                        int *info_w, const ExpC &ec, double *__restrict__ stage, int *done, int seq,
-                                                        const LatentHead &lh, double *__restrict__ out)
-{
-    GPMI_SMALL_LDS
-    constexpr int KM = HEAD ? 2 : VJP_KMAX;   // columns the per-column loops unroll for (the heads have k <= 2)
-    // HEAD: at its phase boundaries below the thread index passes through an empty asm, so that what later phases derive from it
-    // (row and column addresses the compiler would otherwise form early) is not kept live, i.e. spilled, across the head's
-    // exp / log1p: with these the instance needs the scratch of the plain one (3824 B per lane), without them 56 B more
-    int tid = threadIdx.x;
-    if (stage) {   // host-mapped X, Z, Fbar (HEAD: Y): one coalesced pass into device memory
-        const int nx = n * p.D, nz = n * k;
-        if constexpr (HEAD) {
-            const int ny = n * lh.m;
-            for (int e = tid; e < nx + nz + ny; e += 256) {
-                if (e < nx) {
-                    const int d = e / n, i = e - d * n;
-                    stage[e] = X[(size_t)i + (size_t)d * ldx];
-                } else if (e < nx + nz) {
-                    const int c = (e - nx) / n, i = e - nx - c * n;
-                    stage[e] = Z[(size_t)i + (size_t)c * ldz];
-                } else {
-                    const int c = (e - nx - nz) / n, i = e - nx - nz - c * n;
-                    stage[e] = lh.Y[(size_t)i + (size_t)c * lh.ldy];
-                }
-            }
-            __syncthreads();
-        } else {
-            for (int e = tid; e < nx + 2 * nz; e += 256) {
-                if (e < nx) {
-                    const int d = e / n, i = e - d * n;
-                    stage[e] = X[(size_t)i + (size_t)d * ldx];
-                } else {
-                    const int e2 = e - nx, src = e2 < nz ? e2 : e2 - nz, c = src / n, i = src - c * n;
-                    stage[e] = e2 < nz ? Z[(size_t)i + (size_t)c * ldz] : Fb[(size_t)i + (size_t)c * ldfb];
-                }
-            }
-            __syncthreads();
-            Fb = stage + nx + nz;
-            ldfb = n;
-        }
-        X = stage;
-        Z = stage + nx;
-        ldx = ldz = n;
-    }
-    if (tid == 0) *info_w = 0;
-    SmallSe se;
-    se.a2 = p.a2;
-    se.D = p.D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
-    double *V = R, *U = R + (size_t)n * ld, *V2 = R + 2 * (size_t)n * ld;
-    {
-        double *xs = &smem[0][0][0][0];
-#pragma unroll
-        for (int d = 0; d < GPMI_MAXD; ++d)
-            if (d < se.D)
-                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-        __syncthreads();
-        for (int row0 = 0; row0 < n; row0 += SE_TR)
-            for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
-                switch (se.D) {
-                case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                }
-            }
-    }
-    {   // U = I (as logml_grad_small_body)
-        const int rp = 2 * (tid & 127), cp = tid >> 7;
-        if (rp < n)
-            for (int j = cp; j < n; j += 2) *reinterpret_cast<double2 *>(U + (size_t)rp + (size_t)j * ld) = make_double2(0.0, 0.0);
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) U[(size_t)i * (ld + 1)] = 1.0;
-    }
-    __syncthreads();
-    small_potrf_partial<true>(smem, s_F, s_aux, W, ld, n, n, n, info_w, false, U);
-    __syncthreads();
-    if constexpr (HEAD) asm volatile("" : "+v"(tid));
-    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // the packed factors are no longer needed: s_F holds the scaled coordinates, Fbar (then W) and Z, k n doubles each
-    double *xg = s_F, *s_w = s_F + 2048, *s_z = s_F + 4096;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d)
-        if (d < se.D)
-            for (int i = tid; i < n; i += 256) xg[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-    for (int e = tid; e < n * k; e += 256) {
-        const int c = e / n, i = e - c * n;
-        s_z[e] = Z[(size_t)i + (size_t)c * ldz];
-        if constexpr (!HEAD) s_w[e] = Fb[(size_t)i + (size_t)c * ldfb];
-    }
-    __syncthreads();
-    // F, one column at a time: the loop of k_exact_gp_small (row sums in column order)
-    if constexpr (HEAD) asm volatile("" : "+v"(tid));
-    if (HEAD || F)
-        for (int c = 0; c < k; ++c) {
-            if (tid < n) {
-                const int i = tid;
-                const double *zc = s_z + c * n;
-                double acc = 0.0;
-                for (int j0 = 0; j0 <= i; j0 += 16) {
-                    double u[16];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const int j = j0 + q <= i ? j0 + q : i;
-                        u[q] = W[(size_t)i + (size_t)j * ld];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (j0 + q <= i) acc = fma(u[q], zc[j0 + q], acc);
-                }
-                if (F) F[(size_t)i + (size_t)c * ldf] = info ? __builtin_nan("") : acc;
-                if constexpr (HEAD) s_w[c * n + i] = acc;   // the head reads its row of F here and leaves Fbar
-            }
-        }
-    if constexpr (HEAD) {
-        // the head on this thread's row, Fbar into LDS where the sweep reads it; lik and d lik / d sigma by a butterfly inside
-        // every wave and the four wave sums added in wave order
-        double red0 = 0.0, red1 = 0.0, fb0 = 0.0, fb1 = 0.0;
-        if (tid < n) {
-            // Y: the copy made at entry when staged (derived here rather than kept live across the factorisation)
-            const LatentHead hd{lh.family, stage ? stage + n * (p.D + k) : lh.Y, lh.m, stage ? n : lh.ldy, lh.sigma, lh.log_sigma};
-            latent_head_row(hd, s_w[tid], k > 1 ? s_w[n + tid] : 0.0, hd.Y + tid, red0, red1, fb0, fb1);
-            for (int c = 0; c < k; ++c) {
-                const double v = c ? fb1 : fb0;
-                s_w[c * n + tid] = v;
-                if (Fb) Fb[(size_t)tid + (size_t)c * ldfb] = info ? __builtin_nan("") : v;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            red0 += __shfl_xor(red0, off, 64);
-            red1 += __shfl_xor(red1, off, 64);
-        }
-        if ((tid & 63) == 0) {
-            s_aux[(tid >> 6) * 2] = red0;
-            s_aux[(tid >> 6) * 2 + 1] = red1;
-        }
-        __syncthreads();   // (also: every row of Fbar is in s_w)
-        if (tid < 2) out[tid] = info ? __builtin_nan("") : ((s_aux[tid] + s_aux[2 + tid]) + s_aux[4 + tid]) + s_aux[6 + tid];
-        asm volatile("" : "+v"(tid));
-    }
-    // W = L^T Fbar: thread = column j of L, all k columns at once
-    double wj[KM];
-#pragma unroll
-    for (int c = 0; c < KM; ++c) wj[c] = 0.0;
-    if (tid < n) {
-        const int j = tid;
-        const double *col = W + (size_t)j * ld;
-        for (int i0 = j; i0 < n; i0 += 8) {
-            double l8[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) l8[q] = col[i0 + q < n ? i0 + q : n - 1];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (i0 + q < n)
-#pragma unroll
-                    for (int c = 0; c < KM; ++c)
-                        if (c < k) wj[c] = fma(l8[q], s_w[c * n + i0 + q], wj[c]);
-        }
-    }
-    __syncthreads();   // every thread has read Fbar
-    if (tid < n)
-#pragma unroll
-        for (int c = 0; c < KM; ++c)
-            if (c < k) {
-                s_w[c * n + tid] = wj[c];
-                Zb[(size_t)tid + (size_t)c * ldzb] = info ? __builtin_nan("") : wj[c];
-            }
-    __syncthreads();
-    if constexpr (HEAD) asm volatile("" : "+v"(tid));
-    // V = U Phi(W Z^T): thread = row i, columns from the last to the first, one running suffix sum per column of Z
-    if (tid < n) {
-        const int i = tid;
-        double P[KM];
-#pragma unroll
-        for (int c = 0; c < KM; ++c) P[c] = 0.0;
-        for (int j1 = n; j1 > 0; j1 -= 16) {
-            double u[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int j = j1 - 1 - q;
-                u[q] = (j >= i) ? U[(size_t)i + (size_t)j * ld] : 0.0;
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int j = j1 - 1 - q;
-                if (j < 0) break;
-                double v = 0.0;
-#pragma unroll
-                for (int c = 0; c < KM; ++c)
-                    if (c < k) {
-                        const double t = u[q] * s_w[c * n + j];
-                        v = fma(s_z[c * n + j], fma(0.5, t, P[c]), v);
-                        P[c] += t;
-                    }
-                V[(size_t)i + (size_t)j * ld] = v;
-                V2[(size_t)i + (size_t)j * ld] = v;
-            }
-        }
-    }
-    __syncthreads();
-    if constexpr (HEAD) asm volatile("" : "+v"(tid));
-    // [V U] [U V]^T tile by tile (lower tiles), contracted where it is produced; the columns of [V U] left of the tile's first
-    // column are skipped (U's rows there are zero in V U^T; U V^T needs them all)
-    double acc[1 + GPMI_MAXD];
-#pragma unroll
-    for (int q = 0; q < 1 + GPMI_MAXD; ++q) acc[q] = 0.0;
-    const double a2 = se.a2;
-    auto sbar_tiles = [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;   // compile-time dimension count (0: se.D at run time, <= GPMI_MAXD)
-        const int Dn = DT ? DT : se.D;
-        constexpr int DH = DT ? DT : 1;
-        double xm[4][DH], xn[DH];
-        int mm[4], ncur = 0;
-        bool okn = false;
-        auto contract = make_epi3(
-            [&](int tm, int m, bool ok) {
-                mm[tm] = ok ? m : -1;
-                if constexpr (DT != 0) {
-                    const int mc = ok ? m : 0;
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) xm[tm][d] = xg[mc + d * n];
-                }
-            },
-            [&](int nn, bool ok) {
-                ncur = ok ? nn : 0;
-                okn = ok;
-                if constexpr (DT != 0) {
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) xn[d] = xg[ncur + d * n];
-                }
-            },
-            [&](double s2, int tm) {
-                double e = 0.0, r2[GPMI_MAXD];
-                const int mc = mm[tm] < 0 ? 0 : mm[tm];
-#pragma unroll
-                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) {
-                    double r;
-                    if constexpr (DT != 0) r = xm[tm][d] - xn[d];
-                    else r = d < Dn ? xg[mc + d * n] - xg[ncur + d * n] : 0.0;
-                    r2[d] = r * r;
-                    e += r2[d];
-                }
-                const double kse = a2 * exp_nonpos(-0.5 * e, ec);
-                const bool lower = okn && ncur <= mm[tm];
-                const double c = lower ? ((ncur == mm[tm]) ? 0.5 : 1.0) * s2 * kse : 0.0;
-                acc[0] += c;
-#pragma unroll
-                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) acc[1 + d] += c * r2[d];
-            });
-        for (int ti = 0; ti * GT < n; ++ti)
-            for (int tj = 0; tj <= ti; ++tj) {
-                const int k0 = tj * GT;
-                gemm_tile<3>(smem, R + (size_t)k0 * ld, ld, U + (size_t)k0 * ld, ld, W, ld, n, n, 2 * n - k0, ti, tj, 0,
-                             (int)threadIdx.x, contract);
-                __syncthreads();
-            }
-    };
-    switch (se.D) {
-    case 1: sbar_tiles(ic<1>{}); break;
-    case 2: sbar_tiles(ic<2>{}); break;
-    case 3: sbar_tiles(ic<3>{}); break;
-    default: sbar_tiles(ic<0>{}); break;
-    }
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d)   // sums over UNSCALED squared differences (layout of k_grad_partial)
-        acc[1 + d] = (d < se.D) ? acc[1 + d] / (se.inv_ell[d] * se.inv_ell[d]) : 0.0;
-    // fixed-shape reduction: butterfly inside every wave, the four wave sums added in wave order
-    double *s_r = s_aux;
-#pragma unroll
-    for (int q = 0; q < 1 + GPMI_MAXD; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((tid & 63) == 0) s_r[(tid >> 6) * (1 + GPMI_MAXD) + q] = v;
-    }
-    __syncthreads();
-    if (tid < 1 + GPMI_MAXD) {
-        constexpr int S = 1 + GPMI_MAXD;
-        s_r[4 * S + tid] = ((s_r[tid] + s_r[S + tid]) + s_r[2 * S + tid]) + s_r[3 * S + tid];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double nan = __builtin_nan("");
-        if (info)
-            for (int q = 0; q <= n_ell; ++q) grad[q] = nan;
-        else
-            gpmi_grad_from_sums(s_r + 4 * (1 + GPMI_MAXD), se.D, alpha, el.ell, n_ell, grad);
-        *info_out = info;
-    }
-    small_signal_done(done, seq);
-}
-
-__global__ __launch_bounds__(256, 2) void k_exact_gp_vjp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
-                                                            const double *__restrict__ Z, int k, int ldz, const double *__restrict__ Fb,
-                                                            int ldfb, double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
-                                                            double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                            GradEll el, int n_ell, double *__restrict__ grad, int *info_out,
-                                                            int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
-{
-    exact_gp_vjp_small_body<false>(X, n, ldx, p, diag_add, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, W, R, ld, alpha, el, n_ell,
-                                   grad, info_out, info_w, ec, stage, done, seq, LatentHead{}, nullptr);
-}
-
-// forward product, likelihood head, its adjoint and the reverse sweep in one launch (gpmi_latent_gp_lp_grad, n <= 256, k <= 2):
-// out[0] = lik, out[1] = d lik / d sigma; Fb (nullable) receives Fbar
-__global__ __launch_bounds__(256, 2) void k_latent_gp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
-                                                         const double *__restrict__ Z, int k, int ldz, LatentHead lh,
-                                                         double *__restrict__ out, double *__restrict__ Fb, int ldfb,
-                                                         double *__restrict__ F, int ldf, double *__restrict__ Zb, int ldzb,
-                                                         double *__restrict__ W, double *__restrict__ R, size_t ld, double alpha,
-                                                         GradEll el, int n_ell, double *__restrict__ grad, int *info_out, int *info_w,
-                                                         ExpC ec, double *__restrict__ stage, int *done, int seq)
-{
-    exact_gp_vjp_small_body<true>(X, n, ldx, p, diag_add, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, W, R, ld, alpha, el, n_ell, grad, info_out,
-                                  info_w, ec, stage, done, seq, lh, out);
-}
-
-// The CENTRED latent GP (models/heteroscedastic_centered.stan:24-34; gpmi_centered_gp_lp_grad) by ONE workgroup for n <= 256,
-// D <= GPMI_MAXD, k <= CEN_KMAX: the k latent columns are parameters with the GP as their prior.  logml_grad_small_body with k
-// augmented rows instead of one:
-//   build; F^T rides as rows n .. n + k - 1 of the partial factorisation and comes out as Z^T, U = L^-T rides along
-//   (small_potrf_partial<true>); sum log L_ii and sum_c z_c'z_c by the tree of k_logml_partial;
-//   a_c = U z_c for all columns in one pass over U (thread = row); the head on this thread's row of F, Fgrad = Fbar - a;
-//   Sigma^-1 = U U^T tile by tile, contracted in registers with g_ij = 1/2 (sum_c a_ic a_jc - k Sigma^-1_ij) against dSigma/dtheta.
-// W: n + k rows; out (4), Fg (n x k, ldfg), grad (1 + n_ell) and info_out may be host-mapped (stage != null: n (D + k + m)
-// doubles of device scratch receive X, F and Y in one coalesced pass).  The gradient is finished on the device.
-constexpr int CEN_KMAX = GPMI_CEN_KMAX;
-__global__ __launch_bounds__(256, 2) void k_centered_gp_small(const double *__restrict__ X, int n, int ldx, SeParams p, double diag_add,
-                                                           const double *__restrict__ F, int k, int ldf, LatentHead lh,
-                                                           double *__restrict__ out, double *__restrict__ Fg, int ldfg,
-                                                           double *__restrict__ W, double *__restrict__ U, size_t ld, double alpha,
-                                                           GradEll el, int n_ell, double *__restrict__ grad, int *info_out,
-                                                           int *info_w, ExpC ec, double *__restrict__ stage, int *done, int seq)
-{
-    GPMI_SMALL_LDS
-    int tid = threadIdx.x;
-    const bool head = lh.family != GPMI_LIK_NONE;
-    if (stage) {   // host-mapped X, F, Y: one coalesced pass into device memory
-        const int nx = n * p.D, nf = n * k, ny = head ? n * lh.m : 0;
-        for (int e = tid; e < nx + nf + ny; e += 256) {
-            if (e < nx) {
-                const int d = e / n, i = e - d * n;
-                stage[e] = X[(size_t)i + (size_t)d * ldx];
-            } else if (e < nx + nf) {
-                const int c = (e - nx) / n, i = e - nx - c * n;
-                stage[e] = F[(size_t)i + (size_t)c * ldf];
-            } else {
-                const int c = (e - nx - nf) / n, i = e - nx - nf - c * n;
-                stage[e] = lh.Y[(size_t)i + (size_t)c * lh.ldy];
-            }
-        }
-        __syncthreads();
-        X = stage;
-        F = stage + nx;
-        ldx = ldf = n;
-    }
-    if (tid == 0) *info_w = 0;
-    SmallSe se;
-    se.a2 = p.a2;
-    se.D = p.D;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = p.inv_ell[d];
-    {
-        double *xs = &smem[0][0][0][0];
-#pragma unroll
-        for (int d = 0; d < GPMI_MAXD; ++d)
-            if (d < se.D)
-                for (int i = tid; i < n; i += 256) xs[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-        __syncthreads();
-        for (int row0 = 0; row0 < n; row0 += SE_TR)
-            for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC) {
-                switch (se.D) {
-                case 1: se_cov_tile<1, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 2: se_cov_tile<2, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                case 3: se_cov_tile<3, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                default: se_cov_tile<0, true>(xs, n, n, xs, n, n, se, diag_add, 1, 1, W, ld, 1, ec, row0, col0); break;
-                }
-            }
-    }
-    for (int c = 0; c < k; ++c)   // F^T as rows n .. n + k - 1
-        for (int j = tid; j < n; j += 256) W[(size_t)(n + c) + (size_t)j * ld] = F[(size_t)j + (size_t)c * ldf];
-    {   // U = I (as logml_grad_small_body)
-        const int rp = 2 * (tid & 127), cp = tid >> 7;
-        if (rp < n)
-            for (int j = cp; j < n; j += 2) *reinterpret_cast<double2 *>(U + (size_t)rp + (size_t)j * ld) = make_double2(0.0, 0.0);
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) U[(size_t)i * (ld + 1)] = 1.0;
-    }
-    __syncthreads();
-    small_potrf_partial<true>(smem, s_F, s_aux, W, ld, n + k, n, n, info_w, k == 1, U);
-    __syncthreads();
-    asm volatile("" : "+v"(tid));
-    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // the packed factors are no longer needed: s_F holds the scaled coordinates, A = Sigma^-1 F and Z, k n doubles each
-    double *xg = s_F, *s_av = s_F + 2048, *s_z = s_F + 4096;
-    double *s_a = s_aux, *s_b = s_aux + 256;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d)
-        if (d < se.D)
-            for (int i = tid; i < n; i += 256) xg[i + d * n] = __dmul_rn(X[(size_t)i + (size_t)d * ldx], se.inv_ell[d]);
-    {   // value: one slice (n <= 256), the tree of k_logml_partial; the squares of a row's k entries of Z in column order
-        double a = 0.0, b = 0.0;
-        if (tid < n) {
-            a = log(W[(size_t)tid * (ld + 1)]);
-            for (int c = 0; c < k; ++c) {
-                const double z = W[(size_t)(n + c) + (size_t)tid * ld];
-                s_z[c * n + tid] = z;
-                b += z * z;
-            }
-        }
-        s_a[tid] = a;
-        s_b[tid] = b;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if (tid < st) {
-                s_a[tid] += s_a[tid + st];
-                s_b[tid] += s_b[tid + st];
-            }
-            __syncthreads();
-        }
-    }
-    const double sum_log = s_a[0], zz = s_b[0];
-    __syncthreads();   // (s_a, s_b are written again below)
-    // A = U Z (U upper triangular: the columns left of a wave's first row are zero): one pass over U for all k columns,
-    // sixteen loads in flight per round trip
-    double av[CEN_KMAX];
-#pragma unroll
-    for (int c = 0; c < CEN_KMAX; ++c) av[c] = 0.0;
-    {
-        const int ir = tid < n ? tid : n - 1;
-        for (int j0 = tid & ~63; j0 < n; j0 += 16) {
-            double u[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int j = j0 + q < n ? j0 + q : n - 1;
-                u[q] = U[(size_t)ir + (size_t)j * ld];
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (j0 + q < n)
-#pragma unroll
-                    for (int c = 0; c < CEN_KMAX; ++c)
-                        if (c < k) av[c] = fma(u[q], s_z[c * n + j0 + q], av[c]);
-        }
-    }
-    if (tid < n)
-#pragma unroll
-        for (int c = 0; c < CEN_KMAX; ++c)
-            if (c < k) s_av[c * n + tid] = av[c];
-    // the head on this thread's row of F; Fgrad = Fbar - A; lik and d lik / d sigma by a butterfly inside every wave and the
-    // four wave sums added in wave order
-    {
-        double red0 = 0.0, red1 = 0.0, fb0 = 0.0, fb1 = 0.0;
-        if (tid < n) {
-            if (head) {
-                const LatentHead hd{lh.family, stage ? stage + n * (p.D + k) : lh.Y, lh.m, stage ? n : lh.ldy, lh.sigma, lh.log_sigma};
-                latent_head_row(hd, F[tid], k > 1 ? F[(size_t)tid + (size_t)ldf] : 0.0, hd.Y + tid, red0, red1, fb0, fb1);
-            }
-#pragma unroll
-            for (int c = 0; c < CEN_KMAX; ++c)
-                if (c < k) {
-                    const double fb = c == 0 ? fb0 : (c == 1 ? fb1 : 0.0);
-                    Fg[(size_t)tid + (size_t)c * ldfg] = info ? __builtin_nan("") : fb - av[c];
-                }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            red0 += __shfl_xor(red0, off, 64);
-            red1 += __shfl_xor(red1, off, 64);
-        }
-        if ((tid & 63) == 0) {
-            s_b[(tid >> 6) * 2] = red0;
-            s_b[(tid >> 6) * 2 + 1] = red1;
-        }
-    }
-    __syncthreads();   // (also: every row of A is in s_av, the coordinates in xg)
-    const double lik = ((s_b[0] + s_b[2]) + s_b[4]) + s_b[6], dsig = ((s_b[1] + s_b[3]) + s_b[5]) + s_b[7];
-    asm volatile("" : "+v"(tid));
-    // Sigma^-1 = U U^T tile by tile (lower tiles; only the columns >= the tile row's first), contracted where it is produced
-    double acc[1 + GPMI_MAXD];
-#pragma unroll
-    for (int q = 0; q < 1 + GPMI_MAXD; ++q) acc[q] = 0.0;
-    const double a2 = se.a2, kd = (double)k;
-    auto kinv_tiles = [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;   // compile-time dimension count (0: se.D at run time, <= GPMI_MAXD)
-        const int Dn = DT ? DT : se.D;
-        constexpr int DH = DT ? DT : 1;
-        double xm[4][DH], am[4], xn[DH], an = 0.0;
-        int mm[4], ncur = 0;
-        bool okn = false;
-        auto contract = make_epi3(
-            [&](int tm, int m, bool ok) {
-                mm[tm] = ok ? m : -1;           // a row outside the matrix lies above every column: weight 0
-                const int mc = ok ? m : 0;
-                am[tm] = s_av[mc];
-                if constexpr (DT != 0) {
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) xm[tm][d] = xg[mc + d * n];
-                }
-            },
-            [&](int nn, bool ok) {
-                ncur = ok ? nn : 0;
-                okn = ok;
-                an = s_av[ncur];
-                if constexpr (DT != 0) {
-#pragma unroll
-                    for (int d = 0; d < DT; ++d) xn[d] = xg[ncur + d * n];
-                }
-            },
-            [&](double kinv, int tm) {
-                double e = 0.0, r2[GPMI_MAXD];
-                const int mc = mm[tm] < 0 ? 0 : mm[tm];
-#pragma unroll
-                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) {
-                    double r;
-                    if constexpr (DT != 0) r = xm[tm][d] - xn[d];
-                    else r = d < Dn ? xg[mc + d * n] - xg[ncur + d * n] : 0.0;
-                    r2[d] = r * r;
-                    e += r2[d];
-                }
-                const double kse = a2 * exp_nonpos(-0.5 * e, ec);
-                double aa = am[tm] * an;        // sum_c a_mc a_nc, columns in index order (the first pair from registers)
-                for (int c = 1; c < k; ++c) aa += s_av[c * n + mc] * s_av[c * n + ncur];
-                const double g = 0.5 * (aa - kd * kinv);
-                const bool lower = okn && ncur <= mm[tm];
-                const double cc = lower ? ((ncur == mm[tm]) ? 1.0 : 2.0) * g * kse : 0.0;
-                acc[0] += cc;
-#pragma unroll
-                for (int d = 0; d < (DT ? DT : GPMI_MAXD); ++d) acc[1 + d] += cc * r2[d];
-            });
-        for (int ti = 0; ti * GT < n; ++ti)
-            for (int tj = 0; tj <= ti; ++tj) {
-                const int k0 = ti * GT;
-                gemm_tile<3>(smem, U + (size_t)k0 * ld, ld, U + (size_t)k0 * ld, ld, W, ld, n, n, n - k0, ti, tj, 0, (int)threadIdx.x,
-                             contract);
-                __syncthreads();
-            }
-    };
-    switch (se.D) {
-    case 1: kinv_tiles(ic<1>{}); break;
-    case 2: kinv_tiles(ic<2>{}); break;
-    case 3: kinv_tiles(ic<3>{}); break;
-    default: kinv_tiles(ic<0>{}); break;
-    }
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d)   // sums over UNSCALED squared differences (layout of k_grad_partial)
-        acc[1 + d] = (d < se.D) ? acc[1 + d] / (se.inv_ell[d] * se.inv_ell[d]) : 0.0;
-    // fixed-shape reduction: butterfly inside every wave, the four wave sums added in wave order
-    double *s_r = s_aux;
-#pragma unroll
-    for (int q = 0; q < 1 + GPMI_MAXD; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((tid & 63) == 0) s_r[(tid >> 6) * (1 + GPMI_MAXD) + q] = v;
-    }
-    __syncthreads();
-    if (tid < 1 + GPMI_MAXD) {
-        constexpr int S = 1 + GPMI_MAXD;
-        s_r[4 * S + tid] = ((s_r[tid] + s_r[S + tid]) + s_r[2 * S + tid]) + s_r[3 * S + tid];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double nan = __builtin_nan("");
-        if (info)
-            for (int q = 0; q <= n_ell; ++q) grad[q] = nan;
-        else
-            gpmi_grad_from_sums(s_r + 4 * (1 + GPMI_MAXD), se.D, alpha, el.ell, n_ell, grad);
-        out[0] = info ? nan : (-0.5 * zz - kd * sum_log) + lik;
-        out[1] = info ? nan : dsig;
-        out[2] = info ? nan : sum_log;
-        out[3] = info ? nan : zz;
-        *info_out = info;
-    }
-    small_signal_done(done, seq);
-}
-
-// rbf_cov_chol (covariance.cpp:9-47) by ONE workgroup for n <= 128 (test_interpolate.R:5 runs it at N = 100, P = 10 times):
-// Sigma_ij = exp(-(x_i - x_j)^2 / (2 l^2)) + 1e-10 [i == j], L = chol(Sigma), and the forward-mode tangent
-// dL/dl = L Phi(L^-1 Sdot L^-T), Sdot_ij = Sigma_ij (x_i - x_j)^2 / l^3, Phi = lower triangle with halved diagonal --
-// the launch chain of rbf_cov_chol_core (build, factor, copy, tangent build, two panel solves, two transposes, mask, product:
-// ~12 launches) with the same device functions back to back.  Workgroup g handles length-scale ls[g] and writes L (upper
-// zeroed) and dL/dl (lower; its upper triangle exact zeros) to Lout + g ostride, dLout + g ostride (leading dimension ldo;
-// device or host-mapped memory).  Workspace per workgroup: three slices of small_ws_layout(n) (Sigma / L, S, S2).
-struct RbfBatch {
-    double l[64];
-};
-__global__ __launch_bounds__(256, 2) void k_rbf_cov_chol_small(const double *__restrict__ x, int n, RbfBatch ls, double *__restrict__ Wall,
-                                                            size_t wstride, size_t ld, double *__restrict__ Lout,
-                                                            double *__restrict__ dLout, size_t ostride, size_t ldo, int *info_out,
-                                                            int *info_w, ExpC ec, double *__restrict__ stage)
-{
-    GPMI_SMALL_LDS
-    const int g = blockIdx.x, tid = threadIdx.x;
-    const double l = ls.l[g];
-    double *W = Wall + (size_t)g * 3 * wstride, *S = W + wstride, *S2 = S + wstride;
-    double *Lo = Lout + (size_t)g * ostride, *dLo = dLout + (size_t)g * ostride;
-    int *iw = info_w + g;
-    if (stage) {   // x host-mapped: one copy per workgroup
-        double *st = stage + (size_t)g * n;
-        for (int i = tid; i < n; i += 256) st[i] = x[i];
-        __syncthreads();
-        x = st;
-    }
-    if (tid == 0) *iw = 0;
-    SmallSe se;
-    se.a2 = 1.0;
-    se.D = 1;
-#pragma unroll
-    for (int d = 0; d < GPMI_MAXD; ++d) se.inv_ell[d] = 1.0 / l;
-    double *xs = &smem[0][0][0][0];
-    for (int i = tid; i < n; i += 256) xs[i] = __dmul_rn(x[i], se.inv_ell[0]);
-    __syncthreads();
-    for (int row0 = 0; row0 < n; row0 += SE_TR)
-        for (int col0 = 0; col0 < row0 + SE_TR && col0 < n; col0 += SE_TC)
-            se_cov_tile<1, true>(xs, n, n, xs, n, n, se, 1e-10, 1, 1, W, ld, 1, ec, row0, col0);
-    // Sdot, full (the arithmetic of k_rbf_dsigma), thread = row
-    for (int i = tid; i < n; i += 256) {
-        const double xi = x[i];
-        for (int j = 0; j < n; ++j) {
-            const double r = xi - x[j], r2 = r * r;
-            S[(size_t)i + (size_t)j * ld] = exp(-r2 / (2 * l * l)) * r2 / (l * l * l);
-        }
-    }
-    __syncthreads();
-    const int nblk = (n + 15) >> 4;
-    if (n == GPMI_NB) potrf_diag4_body<false, true>(&smem[0][0][0][0], W, ld, n, s_F, iw, 0, 8, tid);
-    else potrf_diag4_body<false, false>(&smem[0][0][0][0], W, ld, n, s_F, iw, 0, nblk, tid);
-    __syncthreads();
-    // (the element-wise passes below keep eight loads in flight per round trip: a loop with one dependent load per iteration
-    // is a chain of n memory latencies -- 100 us per pass at n = 100)
-    // L out, and its upper triangle zeroed in place: W is the A operand of the last product
-    for (int i = tid; i < n; i += 256)
-        for (int j0 = 0; j0 < n; j0 += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int j = j0 + q < n ? j0 + q : n - 1;
-                v[q] = W[(size_t)i + (size_t)j * ld];
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int j = j0 + q;
-                if (j < n) {
-                    if (j > i) W[(size_t)i + (size_t)j * ld] = 0.0;
-                    Lo[(size_t)i + (size_t)j * ldo] = (j <= i) ? v[q] : 0.0;
-                }
-            }
-        }
-    auto solve_rows = [&](double *A) {   // A <- A L^-T, all n rows, 64 per round
-        for (int rb = 0; rb < n; rb += 64) {
-            const int r = rb + (tid >> 6) * 16 + (tid & 15);
-            if (n == GPMI_NB && rb + 64 <= n) trsm_panel_body<true>(s_F, A, ld, r, true, n, tid);
-            else trsm_panel_body<false>(s_F, A, ld, r, r < n, n, tid);
-        }
-        __syncthreads();
-    };
-    solve_rows(S);                                                  // S = Sdot L^-T
-    for (int i = tid; i < n; i += 256)                              // S2 = S^T = L^-1 Sdot
-        for (int j0 = 0; j0 < n; j0 += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = S[(size_t)(j0 + q < n ? j0 + q : n - 1) + (size_t)i * ld];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (j0 + q < n) S2[(size_t)i + (size_t)(j0 + q) * ld] = v[q];
-        }
-    __syncthreads();
-    solve_rows(S2);                                                 // S2 = M = L^-1 Sdot L^-T
-    // B operand of the product: row j, column k holds Phi(M)[k][j]  (k >= j; the diagonal halved)
-    for (int j = tid; j < n; j += 256)
-        for (int k0 = 0; k0 < n; k0 += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = S2[(size_t)(k0 + q < n ? k0 + q : n - 1) + (size_t)j * ld];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int k = k0 + q;
-                if (k < n) S[(size_t)j + (size_t)k * ld] = (k > j) ? v[q] : ((k == j) ? 0.5 * v[q] : 0.0);
-            }
-        }
-    __syncthreads();
-    gemm_tile<2>(smem, W, ld, S, ld, dLo, ldo, n, n, n, 0, 0, 0, tid);   // dL = L Phi (n <= 128: one tile)
-    __syncthreads();
-    if (tid == 0) info_out[g] = __hip_atomic_load(iw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// stream-ordered upload of up to PUT_MAX doubles that travel as kernel arguments (no staging buffer whose reuse would
-// have to be fenced against an earlier asynchronous call)
-constexpr int PUT_MAX = 480;
-struct PutArgs {
-    double v[PUT_MAX];
-};
-__global__ __launch_bounds__(256) void k_put_doubles(PutArgs a, double *__restrict__ dst, int count)
-{
-    for (int i = threadIdx.x; i < count; i += 256) dst[i] = a.v[i];
-}
-
-// the factorisation alone (launch_potrf_partial at small sizes: posteriors, rbf_cov_chol, ...)
-__global__ __launch_bounds__(256, 2) void k_potrf_small(double *__restrict__ W, size_t ld, int M, int ncol, int nfac, int *info)
-{
-    GPMI_SMALL_LDS
-    small_potrf_partial(smem, s_F, s_aux, W, ld, M, ncol, nfac, info, false);
-}
-#undef GPMI_SMALL_LDS
-
 // Packed factors (Fpack) of an ALREADY factored diagonal block: -L tiles in fragment
 // order and the inverse of every 16x16 diagonal tile.  Used by solves against a given L.
 __global__ __launch_bounds__(512) void k_pack_factors(const double *__restrict__ L11, size_t ldl,
@@ -3718,32 +1237,6 @@ __global__ __launch_bounds__(256) void k_probe_peak(double *sink, int iters)
 // ---------------------------------------------------------------------------
 // host-side drivers
 // ---------------------------------------------------------------------------
-// the small kernels use more dynamic workgroup memory than the default limit: raise it once per device
-static void small_lds_attr()
-{
-    static bool done[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || done[dev]) return;
-    const int bytes = SMALL_LDS_DOUBLES * (int)sizeof(double);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_small_batch_ard), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_small_batch_dev), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sample_derivs_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gp_condition_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gp_predict_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_exact_gp_vjp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_latent_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_centered_gp_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_cov_chol_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    const int gbytes = SMALL_GRAD_LDS_DOUBLES * (int)sizeof(double);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_grad_small), hipFuncAttributeMaxDynamicSharedMemorySize, gbytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_logml_grad_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, gbytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_potrf_small), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done[dev] = true;
-}
-
 void gpmi_tuning_defaults(gpmi_tuning *t)
 {
     t->syrk_order = 2;
@@ -4066,8 +1559,7 @@ int launch_potrf_partial(gpmi_ctx *c, double *W, size_t ld, int M, int ncol, int
     // small matrices: the whole partial factorisation in ONE workgroup of one launch (k_potrf_small) instead of a
     // chain of latency-bound launches (tune.small_m; callers that keep the packed factors take the blocked path)
     if (!Fpack_all && M <= c->tune.small_m && M > 0 && nfac > 0) {
-        small_lds_attr();
-        hipLaunchKernelGGL(k_potrf_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), c->stream, W, ld, M, ncol, nfac, d_info);
+        launch_potrf_small(c->stream, W, ld, M, ncol, nfac, d_info);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return gpmi_fail(GPMI_EHIP, "potrf launch failed: %s", hipGetErrorString(e));
         return 0;
@@ -4299,223 +1791,6 @@ int launch_trsv_lower(hipStream_t s, const double *L, size_t ldl, int n, const d
     return 0;
 }
 
-// ---- small-N evaluations: one workgroup each ------------------------------------------------
-// workspace slice of one n-point problem: leading dimension and stride (doubles) between consecutive slices
-void small_ws_layout(int n, size_t *ld, size_t *stride)
-{
-    *ld = (size_t)(((n + 1 + 15) / 16) * 16 + 16);
-    *stride = *ld * (size_t)(n + 1) + 256;  // tile loads may over-read rows past the end of the last column
-}
-
-void launch_logml_small(hipStream_t s, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
-                        double *W, size_t ld, double *d_out3, int *d_info_out, int *d_info_work, double *stage, int *done, int seq)
-{
-    small_lds_attr();
-    hipLaunchKernelGGL(k_logml_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, dX, n, ldx, dy, p, diag_add, W, ld, d_out3,
-                       d_info_out, d_info_work, h_exp, stage, done, seq);
-}
-
-// G <= GPMI_SMALL_PTS points (alpha, rho, sigma) in ONE launch of G workgroups; Wall: G slices (small_ws_layout)
-void launch_logml_small_batch(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
-                              const double *rho, const double *sigma, int G, double jitter, double *Wall, double *d_out3,
-                              int *d_info_out, int *d_info_work)
-{
-    static_assert(SMALL_PTS == GPMI_SMALL_PTS, "batch size of the small-N grid launch");
-    SmallBatch b;
-    for (int g = 0; g < G; ++g) {
-        b.a2[g] = alpha[g] * alpha[g];
-        b.inv_rho[g] = 1.0 / rho[g];
-        b.diag[g] = sigma[g] * sigma[g] + jitter;
-    }
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_logml_small_batch, dim3(G), 256, SMALL_LDS_DOUBLES * sizeof(double), s, dX, n, ldx, D, dy, b, Wall, stride, ld, d_out3, d_info_out,
-                       d_info_work, h_exp);
-}
-
-// G <= GPMI_SMALL_PTS_ARD points with a length-scale per dimension: ell is G x D, point-major
-void launch_logml_small_batch_ard(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
-                                  const double *ell, const double *sigma, int G, double jitter, double *Wall, double *d_out3,
-                                  int *d_info_out, int *d_info_work)
-{
-    static_assert(SMALL_PTS_ARD == GPMI_SMALL_PTS_ARD, "batch size of the small-N ARD grid launch");
-    SmallBatchArd b;
-    for (int g = 0; g < G; ++g) {
-        b.a2[g] = alpha[g] * alpha[g];
-        b.diag[g] = sigma[g] * sigma[g] + jitter;
-        for (int d = 0; d < GPMI_MAXD; ++d) b.inv_ell[g][d] = d < D ? 1.0 / ell[(size_t)g * D + d] : 0.0;
-    }
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_logml_small_batch_ard, dim3(G), 256, SMALL_LDS_DOUBLES * sizeof(double), s, dX, n, ldx, D, dy, b, Wall,
-                       stride, ld, d_out3, d_info_out, d_info_work, h_exp);
-}
-
-// G points (any number) whose parameters are uploaded to d_par (G * (2 + GPMI_MAXD) doubles) in stream order; ell: one
-// length-scale per point (n_ell == 1) or D per point (point-major); Wall: G slices (small_ws_layout)
-void launch_logml_small_batch_dev(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
-                                  const double *ell, int n_ell, const double *sigma, int G, double jitter, double *d_par,
-                                  double *Wall, double *d_out3, int *d_info_out, int *d_info_work)
-{
-    static_assert(PUT_MAX % SMALL_PAR == 0, "whole points per upload");
-    PutArgs a;
-    for (int g0 = 0; g0 < G; g0 += PUT_MAX / SMALL_PAR) {
-        const int gc = (G - g0 < PUT_MAX / SMALL_PAR) ? G - g0 : PUT_MAX / SMALL_PAR;
-        for (int g = 0; g < gc; ++g) {
-            double *q = a.v + g * SMALL_PAR;
-            q[0] = alpha[g0 + g] * alpha[g0 + g];
-            q[1] = sigma[g0 + g] * sigma[g0 + g] + jitter;
-            for (int d = 0; d < GPMI_MAXD; ++d)
-                q[2 + d] = d < D ? 1.0 / (n_ell == 1 ? ell[g0 + g] : ell[(size_t)(g0 + g) * D + d]) : 0.0;
-        }
-        hipLaunchKernelGGL(k_put_doubles, dim3(1), 256, 0, s, a, d_par + (size_t)g0 * SMALL_PAR, gc * SMALL_PAR);
-    }
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_logml_small_batch_dev, dim3(G), 256, SMALL_LDS_DOUBLES * sizeof(double), s, dX, n, ldx, D, dy, d_par, Wall,
-                       stride, ld, d_out3, d_info_out, d_info_work, h_exp);
-}
-
-// value + gradient sums by one workgroup per point: W holds, per point, two slices of small_ws_layout (W, then U)
-void launch_logml_grad_small(hipStream_t s, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
-                             double *W, double *d_res, int *d_info_out, int *d_info_work, double *stage, int *done, int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_logml_grad_small, dim3(1), 256, SMALL_GRAD_LDS_DOUBLES * sizeof(double), s, dX, n, ldx, dy, p, diag_add, W, ld,
-                       W + stride, d_res, d_info_out, d_info_work, h_exp, stage, done, seq);
-}
-
-void launch_logml_grad_small_batch(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
-                                   const double *rho, const double *sigma, int G, double jitter, double *Wall, double *d_res,
-                                   int *d_info_out, int *d_info_work, double *stage, int *done, int seq, int *arrive)
-{
-    SmallBatch b;
-    for (int g = 0; g < G; ++g) {
-        b.a2[g] = alpha[g] * alpha[g];
-        b.inv_rho[g] = 1.0 / rho[g];
-        b.diag[g] = sigma[g] * sigma[g] + jitter;
-    }
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_logml_grad_small_batch, dim3(G), 256, SMALL_GRAD_LDS_DOUBLES * sizeof(double), s, dX, n, ldx, D, dy, b, Wall,
-                       2 * stride, stride, ld, d_res, d_info_out, d_info_work, h_exp, stage, done, seq, arrive);
-}
-
-// B draws by one workgroup each; Wall: B slices of small_ws_layout(n + m); dY: n x B, dZ, draws, mus: m x B (packed); d_par: 3 B
-// doubles, d_info_work: 2 B ints
-void launch_sample_derivs_small_batch(hipStream_t s, const double *dt, int n, const double *dts, int m, const double *dY,
-                                      const double *params /* host: (l, a, sy) per draw */, int B, double jitter, const double *dZ,
-                                      double *d_par, double *Wall, double *d_draws, double *d_mus, int *d_status, int *d_info_work)
-{
-    static_assert(PUT_MAX % 3 == 0, "whole draws per upload");
-    PutArgs a;
-    for (int g0 = 0; g0 < B; g0 += PUT_MAX / 3) {
-        const int gc = (B - g0 < PUT_MAX / 3) ? B - g0 : PUT_MAX / 3;
-        for (int q = 0; q < 3 * gc; ++q) a.v[q] = params[3 * (size_t)g0 + q];
-        hipLaunchKernelGGL(k_put_doubles, dim3(1), 256, 0, s, a, d_par + 3 * (size_t)g0, 3 * gc);
-    }
-    size_t ld, stride;
-    small_ws_layout(n + m, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_sample_derivs_small_batch, dim3(B), 256, SMALL_LDS_DOUBLES * sizeof(double), s, dt, n, dts, m, dY, d_par, jitter, dZ,
-                       Wall, stride, ld, d_draws, d_mus, d_status, d_info_work);
-}
-
-void launch_gp_condition_small(hipStream_t s, const double *t, int n, const double *ts, int m, const double *y, int kindK, int kindS,
-                               int kindSS, int compat, double a2, double l2, double s2, double jitter, double *W, double *Kn, size_t ldo,
-                               double *mn, int *info_out, int *d_info_work, double *stage, int *done, int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n + m, &ld, &stride);
-    small_lds_attr();
-    CondArgs q{kindK, kindS, kindSS, compat, a2, l2, s2, jitter};
-    hipLaunchKernelGGL(k_gp_condition_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, t, n, ts, m, y, q, W, ld, Kn, ldo, mn,
-                       info_out, d_info_work, stage, done, seq);
-}
-
-void launch_gp_predict_small(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const double *y,
-                             const SeParams &p, double diag_add, double *W, double *mean, double *var, int *info_out, int *d_info_work,
-                             int *done, int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n + m, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_gp_predict_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, Xs, m, ldxs, y, p, diag_add, W,
-                       ld, mean, var, info_out, d_info_work, h_exp, done, seq);
-}
-
-void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,
-                           double *W, double *f, int *info_out, int *d_info_work, double *stage, int *done, int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_exact_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, z, p, diag_add, W, ld, f, info_out,
-                       d_info_work, h_exp, stage, done, seq);
-}
-
-// one workgroup; W: 4 slices of small_ws_layout(n) -- the covariance / factor, then [V | U | V] (3 n columns of the same ld)
-void launch_exact_gp_vjp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *Z, int k,
-                               int ldz, const double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb, double *W, double alpha,
-                               const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage, int *done,
-                               int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    const GradEll el = grad_ell(ell, n_ell);
-    hipLaunchKernelGGL(k_exact_gp_vjp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, Fb,
-                       ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
-}
-
-// the same with a likelihood head between the product and the sweep (k <= 2); stage != null: n (D + k + m) doubles
-void launch_latent_gp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *Z, int k,
-                            int ldz, const LatentHead &lh, double *out, double *Fb, int ldfb, double *F, int ldf, double *Zb, int ldzb,
-                            double *W, double alpha, const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work,
-                            double *stage, int *done, int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    const GradEll el = grad_ell(ell, n_ell);
-    hipLaunchKernelGGL(k_latent_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, Z, k, ldz, lh, out,
-                       Fb, ldfb, F, ldf, Zb, ldzb, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done,
-                       seq);
-}
-
-// one workgroup; W: 2 slices of small_ws_layout(n + k - 1) -- the covariance / factor with the k rows of F^T below, then U
-void launch_centered_gp_small(hipStream_t s, const double *X, int n, int ldx, const SeParams &p, double diag_add, const double *F, int k,
-                              int ldf, const LatentHead &lh, double *out, double *Fg, int ldfg, double *W, double alpha,
-                              const double *ell, int n_ell, double *grad, int *info_out, int *d_info_work, double *stage, int *done,
-                              int seq)
-{
-    size_t ld, stride;
-    small_ws_layout(n + k - 1, &ld, &stride);
-    small_lds_attr();
-    const GradEll el = grad_ell(ell, n_ell);
-    hipLaunchKernelGGL(k_centered_gp_small, dim3(1), 256, SMALL_LDS_DOUBLES * sizeof(double), s, X, n, ldx, p, diag_add, F, k, ldf, lh,
-                       out, Fg, ldfg, W, W + stride, ld, alpha, el, n_ell, grad, info_out, d_info_work, h_exp, stage, done, seq);
-}
-
-// P <= 64 length-scales, one workgroup each (n <= 128); Wall: 3 P slices of small_ws_layout(n)
-void launch_rbf_cov_chol_small(hipStream_t s, const double *x, int n, const double *ls, int P, double *Wall, double *Lout, double *dLout,
-                               size_t ostride, size_t ldo, int *info_out, int *d_info_work, double *stage)
-{
-    RbfBatch b;
-    for (int p = 0; p < P; ++p) b.l[p] = ls[p];
-    size_t ld, stride;
-    small_ws_layout(n, &ld, &stride);
-    small_lds_attr();
-    hipLaunchKernelGGL(k_rbf_cov_chol_small, dim3(P), 256, SMALL_LDS_DOUBLES * sizeof(double), s, x, n, b, Wall, stride, ld, Lout, dLout,
-                       ostride, ldo, info_out, d_info_work, h_exp, stage);
-}
-
 void launch_pack_factors(hipStream_t s, const double *L, size_t ldl, int n, double *Fpack_all)
 {
     for (int k = 0; k < n; k += GPMI_NB) {
@@ -4566,12 +1841,18 @@ int probe_fused_read(hipStream_t s, unsigned long long *out5)
     return hipMemcpyToSymbol(HIP_SYMBOL(g_fz), z, sizeof z) != hipSuccess;
 }
 
+int probe_small_body_read(hipStream_t s, unsigned long long *out8);
+// the bodies of both translation units: the blocked launches' (this file's g_body) and the one-workgroup kernels'
 int probe_body_read(hipStream_t s, unsigned long long *out8)
 {
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (hipStreamSynchronize(s) != hipSuccess) return 1;
     if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_body), 8 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_body), z, sizeof z) != hipSuccess;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_body), z, sizeof z) != hipSuccess) return 1;
+    unsigned long long sm[8];
+    if (probe_small_body_read(s, sm)) return 1;
+    for (int i = 0; i < 8; ++i) out8[i] += sm[i];
+    return 0;
 }
 
 int probe_clock_read(hipStream_t s, int reset, unsigned long long *out3)

@@ -4192,15 +4192,17 @@ extern "C" int gpmi_probe_syrk(gpmi_ctx *c, int m, int k, int reps, double *ms)
     return 0;
 }
 
-int probe_fused_read(hipStream_t s, unsigned long long *out5);
+int probe_fused_read(hipStream_t s, unsigned long long *out5);   // chol_kernels.hip's stamp array
+int probe_small_read(hipStream_t s, unsigned long long *out8);   // small_kernels.hip's
 // out5: block 0 of the fused in-block launches since the last call: cycles in its 64 x 64 sub-tile, in the
-// wait for the other two sub-tiles, in the diagonal-block body; launches; sum of K
+// wait for the other two sub-tiles, in the diagonal-block body; launches; sum of K.  The eight phase stamps of the
+// one-workgroup kernels since the last call are added in (tools/grad_phase_probe.py reads all eight through this call)
 extern "C" int gpmi_probe_fused(gpmi_ctx *c, double *out5)
 {
     ENTER(c);
-    unsigned long long h[8];
-    if (probe_fused_read(c->stream, h)) return gpmi_fail(GPMI_EHIP, "probe read failed");
-    for (int i = 0; i < 8; ++i) out5[i] = (double)h[i];   // [5..7]: body cycles, sub-tile cycles, launches of the K = 128 leaf launches
+    unsigned long long h[8], hs[8];
+    if (probe_fused_read(c->stream, h) || probe_small_read(c->stream, hs)) return gpmi_fail(GPMI_EHIP, "probe read failed");
+    for (int i = 0; i < 8; ++i) out5[i] = (double)h[i] + (double)hs[i];   // [5..7]: body cycles, sub-tile cycles, launches of the K = 128 leaf launches
     return 0;
 }
 
@@ -4222,7 +4224,7 @@ extern "C" int gpmi_probe_small(gpmi_ctx *c, double *out6)
 {
     ENTER(c);
     unsigned long long h[8];
-    if (probe_fused_read(c->stream, h)) return gpmi_fail(GPMI_EHIP, "probe read failed");
+    if (probe_small_read(c->stream, h)) return gpmi_fail(GPMI_EHIP, "probe read failed");
     for (int i = 0; i < 6; ++i) out6[i] = (double)h[i];
     return 0;
 }

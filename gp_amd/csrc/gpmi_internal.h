@@ -206,7 +206,7 @@ void launch_gp_blend(hipStream_t s, const double *M, size_t ld, int n, int P, co
 void launch_gp_lookup(hipStream_t s, double *M, size_t ld, int n, int P, const double *lu, const int *perm);
 void launch_phi_mask(hipStream_t s, double *B, size_t ld, int n); // keep upper, halve diag, zero strict lower
 
-// ---- kernel launchers (chol_kernels.hip) -----------------------------------
+// ---- kernel launchers (chol_kernels.hip): the blocked factorisation, solves and products --------------------
 // Factor the first nfac columns of the M x ncol lower-stored matrix in W (right-looking,
 // blocked); rows nfac..M-1 become L21 / the Schur complement of the trailing block.
 int launch_potrf_partial(gpmi_ctx *c, double *W, size_t ld, int M, int ncol, int nfac, int *d_info,
@@ -222,6 +222,9 @@ void launch_gemm_nt(const gpmi_ctx *c, hipStream_t s, const double *A, size_t ld
                     double *C, size_t ldc, int M, int N, int K, int accumulate_minus);
 void launch_syrk_uut(const gpmi_ctx *c, hipStream_t s, const double *U, size_t ldu, double *C, size_t ldc, int n);
 void launch_pack_factors(hipStream_t s, const double *L, size_t ldl, int n, double *Fpack_all);
+// ---- kernel launchers (small_kernels.hip): a whole evaluation by ONE workgroup of one launch -----------------
+// the partial factorisation alone (what launch_potrf_partial runs at M <= tune.small_m)
+void launch_potrf_small(hipStream_t s, double *W, size_t ld, int M, int ncol, int nfac, int *d_info);
 // small-N marginal likelihood: build + factorisation + solve + log-det by ONE workgroup per point
 void small_ws_layout(int n, size_t *ld, size_t *stride);
 void launch_logml_small(hipStream_t s, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
@@ -307,6 +310,7 @@ void launch_rbf_cov_chol_small(hipStream_t s, const double *x, int n, const doub
 void launch_logml_small_batch_dev(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
                                   const double *ell, int n_ell, const double *sigma, int G, double jitter, double *d_par,
                                   double *Wall, double *d_out3, int *d_info_out, int *d_info_work);
+// ---- kernel launchers (chol_kernels.hip): triangular helpers --------------------------------------------------
 // inverses of L's 128 x 128 diagonal blocks (ceil(n / 128) x 128 x 128 doubles, tmp the same) from packed factors
 void launch_diag_inverses(hipStream_t s, const double *Fpack_all, int n, double *Dinv, double *tmp);
 // t = L^-1 k for ONE right-hand side in one launch (k_trsv_wave); k and t are different buffers of n doubles

@@ -1,5 +1,5 @@
 // Likelihood heads of the latent exact-GP models (gpmi_latent_gp_lp_grad): one row of F against the m replicate columns of Y.
-// Included by chol_kernels.hip (the one-workgroup kernel) and latent_kernels.hip (the chain's head kernel), so that both paths
+// Included by small_kernels.hip (the one-workgroup kernel) and latent_kernels.hip (the chain's head kernel), so that both paths
 // evaluate the same expression in the same order.  ocml's double exp / log1p; log sigma comes from the host (LatentHead).
 #pragma once
 

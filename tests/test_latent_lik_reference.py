@@ -1,14 +1,14 @@
 """CPU: the yardsticks of gpmi_latent_gp_lp_grad (tests/latent_lik_reference.py) pinned by central differences, the tie between
-the GPU parity test's tolerances and the reference's own error, the resource usage of the new kernels, and the new entry points'
+the GPU parity test's tolerances and the reference's own error, the resource usage of the chain's head kernels, and the new entry points'
 presence in the header, the binding list, the built library and the R wrapper."""
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from kernel_resources import resource_usage
 import latent_lik_reference as lr
 import vjp_reference as vr
 
@@ -128,49 +128,15 @@ def test_westbrook_tolerance_follows_from_the_reference(l):
     assert 10.0 * d <= lr.GRAD_TOL, d
 
 
-def _resource_usage(src, out_name, device_only=False):
-    from gp_amd import _build
-    out = os.path.join(ROOT, "build", "resource_check")
-    os.makedirs(out, exist_ok=True)
-    cmd = [_build.hipcc(), "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++20", "-fPIC", "-c", src, "-o",
-           os.path.join(out, out_name), "-Rpass-analysis=kernel-resource-usage"] + (["--cuda-device-only"] if device_only else [])
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=_build.CSRC)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels = {}
-    name = None
-    for line in r.stderr.splitlines():
-        mm = re.search(r"Function Name: (\S+)", line)
-        if mm:
-            name = mm.group(1); kernels[name] = {}
-            continue
-        mm = re.search(r"remark:\s+(VGPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if mm and name:
-            kernels[name][mm.group(1)] = int(mm.group(2))
-    return kernels
-
-
 def test_chain_head_kernels_do_not_spill():
     """The head kernels of the blocked chain keep their state in registers and LDS: 0 VGPRs spilled, 0 bytes of scratch."""
     from gp_amd import _build
-    kernels = _resource_usage(os.path.join(_build.CSRC, "latent_kernels.hip"), "latent_kernels.o")
+    kernels = resource_usage(os.path.join(_build.CSRC, "latent_kernels.hip"), "latent_kernels.o")
     for must in ("k_latent_head", "k_latent_head_sum"):
         assert any(must in k for k in kernels), (must, list(kernels))
     for k, v in kernels.items():
         assert v.get("VGPRs Spill") == 0, (k, v)
         assert v.get("ScratchSize [bytes/lane]") == 0, (k, v)
-
-
-def test_one_workgroup_kernel_needs_no_more_scratch_than_the_plain_vjp():
-    """k_latent_gp_small shares the body of k_exact_gp_vjp_small and inherits its spills; the head must not add to them.  Both
-    numbers come from one compilation of chol_kernels.hip (device code only; several minutes)."""
-    from gp_amd import _build
-    kernels = _resource_usage(os.path.join(_build.CSRC, "chol_kernels.hip"), "chol_kernels.o", device_only=True)
-    new = [v for k, v in kernels.items() if "k_latent_gp_small" in k]
-    old = [v for k, v in kernels.items() if "k_exact_gp_vjp_small" in k]
-    assert len(new) == 1 and len(old) == 1, list(kernels)
-    print("scratch bytes/lane: k_latent_gp_small %d, k_exact_gp_vjp_small %d; VGPRs spilled %d, %d" % (
-        new[0]["ScratchSize [bytes/lane]"], old[0]["ScratchSize [bytes/lane]"], new[0]["VGPRs Spill"], old[0]["VGPRs Spill"]))
-    assert new[0]["ScratchSize [bytes/lane]"] <= old[0]["ScratchSize [bytes/lane]"], (new, old)
 
 
 def test_entry_points_are_declared_bound_and_built():

@@ -98,10 +98,10 @@ def disassemble(lib, workdir):
     return outs
 
 
-def compile_asm(out):
+def compile_asm(out, source="small_kernels.hip"):
     hipcc = os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++20", "-S", "--cuda-device-only",
-                           os.path.join(ROOT, "gp_amd", "csrc", "chol_kernels.hip"), "-o", out], stderr=subprocess.DEVNULL)
+                           os.path.join(ROOT, "gp_amd", "csrc", source), "-o", out], stderr=subprocess.DEVNULL)
 
 
 if __name__ == "__main__":
