@@ -381,6 +381,28 @@ __device__ __forceinline__ void trsm_panel_body(const double *__restrict__ s_F, 
 // halves of the 64 banks so the ds_read_b64 fragment reads are conflict-free.
 // ---------------------------------------------------------------------------
 constexpr int GT = 128, GK = 16, GP = 144;
+// Pair-row layout (PAIR, the blocked update kernels): a lane owns TWO ADJACENT operand rows per pair of MFMA tiles -- inside
+// the wave's 64 rows tile t, lane row lr is row (t >> 1) * 32 + 2 * lr + (t & 1) instead of t * 16 + lr -- so that the
+// fragments of tiles t, t + 1 (t even) are 16 contiguous bytes of a k-row (one ds_read_b128) and acc[tn][tm][i],
+// acc[tn][tm + 1][i] are rows r, r + 1 of one column of C (one 16-byte access).  Which row a lane owns inside an MFMA tile is
+// a labelling: every C element sums the same k-terms in the same order.  The image is the same buffer at a k-row pitch of
+// GPP doubles: ds_read_b128 is served in lane groups that mix two k-rows (two lq), conflict-free only at a pitch that is
+// a multiple of 256 B.
+constexpr int GPP = 128;
+typedef double d2 __attribute__((ext_vector_type(2)));
+// Two adjacent rows of C as ONE 16-byte access.  A global-memory access of any width needs dword alignment only, so the
+// pair is typed with the alignment of its elements: a factorisation in place at an odd offset, or with an odd leading
+// dimension, takes the same instructions as an aligned one.
+typedef d2 d2c __attribute__((aligned(8)));
+__device__ __forceinline__ d2 ld_c2(const double *p, bool nt)
+{
+    return nt ? __builtin_nontemporal_load((const d2c *)p) : *(const d2c *)p;
+}
+__device__ __forceinline__ void st_c2(double *p, d2 v, bool nt)
+{
+    if (nt) __builtin_nontemporal_store((d2c)v, (d2c *)p);
+    else *(d2c *)p = v;
+}
 
 // One 128 x 128 output tile (ti, tj); smem is the workgroup's staging buffer (free on entry:
 // every wave has finished reading it).
@@ -403,11 +425,13 @@ __device__ __forceinline__ Epi3<R, C, E> make_epi3(R r, C c, E e)
 {
     return Epi3<R, C, E>{r, c, e};
 }
-template <int MODE, bool WHOLE, class EPI = NoEpi>
+template <int MODE, bool WHOLE, bool PAIR = false, class EPI = NoEpi>
 __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const double *__restrict__ A, size_t lda,
                                             const double *__restrict__ B, size_t ldb, double *__restrict__ C,
                                             size_t ldc, int M, int N, int K, int ti, int tj, int dbg, int tid, EPI &&epi = EPI{})
 {
+    static_assert(!PAIR || MODE == 0 || MODE == 1, "the pair-row layout is the update kernels'");
+    static_assert(2 * 2 * GK * GPP <= 2 * 2 * GK * GP, "the pair-row image lies inside the staging buffer");
     const int m0 = ti * GT, n0 = tj * GT;
     if (MODE == 1 && n0 >= N) return;
     const int lane = tid & 63;
@@ -428,6 +452,13 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
         for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
 
     const int nk = (K + GK - 1) / GK;
+    // PAIR: k-row kr of operand o in a stage -- where its 1-KiB DMA lands and where the lane's 16-byte pairs are read
+    auto pair_row = [&](int stage, int o, int kr) { return &smem[0][0][0][0] + (size_t)((stage * 2 + o) * GK + kr) * GPP; };
+    auto ldpair = [&](int st, int o, int kr, int t, double (&f)[4]) {  // tiles t, t + 1 (t even) of operand o
+        const d2 v = *(const d2 *)(pair_row(st, o, kr) + (o ? wn : wm) * 64 + (t >> 1) * 32 + 2 * lr);
+        f[t] = v.x;
+        f[t + 1] = v.y;
+    };
     auto issue = [&](int stage, int k0) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -436,7 +467,7 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
             kc = kc < K ? kc : K - 1;  // clamp: never read a column past the operand
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(gsrc + (size_t)kc * gld),
-                (__attribute__((address_space(3))) void *)&smem[stage][op][kr][0], 16, 0, 0);
+                (__attribute__((address_space(3))) void *)(PAIR ? pair_row(stage, op, kr) : &smem[stage][op][kr][0]), 16, 0, 0);
         }
     };
     // Fragments of sub-step kk+1 are requested before the 16 MFMAs of sub-step kk are issued
@@ -446,10 +477,17 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
     auto ldfrag = [&](auto mk, int st, int kk, int klim, double (&af)[4], double (&bf)[4]) {
         constexpr bool MASK = decltype(mk)::value != 0;
         const int kr = kk * 4 + lq;
+        if constexpr (PAIR) {
+            ldpair(st, 1, kr, 0, af);
+            ldpair(st, 1, kr, 2, af);
+            ldpair(st, 0, kr, 0, bf);
+            ldpair(st, 0, kr, 2, bf);
+        } else {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            af[t] = smem[st][1][kr][wn * 64 + t * 16 + lr];
-            bf[t] = smem[st][0][kr][wm * 64 + t * 16 + lr];
+            for (int t = 0; t < 4; ++t) {
+                af[t] = smem[st][1][kr][wn * 64 + t * 16 + lr];
+                bf[t] = smem[st][0][kr][wm * 64 + t * 16 + lr];
+            }
         }
         if constexpr (MASK) {
             const bool kv = kr < klim;
@@ -492,7 +530,7 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
 #pragma unroll
         for (int q = 0; q < 8; ++q)  // stage 0, same lean addressing as the loop
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g0 + (size_t)q * gld),
-                                             (__attribute__((address_space(3))) void *)&smem[0][op][krow0 + q][0], 16, 0, 0);
+                                             (__attribute__((address_space(3))) void *)(PAIR ? pair_row(0, op, krow0 + q) : &smem[0][op][krow0 + q][0]), 16, 0, 0);
     } else {
         issue(0, 0);
     }
@@ -517,7 +555,7 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
 #pragma unroll
             for (int q = 0; q < 8; ++q)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gp + (size_t)q * gld),
-                                                 (__attribute__((address_space(3))) void *)&smem[1][op][krow0 + q][0], 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void *)(PAIR ? pair_row(1, op, krow0 + q) : &smem[1][op][krow0 + q][0]), 16, 0, 0);
         }
         ldfrag(ic<0>{}, 0, 0, GK, a0, b0);
         // one k-step that has a successor; DMA: the step after that exists and is requested here
@@ -555,14 +593,19 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(a1[tn], b1[tm], acc[tn][tm]);
                 __builtin_amdgcn_sched_barrier(0);
-                a0[tn] = smem[st ^ 1][1][lq][wn * 64 + tn * 16 + lr];
-                b0[tn] = smem[st ^ 1][0][lq][wm * 64 + tn * 16 + lr];
+                if constexpr (PAIR) {  // one 16-byte read behind each four MFMAs: a0 pair 0, b0 pair 0, a0 pair 1, b0 pair 1
+                    if (tn & 1) ldpair(st ^ 1, 0, lq, tn & 2, b0);
+                    else ldpair(st ^ 1, 1, lq, tn & 2, a0);
+                } else {
+                    a0[tn] = smem[st ^ 1][1][lq][wn * 64 + tn * 16 + lr];
+                    b0[tn] = smem[st ^ 1][0][lq][wm * 64 + tn * 16 + lr];
+                }
                 if constexpr (DMA) if (tn < 2) {  // all eight requests behind the first eight MFMAs: they have until the next barrier
 #pragma unroll
                     for (int q = 4 * tn; q < 4 * tn + 4; ++q)
                         __builtin_amdgcn_global_load_lds(
                             (const __attribute__((address_space(1))) void *)(gp + (size_t)q * gld),
-                            (__attribute__((address_space(3))) void *)&smem[st][op][krow0 + q][0], 16, 0, 0);
+                            (__attribute__((address_space(3))) void *)(PAIR ? pair_row(st, op, krow0 + q) : &smem[st][op][krow0 + q][0]), 16, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -599,13 +642,41 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    if (MODE != 2 && MODE != 3 && interior) {
+    if (!PAIR && MODE != 2 && MODE != 3 && interior) {
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
             for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ch[tn][tm][i] = ld_c(cbase + tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc, cnt);
+    }
+    // PAIR: the lane's rows prow(tm), prow(tm + 1) = prow(tm) + 1 (tm even) and columns pcol(tn, i); half h of the C tile is
+    // tn = 2 h, 2 h + 1: 16 accesses of 16 bytes from one base
+    auto prow = [&](int tm) { return m0 + wm * 64 + (tm >> 1) * 32 + 2 * lr + (tm & 1); };
+    auto pcol = [&](int tn, int i) { return n0 + wn * 64 + (tn >> 1) * 32 + 2 * (lq + 4 * i) + (tn & 1); };
+    double *const cpair = PAIR ? C + (size_t)prow(0) + (size_t)pcol(0, 0) * ldc : nullptr;
+    d2 cp[2][2][4];  // [tn & 1][tm >> 1][i]
+    auto cp_at = [&](int tn, int p, int i) { return cpair + p * 32 + (size_t)((tn >> 1) * 32 + 8 * i + (tn & 1)) * ldc; };
+    auto cp_load = [&](int h) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) cp[t][p][i] = ld_c2(cp_at(2 * h + t, p, i), cnt);
+    };
+    auto cp_store = [&](int h) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    st_c2(cp_at(2 * h + t, p, i),
+                          d2{cp[t][p][i].x - acc[2 * h + t][2 * p][i], cp[t][p][i].y - acc[2 * h + t][2 * p + 1][i]}, cnt);
+    };
+    if constexpr (PAIR) {
+        if (interior) cp_load(0);
     }
     if constexpr (WHOLE) {  // the fragments of sub-step 0 of the last stage are in registers
         const int st = (nk - 1) & 1;
@@ -658,6 +729,36 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm) epi.elem(acc[tn][tm][i], tm);
             }
+        return;
+    }
+    if constexpr (PAIR) {
+        if (interior) {
+            cp_store(0);
+            cp_load(1);
+            cp_store(1);
+            return;
+        }
+        // edge tile, as below with the lane's pair-row indices
+#pragma unroll
+        for (int tn = 0; tn < 4; ++tn) {
+            double ce[4][4];
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    int n = pcol(tn, i), m = prow(tm);
+                    n = n < N ? n : N - 1;
+                    m = m < M ? m : M - 1;
+                    ce[tm][i] = C[(size_t)m + (size_t)n * ldc];
+                }
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int n = pcol(tn, i), m = prow(tm);
+                    if (m < M && n < N && (MODE != 1 || n <= m)) C[(size_t)m + (size_t)n * ldc] = ce[tm][i] - acc[tn][tm][i];
+                }
+        }
         return;
     }
     if (interior) {
@@ -716,13 +817,13 @@ __device__ __forceinline__ void gemm_tile_k(double (&smem)[2][2][GK][GP], const 
 
 // Whole k-steps (every launch of a factorisation whose order is a multiple of 16) take the software-pipelined form;
 // the two forms are separate instantiations so that neither's live ranges weigh on the other's register allocation.
-template <int MODE, class EPI = NoEpi>
+template <int MODE, bool PAIR = false, class EPI = NoEpi>
 __device__ __forceinline__ void gemm_tile(double (&smem)[2][2][GK][GP], const double *__restrict__ A, size_t lda,
                                           const double *__restrict__ B, size_t ldb, double *__restrict__ C,
                                           size_t ldc, int M, int N, int K, int ti, int tj, int dbg, int tid, EPI &&epi = EPI{})
 {
-    if (K % GK == 0 && !(dbg & 16)) gemm_tile_k<MODE, true>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, tid, epi);  // workgroup-uniform
-    else gemm_tile_k<MODE, false>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, tid, epi);
+    if (K % GK == 0 && !(dbg & 16)) gemm_tile_k<MODE, true, PAIR>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, tid, epi);  // workgroup-uniform
+    else gemm_tile_k<MODE, false, PAIR>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, tid, epi);
 }
 
 

@@ -568,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const double *__restrict__ A
             }
         }
     }
-    gemm_tile<MODE>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, (int)threadIdx.x);
+    gemm_tile<MODE, MODE == 0 || MODE == 1>(smem, A, lda, B, ldb, C, ldc, M, N, K, ti, tj, dbg, (int)threadIdx.x);  // the updates: pair-row layout
     if (MODE != 2 && fd.Fp && !(order & 0x200) && ti == 0 && tj == 0) {  // workgroup-uniform
         // the tile's stores must be visible to the other waves of this workgroup, which read the
         // block back in the diagonal kernel's register layout
