@@ -27,6 +27,7 @@ SYMBOLS = (
     "gpmi_joint_logml", "gpmi_joint_logml_dev", "gpmi_joint_logml_grid_dev", "gpmi_rbf_cov_chol", "gpmi_gp_condition", "gpmi_sample_derivs", "gpmi_sample_derivs_batch",
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
     "gpmi_interp_free", "gpmi_logml_grad", "gpmi_logml_grad_grid",
+    "gpmi_logml_grad_dev", "gpmi_logml_grad_grid_dev", "gpmi_logml_grad_grid_ard", "gpmi_logml_grad_grid_ard_dev",
     "gpmi_joint_logml_grad", "gpmi_joint_logml_grad_dev", "gpmi_joint_logml_grad_grid",
     "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
@@ -118,6 +119,11 @@ def _p(a):
 
 def _d(x):
     return C.c_double(float(x))
+
+
+def _vp(ptr):
+    """a raw (device) address as a pointer argument; 0 / None: NULL"""
+    return C.c_void_p(ptr) if ptr else None
 
 
 def _vec(x):
@@ -443,6 +449,22 @@ class Context:
                                             _p(out), _p(g), _p(info)))
         return out, g, info
 
+    def logml_grad_grid_ard(self, X, y, alpha, ell, sigma, jitter=0.0):
+        """(out (G, 3), grad (G, D + 2), info (G,)): value and (d/dalpha, d/dell_0 .. d/dell_{D-1}, d/dsigma) at G points with
+        one length-scale per dimension each (ell: (G, D)); alpha and sigma broadcast as in logml_grid_ard."""
+        X = _mat(X); y = _vec(y)
+        n, D = X.shape
+        if y.size != n:
+            raise GpmiError(-1, "X and y disagree on N")
+        E = np.ascontiguousarray(np.asarray(ell, dtype=np.float64).reshape(-1, D))
+        G = E.shape[0]
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, float), (G,)))
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, float), (G,)))
+        out = np.empty((G, 3)); g = np.empty((G, D + 2)); info = np.zeros(G, dtype=np.int32)
+        _chk(self._lib.gpmi_logml_grad_grid_ard(self._h, _p(X), n, max(n, 1), D, _p(y), _p(a), _p(E), _p(s), G, _d(jitter),
+                                                _p(out), _p(g), _p(info)))
+        return out, g, info
+
     def joint_logml_grad(self, t, yy, alpha, l, sigma, jitter=1e-6):
         """((logml, sum log L_ii, z'z), grad) of the joint [y; y'] model, grad = (d/dalpha, d/dl, d/dsigma) of logml;
         raises NotPositiveDefinite."""
@@ -720,6 +742,31 @@ class Context:
         _chk(self._lib.gpmi_joint_logml_grad_dev(self._h, C.c_void_p(dt_ptr), int(n), C.c_void_p(dyy_ptr), _d(alpha), _d(l),
                                                  _d(sigma), _d(jitter), C.c_void_p(dout_ptr), C.c_void_p(dgrad_ptr),
                                                  C.c_void_p(dinfo_ptr)))
+
+    def logml_grad_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, ell, sigma, jitter, dout_ptr, dgrad_ptr, dinfo_ptr):
+        """gpmi_logml_grad_dev on device pointers: d_out3 (3), d_grad (2 + len(ell)) and d_info (1 int) are written by the device
+        (NaN gradient and info = k when the matrix is not positive definite); enqueued, not synchronised, nothing is raised for
+        that status."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_logml_grad_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _d(alpha), _p(ell),
+                                           int(ell.size), _d(sigma), _d(jitter), _vp(dout_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
+
+    def logml_grad_grid_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, rho, sigma, jitter, dout_ptr, dgrad_ptr, dinfo_ptr):
+        """gpmi_logml_grad_grid_dev: d_out3 (3 G), d_grad (3 G), d_info (G ints); alpha, rho, sigma: host arrays of one length."""
+        a = _vec(alpha); r = _vec(rho); s = _vec(sigma)
+        if not (a.size == r.size == s.size):
+            raise GpmiError(-1, "alpha, rho and sigma disagree on G")
+        _chk(self._lib.gpmi_logml_grad_grid_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _p(a), _p(r), _p(s),
+                                                int(a.size), _d(jitter), _vp(dout_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
+
+    def logml_grad_grid_ard_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, ell, sigma, jitter, dout_ptr, dgrad_ptr, dinfo_ptr):
+        """gpmi_logml_grad_grid_ard_dev: ell (G, D); d_out3 (3 G), d_grad (G (D + 2), point-major), d_info (G ints)."""
+        E = np.ascontiguousarray(np.asarray(ell, dtype=np.float64).reshape(-1, int(D)))
+        G = E.shape[0]
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, float), (G,)))
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, float), (G,)))
+        _chk(self._lib.gpmi_logml_grad_grid_ard_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _p(a), _p(E), _p(s),
+                                                    G, _d(jitter), _vp(dout_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
 
     def joint_logml_grid_dev(self, dt_ptr, n, dyy_ptr, alpha, l, sigma, jitter, dout_ptr, dinfo_ptr):
         a = _vec(alpha); r = _vec(l); s = _vec(sigma)

@@ -2684,6 +2684,34 @@ __global__ void k_vjp_finish(const double *__restrict__ hs, int D, double alpha,
         gpmi_grad_from_sums(hs, D, alpha, e.ell, n_ell, grad);
 }
 
+// The device's logml_grad_unpack, one thread per result record (value triple, then ns contraction sums; stride doubles apart):
+// out3[3 g ..] and grad[g (2 + n_ell) ..] = (d/dalpha, d/dell..., d/dsigma), NaN when info[g] != 0.  The point's parameters
+// (alpha, ell[0 .. n_ell), sigma) are read from par + g (2 + n_ell) (device memory: a grid), or from `one` when par == nullptr
+// (G == 1).  The statements are those of logml_grad_finish: same bits as the host forms.
+struct GradFinishOne {
+    double alpha, sigma;
+    GradEll e;
+};
+__global__ __launch_bounds__(64) void k_logml_grad_finish(const double *__restrict__ res, size_t stride, const int *__restrict__ info, int G,
+                                                          int D, int ns, int n_ell, GradFinishOne one, const double *__restrict__ par,
+                                                          double *__restrict__ out3, double *__restrict__ grad)
+{
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= G) return;
+    const double *r = res + (size_t)g * stride;
+    const double *pg = par ? par + (size_t)g * (2 + n_ell) : nullptr;
+    const double alpha = pg ? pg[0] : one.alpha, sigma = pg ? pg[1 + n_ell] : one.sigma;
+    const double *ell = pg ? pg + 1 : one.e.ell;
+    double *gr = grad + (size_t)g * (2 + n_ell);
+    for (int k = 0; k < 3; ++k) out3[3 * (size_t)g + k] = r[k];
+    if (info[g] != 0) {
+        for (int k = 0; k < 2 + n_ell; ++k) gr[k] = __builtin_nan("");
+    } else {
+        gpmi_grad_from_sums(r + 3, D, alpha, ell, n_ell, gr);
+        gr[1 + n_ell] = 2.0 * sigma * r[3 + ns - 1];
+    }
+}
+
 // A (rows x cols, ld) = NaN when *info != 0
 __global__ __launch_bounds__(256) void k_nan_on_info(double *__restrict__ A, size_t ld, int rows, int cols, const int *__restrict__ info)
 {
@@ -3243,6 +3271,183 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
     lanes_join(c, lanes, caller, la_saved);
     if (rc) return rc;
     return grad_grid_down(c, dres, GRAD_RES, dinfo, G, D, alpha, rho, sigma, out3, grad, info);
+}
+
+// ---- the gradient finished on the device: device-resident forms and ARD grids ------------------------------------------
+// k_logml_grad_finish for G records: one point's parameters travel as kernel arguments (par == nullptr)
+static void launch_logml_grad_finish(hipStream_t s, const double *d_res, size_t stride, const int *d_info, int G, int D, int n_ell,
+                                     double alpha, const double *ell, double sigma, const double *d_par, double *d_out3, double *d_grad)
+{
+    GradFinishOne one;
+    one.alpha = alpha;
+    one.sigma = sigma;
+    one.e = grad_ell(d_par ? nullptr : ell, d_par ? 0 : n_ell);
+    hipLaunchKernelGGL(k_logml_grad_finish, dim3((unsigned)((G + 63) / 64)), 64, 0, s, d_res, stride, d_info, G, D, grad_ns(D), n_ell, one,
+                       d_par, d_out3, d_grad);
+}
+
+// gpmi_logml_grad on device-resident data, enqueued on c->stream: the routes of the host form (one workgroup without its
+// pinned buffer, or the chain), then the finishing kernel.  No synchronisation: a point that is not positive definite
+// leaves *d_info > 0, d_out3 as gpmi_logml_dev leaves it and a NaN gradient.
+extern "C" int gpmi_logml_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, double alpha,
+                                   const double *ell, int n_ell, double sigma, double jitter, double *d_out3, double *d_grad,
+                                   int *d_info)
+{
+    ENTER(c);
+    if (n <= 0 || !dX || !dy || !d_out3 || !d_grad || !d_info || ldx < n || D < 1) return gpmi_fail(GPMI_EARG, "bad argument");
+    SeParams p;
+    int rc;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    double *dres = c->d_fin + 4096;  // second half of the finalize scratch, as in gpmi_logml_grad
+    if (c->tune.small_ng1 > 0 && n <= c->tune.small_ng1 && D <= GPMI_MAXD) {
+        if ((rc = reserve_ws_small(c, n, 2))) return rc;
+        launch_logml_grad_small(c->stream, dX, n, ldx, dy, p, sigma * sigma + jitter, c->W, dres, d_info, c->d_info, nullptr);
+        launch_logml_grad_finish(c->stream, dres, GPMI_SMALL_GRAD_RES, d_info, 1, D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    if ((rc = logml_grad_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dres, d_info))) return rc;
+    launch_logml_grad_finish(c->stream, dres, GRAD_RES, d_info, 1, D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The device part of every value + gradient grid that the device finishes: G points with n_ell (1 or D) length-scales each
+// (ell: G x n_ell, point-major), grad: G x (2 + n_ell).  One workgroup per point (n <= small_ng, or small_ng1 for one point,
+// and D <= GPMI_MAXD: the isotropic kernel with its parameters as kernel arguments, the ARD one with them in device memory),
+// otherwise the lanes; then ONE finishing launch.  The context's scratch holds, behind the root's panel factors: the G result
+// records, the finishing kernel's parameters (alpha, ell..., sigma per point) and -- for the host forms, which pass
+// d_out3 == nullptr and download them -- out3, grad and info.
+struct GradGridOut {
+    double *out3, *grad;
+    int *info;
+};
+static int logml_grad_grid_core(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
+                                const double *ell, int n_ell, const double *sigma, int G, double jitter, double *d_out3, double *d_grad,
+                                int *d_info, GradGridOut *host_out)
+{
+    int rc;
+    std::vector<SeParams> ps(G);
+    for (int g = 0; g < G; ++g)
+        if ((rc = fill_params(&ps[g], D, alpha[g], ell + (size_t)g * n_ell, n_ell))) return rc;
+    const bool small = D <= GPMI_MAXD && n <= (G >= 2 ? c->tune.small_ng : c->tune.small_ng1);
+    const size_t np = 2 + (size_t)n_ell, stride = small ? GPMI_SMALL_GRAD_RES : GRAD_RES;
+    const size_t head = small ? 0 : (size_t)((n + GPMI_NB - 1) / GPMI_NB) * GPMI_FPACK;
+    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
+    if (lanes > 8) lanes = 8;
+    if (lanes > G) lanes = G;
+    const int per = G < GPMI_SMALL_PTS ? G : GPMI_SMALL_PTS;
+    static_assert(GPMI_SMALL_GRAD_DEV_PTS == GPMI_SMALL_PTS, "one workspace size for both one-workgroup gradient grids");
+    if (small) {
+        if ((rc = reserve_ws_small(c, n, 2 * per))) return rc;
+        if ((rc = reserve_small_par(c, G))) return rc;
+    } else {
+        if ((rc = lanes_prepare(c, lanes))) return rc;
+        for (int k = 0; k < lanes; ++k)
+            if ((rc = logml_grad_reserve(k ? c->lane[k - 1] : c, n, D, G > 1))) return rc;
+    }
+    double *base;
+    if ((rc = scratch_buf(c, (head + (size_t)G * (stride + 2 * np + 3 + 1) + 8) * sizeof(double), &base))) return rc;
+    double *dres = base + head, *dpar = dres + (size_t)G * stride;
+    if (!d_out3) {
+        d_out3 = dpar + (size_t)G * np;
+        d_grad = d_out3 + 3 * (size_t)G;
+        d_info = (int *)(d_grad + (size_t)G * np);
+        *host_out = GradGridOut{d_out3, d_grad, d_info};
+    }
+    if (small && n_ell == 1) {
+        for (int g0 = 0; g0 < G; g0 += per) {
+            const int gc = (G - g0 < per) ? G - g0 : per;
+            launch_logml_grad_small_batch(c->stream, dX, n, ldx, D, dy, alpha + g0, ell + g0, sigma + g0, gc, jitter, c->W,
+                                          dres + (size_t)g0 * stride, d_info + g0, c->d_sinfo);
+        }
+    } else if (small) {
+        launch_logml_grad_batch_dev(c->stream, dX, n, ldx, D, dy, alpha, ell, sigma, G, jitter, c->d_spar, c->W, per, dres, d_info,
+                                    c->d_sinfo);
+    } else {
+        const int la_saved = c->lookahead;
+        hipStream_t const caller = c->stream;
+        lanes_fork(c, lanes, caller);
+        for (int g = 0; g < G && !rc; ++g) {
+            gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
+            rc = logml_grad_core(lc, dX, n, ldx, dy, ps[g], sigma[g] * sigma[g] + jitter, dres + (size_t)g * stride, d_info + g, G > 1);
+        }
+        lanes_join(c, lanes, caller, la_saved);
+        if (rc) return rc;
+    }
+    // the finishing kernel's parameters, in stream order
+    std::vector<double> hp((size_t)G * np);
+    for (int g = 0; g < G; ++g) {
+        double *q = hp.data() + (size_t)g * np;
+        q[0] = alpha[g];
+        for (int d = 0; d < n_ell; ++d) q[1 + d] = ell[(size_t)g * n_ell + d];
+        q[1 + n_ell] = sigma[g];
+    }
+    launch_put_doubles(c->stream, hp.data(), hp.size(), dpar);
+    launch_logml_grad_finish(c->stream, dres, stride, d_info, G, D, n_ell, 0.0, nullptr, 0.0, dpar, d_out3, d_grad);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int grad_grid_check(int n, int ldx, int D, const void *X, const void *y, const void *alpha, const void *ell,
+                           const void *sigma, const void *out3, const void *grad, const void *info)
+{
+    if (n <= 0 || ldx < n || D < 1 || D > GPMI_MAXD_BIG) return gpmi_fail(GPMI_EARG, "bad size or leading dimension");
+    if (!X || !y || !alpha || !ell || !sigma || !out3 || !grad || !info) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    return 0;
+}
+
+// gpmi_logml_grad_grid on device-resident data: its routes without the pinned branch, finished on the device
+extern "C" int gpmi_logml_grad_grid_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
+                                        const double *rho, const double *sigma, int G, double jitter, double *d_out3, double *d_grad,
+                                        int *d_info)
+{
+    ENTER(c);
+    if (G < 0) return gpmi_fail(GPMI_EARG, "negative grid size");
+    if (G == 0) return 0;
+    int rc;
+    if ((rc = grad_grid_check(n, ldx, D, dX, dy, alpha, rho, sigma, d_out3, d_grad, d_info))) return rc;
+    return logml_grad_grid_core(c, dX, n, ldx, D, dy, alpha, rho, 1, sigma, G, jitter, d_out3, d_grad, d_info, nullptr);
+}
+
+// Value AND gradient at G points with one length-scale per dimension and point (ell: G x D, point-major; grad: G x (D + 2),
+// point-major: d/dalpha, d/dell_0 .. d/dell_{D-1}, d/dsigma): the several optimiser starts that fitting QQard's theta
+// (R/kernels.R:11-19) takes, since the likelihood is multimodal in the length-scales.
+extern "C" int gpmi_logml_grad_grid_ard_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
+                                            const double *ell, const double *sigma, int G, double jitter, double *d_out3,
+                                            double *d_grad, int *d_info)
+{
+    ENTER(c);
+    if (G < 0) return gpmi_fail(GPMI_EARG, "negative grid size");
+    if (G == 0) return 0;
+    int rc;
+    if ((rc = grad_grid_check(n, ldx, D, dX, dy, alpha, ell, sigma, d_out3, d_grad, d_info))) return rc;
+    return logml_grad_grid_core(c, dX, n, ldx, D, dy, alpha, ell, D, sigma, G, jitter, d_out3, d_grad, d_info, nullptr);
+}
+
+// the host form: X, y up, the device grid with its outputs in the context's scratch, the outputs down, the stream drained
+extern "C" int gpmi_logml_grad_grid_ard(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, const double *alpha,
+                                        const double *ell, const double *sigma, int G, double jitter, double *out3, double *grad,
+                                        int *info)
+{
+    ENTER(c);
+    if (G < 0) return gpmi_fail(GPMI_EARG, "negative grid size");
+    if (G == 0) return 0;
+    int rc;
+    if ((rc = grad_grid_check(n, ldx, D, X, y, alpha, ell, sigma, out3, grad, info))) return rc;
+    for (int g = 0; g < G; ++g)   // before anything is uploaded
+        for (int d = 0; d < D; ++d)
+            if (!(ell[(size_t)g * D + d] > 0.0)) return gpmi_fail(GPMI_EARG, "length-scale must be positive");
+    double *dX, *dy;
+    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
+    GradGridOut o;
+    if ((rc = logml_grad_grid_core(c, dX, n, n, D, dy, alpha, ell, D, sigma, G, jitter, nullptr, nullptr, nullptr, &o))) return rc;
+    HIPCHK(hipMemcpyAsync(out3, o.out3, 3 * (size_t)G * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(grad, o.grad, (size_t)G * (D + 2) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(info, o.info, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // ---- value and gradient of the joint [y; y'] model -------------------------------------------------------------------

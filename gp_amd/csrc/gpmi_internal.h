@@ -246,6 +246,15 @@ void launch_logml_grad_small_batch(hipStream_t s, const double *dX, int n, int l
                                    const double *rho, const double *sigma, int G, double jitter, double *Wall, double *d_res,
                                    int *d_info_out, int *d_info_work, double *stage = nullptr /* G n (D + 1) doubles: X, y host-mapped */,
                                    int *done = nullptr, int seq = 0, int *arrive = nullptr /* zeroed device int, left zero */);
+// ... for any number of points with one length-scale per dimension each (ell: G x D, point-major), device data only: the
+// parameters are uploaded to d_par (G * GPMI_SMALL_PAR doubles) in stream order, `per` <= GPMI_SMALL_GRAD_DEV_PTS points run per
+// launch (Wall: 2 per slices, d_info_work: per ints), d_res: G records of GPMI_SMALL_GRAD_RES doubles
+#define GPMI_SMALL_GRAD_DEV_PTS 128
+void launch_logml_grad_batch_dev(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
+                                 const double *ell, const double *sigma, int G, double jitter, double *d_par, double *Wall, int per,
+                                 double *d_res, int *d_info_out, int *d_info_work);
+// count doubles from host memory to device memory in stream order, as kernel arguments (no staging buffer, no synchronisation)
+void launch_put_doubles(hipStream_t s, const double *src, size_t count, double *dst);
 // B posterior draws of the derivative process, one workgroup each (workspace: B slices of small_ws_layout(n + m); d_par: 3 B doubles,
 // d_info_work: 2 B ints)
 void launch_sample_derivs_small_batch(hipStream_t s, const double *dt, int n, const double *dts, int m, const double *dY,

@@ -754,6 +754,22 @@ __global__ __launch_bounds__(256, 2) void k_logml_grad_small_batch(const double 
     }
 }
 
+// ... and any number of points with one length-scale PER DIMENSION each, their SMALL_PAR records in device memory as for
+// k_logml_small_batch_dev: the ARD grids of gpmi_logml_grad_grid_ard[_dev].  Device data only: no staging, no completion flag
+__global__ __launch_bounds__(256, 2) void k_logml_grad_batch_dev(const double *__restrict__ X, int n, int ldx, int D,
+                                                              const double *__restrict__ y, const double *__restrict__ par,
+                                                              double *__restrict__ Wall, size_t wstride, size_t ustride, size_t ld,
+                                                              double *__restrict__ res, int *info_out, int *info_w, ExpC ec)
+{
+    GPMI_SMALL_LDS
+    const int g = blockIdx.x;
+    const double *pg = par + (size_t)g * SMALL_PAR;
+    const SmallSe se = small_se(pg[0], pg + 2, D);
+    double *W = Wall + (size_t)g * wstride;
+    logml_grad_small_body(smem, s_F, s_aux, X, n, ldx, y, se, pg[1], W, ld, W + ustride, res + (size_t)g * SMALL_GRAD_RES,
+                          info_out + g, info_w + g, ec);
+}
+
 // One posterior draw of the derivative process (sample_derivs, pendulum_fit.R:227-255) per workgroup: the loop
 // mclapply(s_list[1:100], sample_derivs_both_states, mc.cores = 2) (:261-268) is B independent draws, each with its own
 // (l, a, sy) and noisy series, at n = m = 199 -- a chain of ~25 latency-bound launches per draw on the blocked path.  Here
@@ -1668,9 +1684,20 @@ void launch_logml_small_batch_ard(hipStream_t s, const double *dX, int n, int ld
 
 // G points (any number) whose parameters are uploaded to d_par (G * (2 + GPMI_MAXD) doubles) in stream order; ell: one
 // length-scale per point (n_ell == 1) or D per point (point-major); Wall: G slices (small_ws_layout)
-void launch_logml_small_batch_dev(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
-                                  const double *ell, int n_ell, const double *sigma, int G, double jitter, double *d_par,
-                                  double *Wall, double *d_out3, int *d_info_out, int *d_info_work)
+// count doubles of host memory into device memory in stream order, PUT_MAX per launch (the host array may be reused at once)
+void launch_put_doubles(hipStream_t s, const double *src, size_t count, double *dst)
+{
+    PutArgs a;
+    for (size_t i0 = 0; i0 < count; i0 += PUT_MAX) {
+        const int nc = (count - i0 < (size_t)PUT_MAX) ? (int)(count - i0) : PUT_MAX;
+        for (int i = 0; i < nc; ++i) a.v[i] = src[i0 + i];
+        hipLaunchKernelGGL(k_put_doubles, dim3(1), 256, 0, s, a, dst + i0, nc);
+    }
+}
+
+// the SMALL_PAR records of G points into d_par, in stream order
+static void put_small_par(hipStream_t s, int D, const double *alpha, const double *ell, int n_ell, const double *sigma, int G,
+                          double jitter, double *d_par)
 {
     static_assert(PUT_MAX % SMALL_PAR == 0, "whole points per upload");
     PutArgs a;
@@ -1685,6 +1712,13 @@ void launch_logml_small_batch_dev(hipStream_t s, const double *dX, int n, int ld
         }
         hipLaunchKernelGGL(k_put_doubles, dim3(1), 256, 0, s, a, d_par + (size_t)g0 * SMALL_PAR, gc * SMALL_PAR);
     }
+}
+
+void launch_logml_small_batch_dev(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
+                                  const double *ell, int n_ell, const double *sigma, int G, double jitter, double *d_par,
+                                  double *Wall, double *d_out3, int *d_info_out, int *d_info_work)
+{
+    put_small_par(s, D, alpha, ell, n_ell, sigma, G, jitter, d_par);
     size_t ld, stride;
     small_ws_layout(n, &ld, &stride);
     launch_small<k_logml_small_batch_dev>(G, SMALL_LDS_DOUBLES, s, dX, n, ldx, D, dy, d_par, Wall,
@@ -1710,6 +1744,22 @@ void launch_logml_grad_small_batch(hipStream_t s, const double *dX, int n, int l
     small_ws_layout(n, &ld, &stride);
     launch_small<k_logml_grad_small_batch>(G, SMALL_GRAD_LDS_DOUBLES, s, dX, n, ldx, D, dy, b, Wall,
                        2 * stride, stride, ld, d_res, d_info_out, d_info_work, h_exp, stage, done, seq, arrive);
+}
+
+// G ARD points (any number; ell: G x D, point-major), `per` of them per launch: d_par holds G records, Wall 2 per slices
+// (W, then U, per point) and d_info_work per ints; the launches of one call follow each other on s, so the slices are reused
+void launch_logml_grad_batch_dev(hipStream_t s, const double *dX, int n, int ldx, int D, const double *dy, const double *alpha,
+                                 const double *ell, const double *sigma, int G, double jitter, double *d_par, double *Wall, int per,
+                                 double *d_res, int *d_info_out, int *d_info_work)
+{
+    put_small_par(s, D, alpha, ell, D, sigma, G, jitter, d_par);
+    size_t ld, stride;
+    small_ws_layout(n, &ld, &stride);
+    for (int g0 = 0; g0 < G; g0 += per) {
+        const int gc = (G - g0 < per) ? G - g0 : per;
+        launch_small<k_logml_grad_batch_dev>(gc, SMALL_GRAD_LDS_DOUBLES, s, dX, n, ldx, D, dy, d_par + (size_t)g0 * SMALL_PAR, Wall,
+                           2 * stride, stride, ld, d_res + (size_t)g0 * SMALL_GRAD_RES, d_info_out + g0, d_info_work, h_exp);
+    }
 }
 
 // B draws by one workgroup each; Wall: B slices of small_ws_layout(n + m); dY: n x B, dZ, draws, mus: m x B (packed); d_par: 3 B

@@ -251,6 +251,32 @@ GPMI_API int gpmi_logml_grad_grid(gpmi_ctx *ctx, const double *X, int n, int ldx
                                   const double *alpha, const double *rho, const double *sigma, int G, double jitter,
                                   double *out3, double *grad, int *info);
 
+/* gpmi_logml_grad with device-resident X, y, d_out3 (3), d_grad (2 + n_ell), d_info (1 int): enqueued on the context's stream,
+ * no synchronisation; the device itself writes the gradient, NaN when the matrix is not positive definite (ell: host).
+ * The return value says only whether the work was enqueued; the bits are those of gpmi_logml_grad. */
+GPMI_API int gpmi_logml_grad_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                                 double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                                 double *d_out3, double *d_grad, int *d_info);
+
+/* gpmi_logml_grad_grid on device-resident data: d_out3 3 G, d_grad 3 G, d_info G (alpha, rho, sigma: host arrays) */
+GPMI_API int gpmi_logml_grad_grid_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                                      const double *alpha, const double *rho, const double *sigma, int G, double jitter,
+                                      double *d_out3, double *d_grad, int *d_info);
+
+/* Value AND gradient at G points with ONE LENGTH-SCALE PER DIMENSION and point: ell G x D point-major as in
+ * gpmi_logml_grid_ard; grad G x (D + 2) point-major: grad[g (D + 2)] = d/dalpha, [.. + 1 + d] = d/dell_d,
+ * [.. + D + 1] = d/dsigma.  The several optimiser starts of a fit of QQard's theta (R/kernels.R:11-19), whose likelihood is
+ * multimodal in the length-scales.  Status codes, info and NaN as gpmi_logml_grad_grid; every point has the bits of
+ * gpmi_logml_grad at that point, and the _dev form those of the host form.  D <= 64.  n <= 256 (128 for one point) and
+ * D <= 8: one workgroup per point, any number of points; otherwise the context's lanes.  These three grids return GPMI_EARG
+ * for n < 1, G < 0, D outside 1..64, ldx < n, a NULL pointer or a length-scale <= 0; G = 0 returns 0 and writes nothing. */
+GPMI_API int gpmi_logml_grad_grid_ard(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, const double *y,
+                                      const double *alpha, const double *ell, const double *sigma, int G, double jitter,
+                                      double *out3, double *grad, int *info);
+GPMI_API int gpmi_logml_grad_grid_ard_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                                          const double *alpha, const double *ell, const double *sigma, int G, double jitter,
+                                          double *d_out3, double *d_grad, int *d_info);
+
 /* G independent hyper-parameter points (alpha[g], rho[g], sigma[g]) on the same
  * data: out3[3*g..], info[g].  Non-PD points get NaN and info[g] = k and the
  * grid continues.  Replaces the stan()-fit + arg-max of R/tests.R:13-27 when a

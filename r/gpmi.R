@@ -144,6 +144,15 @@ gp_log_marginal_grad_chains <- function(X, y, alpha, rho, sigma, jitter = 0) {
         rep_len(as.double(sigma), G), jitter)
 }
 
+# value and gradient at G ARD points at once -- the several starts of an optimiser over QQard's length-scales: ell_mat is D x G
+# (column g = the length-scale vector of point g); list(value 3 x G, grad (D + 2) x G = (d/dalpha, d/dell..., d/dsigma), info)
+gp_log_marginal_grad_grid_ard <- function(X, y, alpha, ell_mat, sigma, jitter = 0) {
+  ell_mat <- as.matrix(ell_mat); storage.mode(ell_mat) <- "double"
+  G <- ncol(ell_mat)
+  .Call("gpmi_R_logml_grad_grid_ard", as.matrix(X), as.double(y), rep_len(as.double(alpha), G), ell_mat,
+        rep_len(as.double(sigma), G), jitter)
+}
+
 # the joint [y; y'] model of ode_gp_library.R:29-30: value and gradient w.r.t. (alpha, l, sigma) of the log marginal likelihood
 # of yy = c(y, dy) at the times t, through one factorisation; feeds optim() as gp_log_marginal_grad does
 gpmi_joint_logml_grad <- function(t, y, dy, alpha, l, sigma, jitter = 1e-6)

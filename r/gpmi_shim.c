@@ -398,6 +398,25 @@ SEXP gpmi_R_logml_grad_grid(SEXP X, SEXP y, SEXP alpha, SEXP rho, SEXP sigma, SE
     return out;
 }
 
+/* ... at G points with one length-scale per dimension each (ell: D x G, column g = the length-scales of point g): an unnamed
+ * list of value (3 x G), grad ((D + 2) x G: d/dalpha, d/dell_1 .. d/dell_D, d/dsigma per column) and info (G) */
+SEXP gpmi_R_logml_grad_grid_ard(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), G = Rf_ncols(ell);
+    need(is_real(X) && is_real(y) && is_real(alpha) && is_real(ell) && is_real(sigma), "X, y, alpha, ell, sigma must be double");
+    need(Rf_length(y) == n, "length(y) must equal nrow(X)");
+    need(Rf_nrows(ell) == D, "ell must be ncol(X) x (grid points)");
+    need(Rf_length(alpha) == G && Rf_length(sigma) == G, "alpha and sigma must have one entry per grid point (recycle in R)");
+    SEXP val = PROTECT(Rf_allocMatrix(REALSXP, 3, G)), g = PROTECT(Rf_allocMatrix(REALSXP, D + 2, G)), info = PROTECT(Rf_allocVector(INTSXP, G));
+    int rc = gpmi_logml_grad_grid_ard(ctx(), REAL(X), n, n, D, REAL(y), REAL(alpha), REAL(ell), REAL(sigma), G, Rf_asReal(jitter),
+                                      REAL(val), REAL(g), INTEGER(info));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, val); SET_VECTOR_ELT(out, 1, g); SET_VECTOR_ELT(out, 2, info);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
 /* the joint [y; y'] model (R/ode_gp_library.R:29-30): list(value = c(logml, sum log L_ii, z'z), grad = c(d/dalpha, d/dl,
  * d/dsigma) of logml) through one factorisation of the order-2n matrix; yy = c(y, y') */
 SEXP gpmi_R_joint_logml_grad(SEXP t, SEXP yy, SEXP alpha, SEXP l, SEXP sigma, SEXP jitter)
