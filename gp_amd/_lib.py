@@ -32,11 +32,12 @@ SYMBOLS = (
     "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
     "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy", "gpmi_seq_marginals",
-    "gpmi_gp_predict", "gpmi_gp_predict_dev",
+    "gpmi_gp_predict", "gpmi_gp_predict_dev", "gpmi_gp_predict_joint", "gpmi_gp_predict_joint_dev",
     "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex",
 )
 # additionally exported by the probe build (libgpmi_probes.so, -DGPMI_PROBES; tools/ only)
-PROBE_SYMBOLS = ("gpmi_probe_syrk", "gpmi_probe_mfma", "gpmi_probe_mfma_peak", "gpmi_probe_clock", "gpmi_probe_fused", "gpmi_probe_small", "gpmi_probe_body")
+PROBE_SYMBOLS = ("gpmi_probe_syrk", "gpmi_probe_mfma", "gpmi_probe_mfma_peak", "gpmi_probe_clock", "gpmi_probe_fused", "gpmi_probe_small", "gpmi_probe_body",
+                 "gpmi_probe_tril_draws")
 
 
 class GpmiError(RuntimeError):
@@ -642,6 +643,32 @@ class Context:
                     allow_info=True)
         return {"mean": mean, "var": var, "info": int(info)}
 
+    def gp_predict_joint(self, X, y, alpha, ell, sigma, jitter, Xs, post_jitter=0.0, Z=None, want_cov=True):
+        """Joint posterior of the latent function at the rows of Xs (m x D) given (X, y) under the model of gp_predict:
+        {"mean" (m,), "cov" (m, m) or None, "draws" (m, B) or None, "info"}.  cov = K(Xs, Xs) - Ks Sigma^-1 Ks^T + post_jitter I as
+        computed (both triangles, bit-for-bit symmetric); draws[:, b] = mean + chol(cov) Z[:, b] for the caller's standard-normal
+        Z (m, B).  info = k in 1..n: Sigma is not positive definite at order k (everything NaN); n + k: cov is not (draws NaN)."""
+        X = _mat(X); y = _vec(y); ell = _vec(ell); Xs = _mat(Xs)
+        n, D = X.shape
+        m = Xs.shape[0]
+        if y.size != n or Xs.shape[1] != D:
+            raise GpmiError(-1, "X, y and Xs disagree on N or D")
+        B = 0
+        if Z is not None:
+            Z = np.asarray(Z, dtype=np.float64)
+            Z = np.asfortranarray(Z.reshape(m, -1) if Z.ndim != 2 else Z)
+            if Z.shape[0] != m:
+                raise GpmiError(-1, "Z must have one row per row of Xs")
+            B = Z.shape[1]
+        mean = np.empty(m)
+        cov = np.empty((m, m), order="F") if want_cov else None
+        draws = np.empty((m, B), order="F") if B else None
+        info = _chk(self._lib.gpmi_gp_predict_joint(self._h, _p(X), n, max(n, 1), D, _p(y), _d(alpha), _p(ell), int(ell.size),
+                                                    _d(sigma), _d(jitter), _p(Xs), m, max(m, 1), _d(post_jitter), _p(mean),
+                                                    _p(cov) if want_cov else None, max(m, 1), _p(Z) if B else None, B, max(m, 1),
+                                                    _p(draws) if B else None, max(m, 1)), allow_info=True)
+        return {"mean": mean, "cov": cov, "draws": draws, "info": int(info)}
+
     def sample_derivs(self, t, ts, y, l, a, sy, jitter, z):
         """(draw, mu): mu + chol(cov) z of sample_derivs (pendulum_fit.R:227-255), fused on the device."""
         t = _vec(t); ts = _vec(ts); y = _vec(y); z = _vec(z)
@@ -686,6 +713,16 @@ class Context:
                                            _p(ell), int(ell.size), _d(sigma), _d(jitter), C.c_void_p(dXs_ptr), int(m), int(ldxs),
                                            C.c_void_p(dmean_ptr), C.c_void_p(dvar_ptr) if dvar_ptr else None,
                                            C.c_void_p(dinfo_ptr)))
+
+    def gp_predict_joint_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, ell, sigma, jitter, dXs_ptr, m, ldxs, post_jitter, dmean_ptr,
+                             dcov_ptr, ldc, dZ_ptr, B, ldz, ddraws_ptr, ldd, dinfo_ptr):
+        """gpmi_gp_predict_joint_dev on device pointers (dcov_ptr may be None; dZ_ptr / ddraws_ptr may be None when B == 0);
+        enqueued, not synchronised."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_gp_predict_joint_dev(self._h, C.c_void_p(dX_ptr), int(n), int(ldx), int(D), C.c_void_p(dy_ptr), _d(alpha),
+                                                 _p(ell), int(ell.size), _d(sigma), _d(jitter), C.c_void_p(dXs_ptr), int(m), int(ldxs),
+                                                 _d(post_jitter), C.c_void_p(dmean_ptr), _vp(dcov_ptr), int(ldc), _vp(dZ_ptr), int(B),
+                                                 int(ldz), _vp(ddraws_ptr), int(ldd), C.c_void_p(dinfo_ptr)))
 
     def exact_gp_f_vjp_dev(self, dX_ptr, n, ldx, D, alpha, ell, jitter, dZ_ptr, k, ldz, dFbar_ptr, ldfb, dF_ptr, ldf, dZbar_ptr,
                            ldzb, dgrad_ptr, dinfo_ptr):

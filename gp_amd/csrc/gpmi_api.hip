@@ -439,6 +439,11 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         c->tune.small_pr = value;
         return 0;
     }
+    if (!strcmp(name, "small_pj")) {  // gp_predict_joint by one workgroup up to this many rows n + m + 1 (0: every size takes the chain)
+        if (value < 0 || value > 1024) return gpmi_fail(GPMI_EARG, "small_pj must be 0 .. 1024");
+        c->tune.small_pj = value;
+        return 0;
+    }
     if (!strcmp(name, "predict_mb")) {  // rows of Xs per chunk of the prediction chains (0: auto)
         if (value < 0) return gpmi_fail(GPMI_EARG, "predict_mb must be >= 0");
         c->tune.predict_mb = value;
@@ -3926,6 +3931,125 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
     return 0;
 }
 
+// ---- GP posterior at new D-dimensional inputs: the JOINT distribution -------------------------------------------------
+// Sigma = K(X, X) + (sigma^2 + jitter) I (gpmi_gp_predict's matrix), Ks = K(Xs, X):
+//   mean = Ks Sigma^-1 y,   C = K(Xs, Xs) - Ks Sigma^-1 Ks^T + post_jitter I,   draws[:, b] = mean + chol(C) Z[:, b]
+// -- what create_p_dotXnS (R/ode_gp_library.R:43-93) samples from one point at a time, for all m points at once.  The
+// composition of gpmi_gp_condition / sample_derivs_core with launch_se_cov in place of launch_deriv_cov: one workspace of
+// order n + m + 1 holds [[Sigma, .], [Ks, K(Xs, Xs)]] and the row [y^T, 0]; the partial factorisation of its first n columns
+// leaves the Schur block C - post_jitter I and the row -mean^T; the block is read out (launch_joint_readout), factored in
+// place and multiplied into Z by ONE triangular matrix-matrix product (launch_tril_draws) for every B >= 1.  The route depends
+// on (n, m, D) and the options, never on B: column b of draws has the same bits whatever B is.
+static bool small_predict_joint(const gpmi_ctx *c, int n, int m, int D)
+{
+    return c->tune.small_pj > 0 && (long long)n + m + 1 <= (long long)c->tune.small_pj && D <= GPMI_MAXD;
+}
+
+static int predict_joint_check(int n, int ldx, int D, double alpha, double sigma, int m, int ldxs, bool cov, int ldc, int B, int ldz,
+                               int ldd)
+{
+    int rc;
+    if ((rc = predict_check(n, ldx, D, alpha, sigma, m, ldxs))) return rc;
+    if (B < 0) return gpmi_fail(GPMI_EARG, "negative number of draws");
+    if (cov && ldc < m) return gpmi_fail(GPMI_EARG, "leading dimension of cov smaller than m");
+    if (B > 0 && (ldz < m || ldd < m)) return gpmi_fail(GPMI_EARG, "leading dimension of Z or draws smaller than m");
+    return 0;
+}
+
+// every device buffer predict_joint_core(c, n, m, D) touches, at its final size (a growing buffer synchronises its stream)
+static int predict_joint_reserve(gpmi_ctx *c, int n, int m, int D)
+{
+    if (small_predict_joint(c, n, m, D)) return reserve_ws_small(c, n + m, 1);
+    return reserve_ws(c, n + m + 1, n + m);
+}
+
+// all pointers device; d_cov nullable; dZ / d_draws unused when B == 0; enqueues on c->stream, no synchronisation
+static int predict_joint_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
+                              const double *dXs, int m, int ldxs, double post_jitter, double *d_mean, double *d_cov, int ldc,
+                              const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info)
+{
+    int rc;
+    hipStream_t s = c->stream;
+    if ((rc = predict_joint_reserve(c, n, m, p.D))) return rc;
+    if (small_predict_joint(c, n, m, p.D)) {
+        launch_gp_predict_joint_wg(s, dX, n, ldx, dXs, m, ldxs, dy, p, diag_add, post_jitter, c->W, d_mean, d_cov, (size_t)ldc, dZ, B,
+                                   (size_t)ldz, d_draws, (size_t)ldd, d_info, c->d_info + 2);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    const int nt = n + m, M = nt + 1;
+    const size_t ld = (size_t)c->ld;
+    HIPCHK(hipMemsetAsync(c->d_info, 0, 4 * sizeof(int), s));
+    // [[Sigma, .], [Ks, K(Xs, Xs)]] lower-stored (alpha^2 on the diagonal of the new points: the latent function), the row [y^T, 0]
+    launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, diag_add, 1, c->W, ld);
+    launch_se_cov(c, s, dXs, m, ldxs, dX, n, ldx, p, 0.0, 0, c->W + n, ld);
+    launch_se_cov(c, s, dXs, m, ldxs, nullptr, m, ldxs, p, 0.0, 1, c->W + n + (size_t)n * ld, ld);
+    launch_set_row(s, c->W, ld, nt, dy, n, nt);
+    if ((rc = launch_potrf_partial(c, c->W, ld, M, nt, n, c->d_info, nullptr))) return rc;
+    double *S = c->W + n + (size_t)n * ld;   // Schur complement = C - post_jitter I (lower), rows n .. nt - 1; below it -mean^T
+    launch_joint_readout(s, S, ld, c->W + nt + (size_t)n * ld, m, post_jitter, d_mean, d_cov, (size_t)ldc, c->d_info);
+    if (B > 0) {
+        if ((rc = launch_potrf_partial(c, S, ld, m, m, m, c->d_info + 2, nullptr))) return rc;
+        launch_tril_draws(s, S, ld, m, d_mean, dZ, (size_t)ldz, B, d_draws, (size_t)ldd, c->d_info, c->d_info + 2);
+    }
+    hipLaunchKernelGGL(k_merge_info, dim3(1), 64, 0, s, c->d_info, c->d_info + 2, n, d_info);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_gp_predict_joint_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, double alpha,
+                                         const double *ell, int n_ell, double sigma, double jitter, const double *dXs, int m, int ldxs,
+                                         double post_jitter, double *d_mean, double *d_cov, int ldc, const double *dZ, int B, int ldz,
+                                         double *d_draws, int ldd, int *d_info)
+{
+    ENTER(c);
+    if (!dX || !dy || !dXs || !d_mean || !d_info || (B > 0 && (!dZ || !d_draws))) return gpmi_fail(GPMI_EARG, "NULL argument");
+    int rc;
+    if ((rc = predict_joint_check(n, ldx, D, alpha, sigma, m, ldxs, d_cov != nullptr, ldc, B, ldz, ldd))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    return predict_joint_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dXs, m, ldxs, post_jitter, d_mean, d_cov, ldc, dZ, B, ldz,
+                              d_draws, ldd, d_info);
+}
+
+extern "C" int gpmi_gp_predict_joint(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double alpha,
+                                     const double *ell, int n_ell, double sigma, double jitter, const double *Xs, int m, int ldxs,
+                                     double post_jitter, double *mean, double *cov, int ldc, const double *Z, int B, int ldz,
+                                     double *draws, int ldd)
+{
+    ENTER(c);
+    if (!X || !y || !Xs || !mean || (B > 0 && (!Z || !draws))) return gpmi_fail(GPMI_EARG, "NULL argument");
+    int rc;
+    if ((rc = predict_joint_check(n, ldx, D, alpha, sigma, m, ldxs, cov != nullptr, ldc, B, ldz, ldd))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    const double diag_add = sigma * sigma + jitter;
+    if (small_predict_joint(c, n, m, D)) {
+        // ONE launch: inputs and results travel through the pinned, device-mapped buffer (each input is read once)
+        PinCall pc(c);
+        const size_t mean_ = pc.out(mean, m, 1, m), cov_ = cov ? pc.out(cov, m, m, ldc) : 0, draws_ = B ? pc.out(draws, m, B, ldd) : 0,
+                     X_ = pc.in(X, n, D, ldx), Xs_ = pc.in(Xs, m, D, ldxs), y_ = pc.in(y, n, 1, n), Z_ = B ? pc.in(Z, m, B, ldz) : 0;
+        if ((rc = pc.begin(0, n + m, 1))) return rc;
+        launch_gp_predict_joint_wg(c->stream, pc.dev(X_), n, n, pc.dev(Xs_), m, m, pc.dev(y_), p, diag_add, post_jitter, c->W,
+                                   pc.dev(mean_), cov ? pc.dev(cov_) : nullptr, (size_t)m, B ? pc.dev(Z_) : nullptr, B, (size_t)m,
+                                   B ? pc.dev(draws_) : nullptr, (size_t)m, pc.info(), c->d_info + 2, pc.flag(), pc.seq);
+        return pc.finish();
+    }
+    // the chain: Xs, Z and the results in staging buffer 3 (X and y in 0 and 1); cov == NULL: no m x m staging either
+    if ((rc = predict_joint_reserve(c, n, m, D))) return rc;
+    StageCall sc(c);
+    const size_t Xs_ = sc.in(Xs, m, D, ldxs), Z_ = B ? sc.in(Z, m, B, ldz) : 0, mean_ = sc.out(mean, m, 1, m),
+                 cov_ = cov ? sc.out(cov, m, m, ldc) : 0, draws_ = B ? sc.out(draws, m, B, ldd) : 0;
+    double *dX, *dy;
+    if ((rc = sc.begin(3))) return rc;
+    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
+    if ((rc = predict_joint_core(c, dX, n, n, dy, p, diag_add, sc.dev(Xs_), m, m, post_jitter, sc.dev(mean_),
+                                 cov ? sc.dev(cov_) : nullptr, m, B ? sc.dev(Z_) : nullptr, B, m, B ? sc.dev(draws_) : nullptr, m,
+                                 c->d_info + 1)))
+        return rc;
+    return sc.finish(c->d_info + 1);
+}
+
 // ---- sequential conditional sampler -------------------------------------
 // create_p_dotXnS, R/ode_gp_library.R:43-93.  The reference re-derives, at every call, the joint
 // mean and covariance of ALL star points so far,
@@ -4487,6 +4611,50 @@ extern "C" int gpmi_probe_mfma_peak(gpmi_ctx *c, int iters, double *tflops, doub
             real += h[9 + 2 * b];
         }
         *clock_mhz = real > 0.0 ? cyc / real * 100.0 : 0.0;
+    }
+    return 0;
+}
+
+// draws = mean 1^T + L Z on one m x m lower-triangular factor in the workspace (any finite numbers: the time does not depend on
+// them), B columns: ms2[0] = launch_tril_draws, ms2[1] = the loop of B (launch_trmv_lower + the addition of the mean) that was
+// the tree's only way before it; HIP events around `reps` repetitions each, after one warm-up
+extern "C" int gpmi_probe_tril_draws(gpmi_ctx *c, int m, int B, int reps, double *ms2)
+{
+    ENTER(c);
+    if (m < 1 || B < 1 || reps < 1 || !ms2) return gpmi_fail(GPMI_EARG, "bad argument");
+    int rc;
+    if ((rc = reserve_ws(c, m, m))) return rc;
+    const size_t ld = (size_t)c->ld;
+    double *zd, *part;
+    if ((rc = stage_buf(c, 0, ((size_t)2 * m * B + m) * sizeof(double), &zd))) return rc;
+    if ((rc = stage_buf(c, 3, (size_t)trmv_lower_chunks(m) * m * sizeof(double), &part))) return rc;
+    double *dr = zd + (size_t)m * B, *mu = dr + (size_t)m * B;
+    hipStream_t s = c->stream;
+    std::vector<double> h((size_t)m * B + m);
+    for (size_t i = 0; i < h.size(); ++i) h[i] = (double)((i * 2654435761u) % 2001u) * 1e-3 - 1.0;
+    HIPCHK(hipMemcpyAsync(zd, h.data(), (size_t)m * B * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(mu, h.data() + (size_t)m * B, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_info, 0, 4 * sizeof(int), s));
+    SeParams p;
+    const double one = 1.0;
+    if ((rc = fill_params(&p, 1, 1.0, &one, 1))) return rc;
+    launch_se_cov(c, s, mu, m, m, nullptr, m, m, p, 1.0, 1, c->W, ld);   // a lower triangle of numbers in (0, 2]
+    for (int mode = 0; mode < 2; ++mode) {
+        for (int r = -1; r < reps; ++r) {
+            if (r == 0) HIPCHK(hipEventRecord(c->ev[0], s));
+            if (mode == 0) launch_tril_draws(s, c->W, ld, m, mu, zd, (size_t)m, B, dr, (size_t)m, c->d_info, c->d_info + 2);
+            else
+                for (int b = 0; b < B; ++b) {
+                    launch_trmv_lower(s, c->W, ld, m, zd + (size_t)b * m, dr + (size_t)b * m, part);
+                    hipLaunchKernelGGL(k_axpy1, dim3((m + 255) / 256), 256, 0, s, dr + (size_t)b * m, mu, m);
+                }
+        }
+        HIPCHK(hipEventRecord(c->ev[1], s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        ms2[mode] = (double)ms / reps;
     }
     return 0;
 }

@@ -68,6 +68,7 @@ struct gpmi_tuning {
     int small_gc;            // gpmi_gp_condition: one workgroup, one launch, up to n + m + 1 <= small_gc rows (0: off)
     int small_pr;            // gpmi_gp_predict[_dev]: one workgroup, one launch, up to n + m + 1 <= small_pr rows and D <= GPMI_MAXD (0: off)
     int predict_mb;          // gpmi_gp_predict / gpmi_seq_marginals: rows of Xs per chunk of the blocked chain (0: auto)
+    int small_pj;            // gpmi_gp_predict_joint[_dev]: one workgroup, one launch, up to n + m + 1 <= small_pj rows and D <= GPMI_MAXD (0: off)
     int small_sd, small_sdb; // sample_derivs_batch: one workgroup per draw when n + m + 1 <= small_sd rows and at least small_sdb (n + m + 1)^2 / 400^2 draws (0: off)
     int small_n2, small_g2;  // grids of >= small_g2 (n / 1024)^2 + 2 points: one workgroup per point up to n <= small_n2 (every CU a problem of its own)
 };
@@ -269,6 +270,12 @@ void launch_gp_condition_small(hipStream_t s, const double *t, int n, const doub
 void launch_gp_predict_small(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const double *y,
                              const SeParams &p, double diag_add, double *W, double *mean, double *var, int *info_out, int *d_info_work,
                              int *done = nullptr, int seq = 0);
+// gp_predict_joint by one workgroup (workspace: one slice of small_ws_layout(n + m), n + m <= 1023, D <= GPMI_MAXD; d_info_work: 2
+// ints); every pointer but W and d_info_work may be host-mapped (each input is read once); cov nullable, Z / draws unused at B == 0
+void launch_gp_predict_joint_wg(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const double *y,
+                                const SeParams &p, double diag_add, double post_jitter, double *W, double *mean, double *cov, size_t ldc,
+                                const double *Z, int B, size_t ldz, double *draws, size_t ldd, int *info_out, int *d_info_work,
+                                int *done = nullptr, int seq = 0);
 // f = chol(K + diag_add I) z by one workgroup (n <= 256, D <= GPMI_MAXD); X, z / f, info_out may be host-mapped (stage != null)
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,
                            double *W, double *f, int *info_out, int *d_info_work, double *stage, int *done = nullptr, int seq = 0);
@@ -358,3 +365,12 @@ void launch_trsv_lower_t(hipStream_t s, const double *L, size_t ldl, int n, doub
 // mean[j] = sum_i k(xs_j, x_i) a_i without storing the cross-covariance: entries as gpmi_se_cov writes them
 void launch_predict_mean(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const SeParams &p,
                          const double *a, double *part, double *mean, const int *info, int *info_out);
+// read-out of the joint posterior's chain: S (m x m, lower, ld) is the Schur block, row[r * ld] = -mean[r].  mean is written,
+// post_jitter is added to the diagonal of S IN PLACE, and cov (nullable; ldc) receives S mirrored; *info != 0 -> NaN outputs
+void launch_joint_readout(hipStream_t s, double *S, size_t ld, const double *row, int m, double post_jitter, double *mean, double *cov,
+                          size_t ldc, const int *info);
+// draws = mean 1^T + L Z for the m x m lower-triangular L (ldl; its strict upper part is never read) and B columns (Z: ldz,
+// draws: ldd), one MFMA product; a column's bits do not depend on B or on the other columns.  *info_a or *info_b (nullable)
+// non-zero -> every draw is NaN
+void launch_tril_draws(hipStream_t s, const double *L, size_t ldl, int m, const double *mean, const double *Z, size_t ldz, int B,
+                       double *draws, size_t ldd, const int *info_a, const int *info_b);

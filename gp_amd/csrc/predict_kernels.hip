@@ -193,7 +193,146 @@ __global__ __launch_bounds__(256) void k_predict_mean_sum(const double *__restri
     mean[j] = bad ? __builtin_nan("") : sm;
 }
 
+// ---- the ends of the joint posterior's chain (gpmi_gp_predict_joint) -------------------------------------------------
+// After the augmented partial factorisation the workspace holds the Schur block S (m x m, lower) and, in the row below it,
+// -mean^T.  mean[r] = -row[r] and S[r, r] += post_jitter (thread = r: the only writer of that element) ...
+__global__ __launch_bounds__(256) void k_joint_mean_diag(double *__restrict__ S, size_t ld, const double *__restrict__ row, int m,
+                                                         double post_jitter, double *__restrict__ mean, const int *info)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= m) return;
+    mean[r] = *info ? __builtin_nan("") : -row[(size_t)r * ld];
+    S[(size_t)r * (ld + 1)] += post_jitter;
+}
+
+// ... then cov = S mirrored (both triangles from the SAME stored element: bit-for-bit symmetric), NaN when *info != 0.
+// thread = row, 64 rows x 16 columns per workgroup; the upper half reads S along its columns as well (the element (c, r))
+__global__ __launch_bounds__(256) void k_joint_cov(const double *__restrict__ S, size_t ld, int m, double *__restrict__ cov, size_t ldc,
+                                                   const int *info)
+{
+    __shared__ double s_t[16][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 16;
+    const int bad = *info;
+    // upper part of this block (r < c): the 16 x 64 piece S[c0 .. c0 + 16, r0 .. r0 + 64) read with the lanes along its rows c
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = q * 256 + (int)threadIdx.x, cc = e & 15, rr = e >> 4;
+        const int c = c0 + cc, r = r0 + rr;
+        s_t[cc][rr] = (c < m && r < c) ? S[(size_t)c + (size_t)r * ld] : 0.0;
+    }
+    __syncthreads();
+    const int r = r0 + tx;
+    if (r >= m) return;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int cc = ty * 4 + q, c = c0 + cc;
+        if (c < m) {
+            const double v = (r >= c) ? S[(size_t)r + (size_t)c * ld] : s_t[cc][tx];
+            cov[(size_t)r + (size_t)c * ldc] = bad ? __builtin_nan("") : v;
+        }
+    }
+}
+
+// Draws = mean 1^T + Lc Z: Lc m x m lower (leading dimension ldl; whatever lies above its diagonal is never used), Z and
+// Draws m x B.  A lower-triangular matrix-matrix product on v_mfma_f64_16x16x4_f64 with the operand conventions of gemm_tile
+// (gpmi_probe_mfma): lane l gives A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15] and receives D[row (l >> 4) + 4 i][col l & 15]
+// in element i.  A workgroup owns TD_R = 64 rows (wave w rows 16 w .. 16 w + 15) and up to 64 columns (four accumulator tiles
+// per wave) and walks k in chunks of TD_K = 32 from 0 to the end of its diagonal tile: the chunk of Lc (64 x 32, elements with
+// k > row and rows >= m replaced by exact zeros) and of Z (32 x 64, zeros past m and B) are loaded into registers one chunk
+// ahead of the MFMAs and passed through LDS.  Lc is therefore read once per 64 columns of Z (launch_trmv_lower: once per column).
+// LDS images (ds_read_b64 serves 32 lanes per pass, 64 banks of 4 bytes):
+//   s_a[k][row], stride 80 doubles: a pass reads rows lr = 0..15 of k and k + 1: 160 dwords apart = 32 banks -> all 64 distinct;
+//   s_z[col][k], stride 34 doubles: a pass reads columns lr = 0..15 (68 dwords apart = 4 banks) at k, k + 1 (2 dwords) -> distinct.
+// Every output element is one accumulator element summed over k = 0, 1, 2, ... in chunks that depend on its row tile alone:
+// column b has the same bits whatever B is and whatever the other columns hold.  The tile is written out through LDS so that
+// the stores run along the columns of Draws.  info_a / info_b (device; info_b nullable): non-zero -> every draw is NaN.
+constexpr int TD_R = 64, TD_K = 32, TD_C = 64, TD_SA = 80, TD_SZ = 34, TD_SO = 66;
+__global__ __launch_bounds__(256) void k_tril_draws(const double *__restrict__ L, size_t ldl, int m, const double *__restrict__ mean,
+                                                    const double *__restrict__ Z, size_t ldz, int B, double *__restrict__ draws,
+                                                    size_t ldd, const int *info_a, const int *info_b)
+{
+    static_assert(TD_K * TD_SA + TD_C * TD_SZ >= TD_C * TD_SO, "the output tile reuses the operand images");
+    __shared__ double s_buf[TD_K * TD_SA + TD_C * TD_SZ];
+    double *s_a = s_buf, *s_z = s_buf + TD_K * TD_SA;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+    const int i0 = ((int)gridDim.x - 1 - (int)blockIdx.x) * TD_R;   // the long row tiles start first
+    const int c0 = blockIdx.y * TD_C;
+    const int kend = i0 + TD_R < m ? i0 + TD_R : m;
+    const int nch = (kend + TD_K - 1) / TD_K;
+    const int nct = (B - c0 + 15) / 16 < 4 ? (B - c0 + 15) / 16 : 4;   // column tiles in use (workgroup-uniform)
+    const int gr = i0 + lane;                       // staging of Lc: row `lane`, k = w + 4 j
+    const int zk = tid & (TD_K - 1), zc = tid >> 5;  // staging of Z: k = zk, column zc + 8 j
+    double pa[8], pz[8];
+    auto gload = [&](int k0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int gk = k0 + w + 4 * j;
+            pa[j] = (gr < m && gk <= gr) ? L[(size_t)gr + (size_t)gk * ldl] : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int gk = k0 + zk, gc = c0 + zc + 8 * j;
+            pz[j] = (gk < m && gc < B) ? Z[(size_t)gk + (size_t)gc * ldz] : 0.0;
+        }
+    };
+    d4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
+    gload(0);
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();   // the previous chunk's fragments have been read
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s_a[(w + 4 * j) * TD_SA + lane] = pa[j];
+            s_z[(zc + 8 * j) * TD_SZ + zk] = pz[j];
+        }
+        __syncthreads();
+        if (ch + 1 < nch) gload((ch + 1) * TD_K);
+#pragma unroll
+        for (int kk = 0; kk < TD_K / 4; ++kk) {
+            const double a = s_a[(4 * kk + lq) * TD_SA + 16 * w + lr];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (t < nct) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, s_z[(16 * t + lr) * TD_SZ + 4 * kk + lq], acc[t], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+    double *s_o = s_buf;   // [column][row], stride TD_SO
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (t < nct) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s_o[(16 * t + lr) * TD_SO + 16 * w + lq + 4 * i] = acc[t][i];
+        }
+    __syncthreads();
+    const int bad = *info_a | (info_b ? *info_b : 0);
+    if (gr < m) {
+        const double mu = mean[gr];
+        for (int col = w; col < 16 * nct; col += 4) {
+            const int gc = c0 + col;
+            if (gc < B) draws[(size_t)gr + (size_t)gc * ldd] = bad ? __builtin_nan("") : s_o[col * TD_SO + lane] + mu;
+        }
+    }
+}
+
 }  // namespace
+
+void launch_joint_readout(hipStream_t s, double *S, size_t ld, const double *row, int m, double post_jitter, double *mean, double *cov,
+                          size_t ldc, const int *info)
+{
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_joint_mean_diag, dim3((m + 255) / 256), 256, 0, s, S, ld, row, m, post_jitter, mean, info);
+    if (cov) hipLaunchKernelGGL(k_joint_cov, dim3((m + 63) / 64, (m + 15) / 16), 256, 0, s, S, ld, m, cov, ldc, info);
+}
+
+void launch_tril_draws(hipStream_t s, const double *L, size_t ldl, int m, const double *mean, const double *Z, size_t ldz, int B,
+                       double *draws, size_t ldd, const int *info_a, const int *info_b)
+{
+    if (m <= 0 || B <= 0) return;
+    hipLaunchKernelGGL(k_tril_draws, dim3((m + TD_R - 1) / TD_R, (B + TD_C - 1) / TD_C), 256, 0, s, L, ldl, m, mean, Z, ldz, B, draws,
+                       ldd, info_a, info_b);
+}
 
 size_t predict_rows_part_doubles(int n, int mrows)
 {

@@ -926,6 +926,94 @@ __global__ __launch_bounds__(256, 2) void k_gp_predict_small(const double *__res
     small_signal_done(done, seq);
 }
 
+// gpmi_gp_predict_joint (the JOINT posterior at m new D-dimensional inputs: mean, covariance and draws; what create_p_dotXnS,
+// R/ode_gp_library.R:43-93, conditions on, without its sequential loop) by ONE workgroup: the build and the first partial
+// factorisation of k_gp_predict_small; then mean = minus the last row and cov = the mirrored Schur block + post_jitter I
+// (k_gp_condition_small's read-out); then, for B > 0 columns, the second factorisation in place and draws[:, b] = mean + Lc Z[:, b]
+// by the row loop of k_sample_derivs_small_batch, column b of Z staged in LDS (read once: Z may be host-mapped like every
+// other pointer but W and info_w).  A row's sum runs over its columns in order with one accumulator, whatever B is.
+// status: 0, k (Sigma not PD at order k: every output NaN), n + k (cov not PD: draws NaN, mean and cov as with B = 0).
+__global__ __launch_bounds__(256, 2) void k_gp_predict_joint_wg(const double *__restrict__ X, int n, int ldx, const double *__restrict__ Xs,
+                                                             int m, int ldxs, const double *__restrict__ y, SeParams p, double diag_add,
+                                                             double post_jitter, double *__restrict__ W, size_t ld,
+                                                             double *__restrict__ mean, double *__restrict__ cov, size_t ldc,
+                                                             const double *__restrict__ Z, int B, size_t ldz,
+                                                             double *__restrict__ draws, size_t ldd, int *info_out, int *info_w, ExpC ec,
+                                                             int *done, int seq)
+{
+    GPMI_SMALL_LDS
+    int tid = threadIdx.x;
+    const int nt = n + m;
+    if (tid < 2) info_w[tid] = 0;
+    const SmallSe se = small_se(p.a2, p.inv_ell, p.D);
+    {
+        double *xs = &smem[0][0][0][0];   // nt * D <= 1024 * GPMI_MAXD doubles fit the tile staging buffer
+#pragma unroll
+        for (int d = 0; d < GPMI_MAXD; ++d)
+            if (d < se.D)
+                for (int i = tid; i < nt; i += 256)
+                    xs[i + d * nt] = __dmul_rn(i < n ? X[(size_t)i + (size_t)d * ldx] : Xs[(size_t)(i - n) + (size_t)d * ldxs], se.inv_ell[d]);
+        __syncthreads();
+        small_se_build(xs, nt, se, diag_add, W, ld, ec);
+    }
+    __syncthreads();
+    for (int i = n + tid; i < nt; i += 256) W[(size_t)i * (ld + 1)] = se.a2;
+    for (int j = tid; j < nt; j += 256) W[(size_t)nt + (size_t)j * ld] = j < n ? y[j] : 0.0;
+    __syncthreads();
+    small_potrf_partial(smem, s_F, s_aux, W, ld, nt + 1, nt, n, info_w, false);
+    __syncthreads();
+    asm volatile("" : "+v"(tid));
+    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double *S = W + (size_t)n + (size_t)n * ld;   // Schur complement (lower), rows n .. nt - 1
+    // thread = row: its own diagonal element takes post_jitter (for the read-out and for the factorisation below); nothing else
+    // of the block is written here, so no thread reads what another one changes
+    for (int r = tid; r < m; r += 256) {
+        mean[r] = info ? __builtin_nan("") : -W[(size_t)nt + (size_t)(n + r) * ld];
+        S[(size_t)r * (ld + 1)] += post_jitter;
+        if (cov)
+            for (int c = 0; c < m; ++c) {
+                const double v = (r >= c) ? S[(size_t)r + (size_t)c * ld] : S[(size_t)c + (size_t)r * ld];
+                cov[(size_t)r + (size_t)c * ldc] = info ? __builtin_nan("") : v;
+            }
+    }
+    int info2 = 0;
+    if (B > 0) {   // kernel argument: workgroup-uniform
+        __syncthreads();
+        if (!info) {
+            small_potrf_partial(smem, s_F, s_aux, S, ld, m, m, m, info_w + 1, false);
+            __syncthreads();
+            asm volatile("" : "+v"(tid));
+            info2 = __hip_atomic_load(info_w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        const bool bad = info || info2;
+        double *zl = &smem[0][0][0][0];   // m <= 1023 doubles
+        for (int b = 0; b < B; ++b) {
+            for (int j = tid; j < m; j += 256) zl[j] = Z[(size_t)j + (size_t)b * ldz];
+            __syncthreads();
+            for (int i0 = 0; i0 < m; i0 += 256) {
+                const int i = i0 + tid, ic = i < m ? i : m - 1;
+                double acc = 0.0;
+                const int jend = (i0 + 255 < m ? i0 + 255 : m - 1);   // workgroup-uniform bound; columns > i contribute nothing
+                for (int j0 = 0; j0 <= jend; j0 += 16) {
+                    double u[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int j = j0 + q <= ic ? j0 + q : ic;
+                        u[q] = S[(size_t)ic + (size_t)j * ld];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if (j0 + q <= ic) acc = fma(u[q], zl[j0 + q], acc);
+                }
+                if (i < m) draws[(size_t)i + (size_t)b * ldd] = bad ? __builtin_nan("") : acc - W[(size_t)nt + (size_t)(n + i) * ld];
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) *info_out = info ? info : (info2 ? n + info2 : 0);
+    small_signal_done(done, seq);
+}
+
 // f = chol(cov_exp_quad(X, alpha, ell) + diag_add I) z (models/exact_gp.stan:17-25: the latent exact GP's transform, once per
 // leapfrog step with a new length-scale) by ONE workgroup for n <= 256: build (se_cov_tile), factorisation, and the row sums
 // f_i = sum_{j <= i} L_ij z_j in column order (the order of k_trmv_lower_part inside its first chunk).  stage (nullable): X, z
@@ -1800,6 +1888,17 @@ void launch_gp_predict_small(hipStream_t s, const double *X, int n, int ldx, con
     small_ws_layout(n + m, &ld, &stride);
     launch_small<k_gp_predict_small>(1, SMALL_LDS_DOUBLES, s, X, n, ldx, Xs, m, ldxs, y, p, diag_add, W,
                        ld, mean, var, info_out, d_info_work, h_exp, done, seq);
+}
+
+void launch_gp_predict_joint_wg(hipStream_t s, const double *X, int n, int ldx, const double *Xs, int m, int ldxs, const double *y,
+                                const SeParams &p, double diag_add, double post_jitter, double *W, double *mean, double *cov, size_t ldc,
+                                const double *Z, int B, size_t ldz, double *draws, size_t ldd, int *info_out, int *d_info_work, int *done,
+                                int seq)
+{
+    size_t ld, stride;
+    small_ws_layout(n + m, &ld, &stride);
+    launch_small<k_gp_predict_joint_wg>(1, SMALL_LDS_DOUBLES, s, X, n, ldx, Xs, m, ldxs, y, p, diag_add, post_jitter, W, ld, mean, cov,
+                       ldc, Z, B, ldz, draws, ldd, info_out, d_info_work, h_exp, done, seq);
 }
 
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,

@@ -89,7 +89,8 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * problems), "small_ng1", "small_ng" (value + gradient by one workgroup: one evaluation up to n <= small_ng1, several at once
  * up to n <= small_ng <= 256), "grad_aug_n", "grad_aug_ng" (value + gradient through ONE augmented partial factorisation up
  * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_pr" (gpmi_gp_predict[_dev] in
- * one launch up to n + m + 1 <= small_pr rows and D <= 8; 0 sends every size to the blocked chain), "predict_mb" (rows of Xs per chunk of the
+ * one launch up to n + m + 1 <= small_pr rows and D <= 8; 0 sends every size to the blocked chain), "small_pj" (the same for
+ * gpmi_gp_predict_joint[_dev], 0 .. 1024), "predict_mb" (rows of Xs per chunk of the
  * chains of gpmi_gp_predict / gpmi_seq_marginals; 0 = auto, about n / 4), "small_vjp" (gpmi_exact_gp_f_vjp[_dev] by
  * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_cen" (gpmi_centered_gp_lp_grad[_dev] by one
  * workgroup up to n <= small_cen <= 256 (default 192: the measured crossover), D <= 8, k <= 8; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
@@ -427,6 +428,34 @@ GPMI_API int gpmi_gp_predict_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx
                         double alpha, const double *ell, int n_ell, double sigma, double jitter,
                         const double *dXs, int m, int ldxs, double *d_mean, double *d_var /* nullable */, int *d_info);
 
+/* JOINT posterior of the latent function at the m new inputs Xs under the same model (Sigma, ell / n_ell as in gpmi_gp_predict):
+ *   mean = Ks Sigma^-1 y,   C = K(Xs, Xs) - Ks Sigma^-1 Ks^T + post_jitter I,   draws[:, b] = mean + chol(C) Z[:, b],   Ks = K(Xs, X)
+ * -- the distribution create_p_dotXnS (R/ode_gp_library.R:43-93) samples from point by point, for all m points in one call.  C is
+ * the LATENT function's covariance as computed, not clamped (the caller puts sigma^2 for new observations into post_jitter; any
+ * finite value, negative included).  cov (m x m, ldc; nullable) receives C with both triangles written, bit-for-bit symmetric;
+ * with cov == NULL the m x m matrix never leaves the device.  Z (m x B, ldz) holds the caller's standard-normal variates, draws
+ * (m x B, ldd) the B draws; both may be NULL iff B == 0, and then C is not factored.  n + m + 1 <= small_pj rows and D <= 8: one
+ * launch of one workgroup; otherwise one workspace of (n + m + 1)^2 doubles, two partial factorisations and one triangular
+ * matrix-matrix product (GPMI_ENOMEM when the workspace cannot be allocated).  The route depends on (n, m, D) and the options,
+ * never on B, and all sums run in a fixed order: repeated calls give identical bits, and column b of draws has the same bits
+ * whatever B is and whatever the other columns of Z hold.  Status: 0; k in 1..n: Sigma is not positive definite at order k and
+ * every output is NaN; n + k: C is not positive definite at order k, mean and cov are valid (the bits of the same call with
+ * B = 0) and draws are all NaN.  GPMI_EARG: n or m < 1, B < 0, D outside 1..64, ldx < n, ldxs < m, ldc < m with cov, ldz < m or
+ * ldd < m with B > 0, alpha <= 0, a length-scale <= 0, sigma < 0, a NULL pointer other than cov (and Z / draws when B == 0). */
+GPMI_API int gpmi_gp_predict_joint(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, const double *y,
+                    double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                    const double *Xs, int m, int ldxs, double post_jitter,
+                    double *mean /* m */, double *cov /* m x m, nullable */, int ldc,
+                    const double *Z /* m x B */, int B, int ldz, double *draws /* m x B */, int ldd);
+/* the same with device-resident X, y, Xs, mean, cov, Z, draws and d_info (1 int): enqueued on the context's stream, not
+ * synchronised; the return value says only whether the work was enqueued, the device writes d_info and the NaNs.  Nothing
+ * outside the m rows of a column is written */
+GPMI_API int gpmi_gp_predict_joint_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                    double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                    const double *dXs, int m, int ldxs, double post_jitter,
+                    double *d_mean, double *d_cov /* nullable */, int ldc,
+                    const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info);
+
 /* One draw of the derivative process given noisy values: sample_derivs(params = (l, a, sy), ynoise, ti),
  * pendulum_fit.R:227-255 (separate prediction times ts: lorenz.Rmd:80-107, jitter 1e-6 there, 1e-8 here):
  * draw = mu + chol(cov) z with the (QQ, RQ, RR) moments of gpmi_gp_condition, fused on the device -- the
@@ -522,6 +551,10 @@ GPMI_API int gpmi_probe_mfma(gpmi_ctx *ctx, const double *A64, const double *B64
  * the whole chip and (nullable) the shader clock held meanwhile, from
  * d(s_memtime)/d(s_memrealtime). */
 GPMI_API int gpmi_probe_mfma_peak(gpmi_ctx *ctx, int iters, double *tflops, double *clock_mhz);
+/* The product of gpmi_gp_predict_joint's chain, draws = mean 1^T + L Z, on one m x m lower factor and B columns in device
+ * memory: ms2[0] = milliseconds per call of the triangular matrix-matrix kernel, ms2[1] = of a loop of B one-column
+ * products (what it replaced); HIP events around `reps` repetitions each. */
+GPMI_API int gpmi_probe_tril_draws(gpmi_ctx *ctx, int m, int B, int reps, double *ms2);
 #endif /* GPMI_PROBES */
 
 #ifdef __cplusplus

@@ -218,3 +218,14 @@ gp_predict <- function(X, y, alpha, rho, sigma, Xs, jitter = 0) {
   r <- .Call("gpmi_R_gp_predict", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter, as.matrix(Xs) + 0.0)
   list(mean = r[[1]], var = r[[2]])
 }
+
+# the JOINT posterior at the rows of Xs under the same model: list(mean, cov, draws) with cov = K(Xs, Xs) - Ks Sigma^-1 t(Ks) +
+# post_jitter I (the latent function's covariance as computed; put sigma^2 into post_jitter for new observations) and
+# draws = mean + t(chol(cov)) %*% Z for B = n_draws columns of R's own rnorm -- all m points of create_p_dotXnS's loop
+# (R/ode_gp_library.R:43-93) in one call; n_draws = 0: no draws, cov is not factored
+gp_predict_joint <- function(X, y, alpha, rho, sigma, Xs, jitter = 0, post_jitter = 0, n_draws = 0) {
+  Xs <- as.matrix(Xs) + 0.0
+  Z <- matrix(rnorm(nrow(Xs) * n_draws), nrow(Xs), n_draws)
+  r <- .Call("gpmi_R_gp_predict_joint", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter, Xs, post_jitter, Z)
+  list(mean = r[[1]], cov = r[[2]], draws = r[[3]])
+}

@@ -527,6 +527,29 @@ SEXP gpmi_R_gp_predict(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP ji
     return out;
 }
 
+/* list(mean, cov, draws): the JOINT posterior of the latent function at the rows of Xs under the same model -- cov = K(Xs, Xs) -
+ * Ks Sigma^-1 Ks' + post_jitter I (m x m) and draws = mean + chol(cov) Z for the caller's Z = matrix(rnorm(m * B), m, B) (R's own
+ * RNG stream); Z with zero columns: no draws, cov is not factored */
+SEXP gpmi_R_gp_predict_joint(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter, SEXP Xs, SEXP post_jitter, SEXP Z)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), m = Rf_nrows(Xs), B = Rf_ncols(Z);
+    need(is_real(X) && is_real(y) && is_real(ell) && is_real(Xs) && is_real(Z), "X, y, the length-scales, Xs and Z must be double");
+    need(Rf_length(y) == n, "length(y) must equal nrow(X)");
+    need(Rf_ncols(Xs) == D, "Xs must have ncol(X) columns");
+    need(Rf_length(ell) == 1 || Rf_length(ell) == D, "length-scale must have length 1 or ncol(X)");
+    need(Rf_nrows(Z) == m, "Z must have nrow(Xs) rows");
+    SEXP mean = PROTECT(Rf_allocVector(REALSXP, m)), cov = PROTECT(Rf_allocMatrix(REALSXP, m, m)),
+         draws = PROTECT(Rf_allocMatrix(REALSXP, m, B));
+    int rc = gpmi_gp_predict_joint(ctx(), REAL(X), n, n, D, REAL(y), Rf_asReal(alpha), REAL(ell), Rf_length(ell), Rf_asReal(sigma),
+                                   Rf_asReal(jitter), REAL(Xs), m, m, Rf_asReal(post_jitter), REAL(mean), REAL(cov), m,
+                                   B > 0 ? REAL(Z) : NULL, B, m, B > 0 ? REAL(draws) : NULL, m);
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, mean); SET_VECTOR_ELT(out, 1, cov); SET_VECTOR_ELT(out, 2, draws);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
 /* sample_derivs(params, ynoise, ti): pendulum_fit.R:227-255, one draw mu + chol(cov) z fused on the device; z = rnorm(m)
  * comes from R's own RNG (the reference's MASS::mvrnorm stream cannot be reproduced: eigen-decomposition draw) */
 SEXP gpmi_R_sample_derivs(SEXP t, SEXP ts, SEXP y, SEXP params, SEXP jitter, SEXP z)
