@@ -33,11 +33,12 @@ SYMBOLS = (
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
     "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy", "gpmi_seq_marginals",
     "gpmi_gp_predict", "gpmi_gp_predict_dev", "gpmi_gp_predict_joint", "gpmi_gp_predict_joint_dev",
+    "gpmi_joint_predict", "gpmi_joint_predict_dev",
     "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex",
 )
 # additionally exported by the probe build (libgpmi_probes.so, -DGPMI_PROBES; tools/ only)
 PROBE_SYMBOLS = ("gpmi_probe_syrk", "gpmi_probe_mfma", "gpmi_probe_mfma_peak", "gpmi_probe_clock", "gpmi_probe_fused", "gpmi_probe_small", "gpmi_probe_body",
-                 "gpmi_probe_tril_draws")
+                 "gpmi_probe_tril_draws", "gpmi_probe_joint_star")
 
 
 class GpmiError(RuntimeError):
@@ -668,6 +669,46 @@ class Context:
                                                     _p(cov) if want_cov else None, max(m, 1), _p(Z) if B else None, B, max(m, 1),
                                                     _p(draws) if B else None, max(m, 1)), allow_info=True)
         return {"mean": mean, "cov": cov, "draws": draws, "info": int(info)}
+
+    def joint_predict(self, t, yy, alpha, l, sigma, jitter, ts, orders, post_jitter, Z=None, want_cov=True):
+        """Posterior of f, f', f'' at the m times ts given yy = [y; y'] at the n times t under the joint model of joint_logml:
+        {"mean" (p m,), "cov" (p m, p m) or None, "draws" (p m, B) or None, "info"}, stacked by derivative order (m rows each) for
+        the p orders in the bit mask `orders` (1: f, 2: f', 4: f'').  cov = Kss - Ks S^-1 Ks^T + post_jitter[a] on the diagonal of
+        block a (both triangles, bit-for-bit symmetric); draws[:, b] = mean + chol(cov) Z[:, b] for the caller's standard-normal
+        Z (p m, B).  info = k in 1..2n: S is not positive definite at order k (everything NaN); 2n + k: cov is not (draws NaN)."""
+        t = _vec(t); yy = _vec(yy); ts = _vec(ts); post_jitter = _vec(post_jitter)
+        n, m, orders = t.size, ts.size, int(orders)
+        p = bin(orders & 7).count("1") if 1 <= orders <= 7 else 1
+        if yy.size != 2 * n:
+            raise GpmiError(-1, "yy must hold 2 n values")
+        if post_jitter.size != p:
+            raise GpmiError(-1, "post_jitter must hold one value per requested order")
+        pm = p * m
+        B = 0
+        if Z is not None:
+            Z = np.asarray(Z, dtype=np.float64)
+            Z = np.asfortranarray(Z.reshape(pm, -1) if Z.ndim != 2 else Z)
+            if Z.shape[0] != pm:
+                raise GpmiError(-1, "Z must have one row per requested order and time")
+            B = Z.shape[1]
+        mean = np.empty(pm)
+        cov = np.empty((pm, pm), order="F") if want_cov else None
+        draws = np.empty((pm, B), order="F") if B else None
+        info = _chk(self._lib.gpmi_joint_predict(self._h, _p(t), n, _p(yy), _d(alpha), _d(l), _d(sigma), _d(jitter), _p(ts), m, orders,
+                                                 _p(post_jitter), _p(mean), _p(cov) if want_cov else None, max(pm, 1),
+                                                 _p(Z) if B else None, B, max(pm, 1), _p(draws) if B else None, max(pm, 1)),
+                    allow_info=True)
+        return {"mean": mean, "cov": cov, "draws": draws, "info": int(info)}
+
+    def joint_predict_dev(self, dt_ptr, n, dyy_ptr, alpha, l, sigma, jitter, dts_ptr, m, orders, post_jitter, dmean_ptr, dcov_ptr, ldc,
+                          dZ_ptr, B, ldz, ddraws_ptr, ldd, dinfo_ptr):
+        """gpmi_joint_predict_dev on device pointers (post_jitter: host values, one per requested order; dcov_ptr may be None;
+        dZ_ptr / ddraws_ptr may be None when B == 0); enqueued, not synchronised."""
+        post_jitter = _vec(post_jitter)
+        _chk(self._lib.gpmi_joint_predict_dev(self._h, C.c_void_p(dt_ptr), int(n), C.c_void_p(dyy_ptr), _d(alpha), _d(l), _d(sigma),
+                                              _d(jitter), C.c_void_p(dts_ptr), int(m), int(orders), _p(post_jitter),
+                                              C.c_void_p(dmean_ptr), _vp(dcov_ptr), int(ldc), _vp(dZ_ptr), int(B), int(ldz),
+                                              _vp(ddraws_ptr), int(ldd), C.c_void_p(dinfo_ptr)))
 
     def sample_derivs(self, t, ts, y, l, a, sy, jitter, z):
         """(draw, mu): mu + chol(cov) z of sample_derivs (pendulum_fit.R:227-255), fused on the device."""

@@ -1267,7 +1267,9 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->small_gc = 180;    // gpmi_gp_condition by one workgroup up to n + m + 1 rows (tools/cond_bench.py)
     t->small_pr = 180;    // gpmi_gp_predict by one workgroup up to n + m + 1 rows (tools/predict_bench.py)
     t->small_pj = 300;    // gpmi_gp_predict_joint by one workgroup up to n + m + 1 rows: the crossover at B = 1 (tools/predict_joint_bench.py)
-    t->predict_mb = 0;    // rows of Xs per chunk of the blocked prediction chain (0: auto, about n / 4)
+    t->small_jp = 220;    // gpmi_joint_predict by one workgroup up to 2n + p m + 1 rows: the crossover at B = 1, p = 3 (tools/joint_predict_bench.py
+                          // --crossover: 165 / 187 us one workgroup / chain at 201 rows, 265 / 228 at 251)
+    t->predict_mb = 0;   // rows of Xs per chunk of the blocked prediction chain (0: auto, about n / 4)
     t->small_sd = 640;
     t->small_sdb = 5;     // tools/sample_derivs_bench.py: one workgroup 0.21 / 0.56 / 0.73 ms at n = m = 79 / 199 / 256, the lanes 95 / 136 / 129 us per draw
     t->small_n2 = 1024;

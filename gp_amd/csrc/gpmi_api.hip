@@ -444,6 +444,11 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         c->tune.small_pj = value;
         return 0;
     }
+    if (!strcmp(name, "small_jp")) {  // joint_predict by one workgroup up to this many rows 2n + p m + 1 (0: every size takes the chain)
+        if (value < 0 || value > 1024) return gpmi_fail(GPMI_EARG, "small_jp must be 0 .. 1024");
+        c->tune.small_jp = value;
+        return 0;
+    }
     if (!strcmp(name, "predict_mb")) {  // rows of Xs per chunk of the prediction chains (0: auto)
         if (value < 0) return gpmi_fail(GPMI_EARG, "predict_mb must be >= 0");
         c->tune.predict_mb = value;
@@ -4050,6 +4055,122 @@ extern "C" int gpmi_gp_predict_joint(gpmi_ctx *c, const double *X, int n, int ld
     return sc.finish(c->d_info + 1);
 }
 
+// ---- prediction for the joint [y; y'] model: f, f', f'' at new times given both series ---------------------------------
+// S = gpmi_joint_logml's matrix (launch_joint_cov, compat 0), the requested orders a_1 < .. < a_p of `orders`, stacked by order:
+//   Ks block a = alpha^2 [kind(a, Q)(ts, t), kind(a, R)(ts, t)],   Kss block (a, b) = alpha^2 kind(a, b)(ts, ts),
+//   mean = Ks S^-1 yy,   C = Kss - Ks S^-1 Ks^T + diag(post_jitter[a] on block a),   draws[:, b] = mean + chol(C) Z[:, b]
+// -- what pendulum_fit3.R:31-46 observes (ynoise and ypnoise on one grid) conditioned on jointly, where the reference
+// differentiates each series on its own (pendulum_fit.R:227-268).  predict_joint_core with the order-2n builder and the fused
+// star builder in place of launch_se_cov: one workspace of order 2n + p m + 1 holds [[S, .], [Ks, Kss]] and the row [yy^T, 0].
+// The route depends on (n, m, p) and the options, never on B.
+static bool small_joint_predict(const gpmi_ctx *c, int n, int m, int p)
+{
+    return c->tune.small_jp > 0 && 2LL * n + (long long)p * m + 1 <= (long long)c->tune.small_jp;
+}
+
+static int joint_predict_check(int n, double alpha, double l, double sigma, int m, int orders, const double *post_jitter, bool cov,
+                               int ldc, int B, int ldz, int ldd)
+{
+    if (n < 1 || m < 1) return gpmi_fail(GPMI_EARG, "n and m must be positive");
+    if (B < 0) return gpmi_fail(GPMI_EARG, "negative number of draws");
+    if (orders < 1 || orders > 7) return gpmi_fail(GPMI_EARG, "orders must be a mask of GPMI_OUT_VALUE | _DERIV | _DERIV2");
+    if (!(alpha > 0.0) || !(l > 0.0) || !std::isfinite(l) || !(sigma >= 0.0))
+        return gpmi_fail(GPMI_EARG, "alpha and l must be positive, l finite, sigma non-negative");
+    const long long pm = (long long)__builtin_popcount(orders) * m;
+    if (2LL * n + pm + 1 > 2147483000LL) return gpmi_fail(GPMI_EARG, "2n + p m does not fit an int");
+    for (int a = 0; a < __builtin_popcount(orders); ++a)
+        if (!std::isfinite(post_jitter[a])) return gpmi_fail(GPMI_EARG, "post_jitter must be finite");
+    if (cov && ldc < pm) return gpmi_fail(GPMI_EARG, "leading dimension of cov smaller than p m");
+    if (B > 0 && (ldz < pm || ldd < pm)) return gpmi_fail(GPMI_EARG, "leading dimension of Z or draws smaller than p m");
+    return 0;
+}
+
+// every device buffer joint_predict_core(c, n, m, p) touches, at its final size (a growing buffer synchronises its stream)
+static int joint_predict_reserve(gpmi_ctx *c, int n, int m, int p)
+{
+    if (small_joint_predict(c, n, m, p)) return reserve_ws_small(c, 2 * n + p * m, 1);
+    return reserve_ws(c, 2 * n + p * m + 1, 2 * n + p * m);
+}
+
+// all pointers device but post_jitter (host, p values); d_cov nullable; dZ / d_draws unused when B == 0; enqueues on c->stream
+static int joint_predict_core(gpmi_ctx *c, const double *dt, int n, const double *dyy, double alpha, double l, double sigma,
+                              double jitter, const double *dts, int m, int orders, const double *post_jitter, double *d_mean,
+                              double *d_cov, int ldc, const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info)
+{
+    int rc;
+    hipStream_t s = c->stream;
+    const int p = __builtin_popcount(orders), n2 = 2 * n, pm = p * m;
+    if ((rc = joint_predict_reserve(c, n, m, p))) return rc;
+    if (small_joint_predict(c, n, m, p)) {
+        launch_joint_predict_wg(s, dt, n, dts, m, dyy, alpha * alpha, l, sigma * sigma, jitter, orders, post_jitter, c->W, d_mean, d_cov,
+                                (size_t)ldc, dZ, B, (size_t)ldz, d_draws, (size_t)ldd, d_info, c->d_info + 2);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    const int nt = n2 + pm, M = nt + 1;
+    const size_t ld = (size_t)c->ld;
+    HIPCHK(hipMemsetAsync(c->d_info, 0, 4 * sizeof(int), s));
+    launch_joint_cov(s, dt, n, alpha * alpha, l, sigma * sigma, jitter, 0, 1, c->W, ld);
+    launch_joint_star(s, dt, n, dts, m, orders, alpha * alpha, l, c->W, ld);
+    launch_set_row(s, c->W, ld, nt, dyy, n2, nt);
+    if ((rc = launch_potrf_partial(c, c->W, ld, M, nt, n2, c->d_info, nullptr))) return rc;
+    double *S = c->W + n2 + (size_t)n2 * ld;   // Schur complement = C without the post-jitters (lower); below it -mean^T
+    launch_joint_readout_blocks(s, S, ld, c->W + nt + (size_t)n2 * ld, pm, post_jitter, m, d_mean, d_cov, (size_t)ldc, c->d_info);
+    if (B > 0) {
+        if ((rc = launch_potrf_partial(c, S, ld, pm, pm, pm, c->d_info + 2, nullptr))) return rc;
+        launch_tril_draws(s, S, ld, pm, d_mean, dZ, (size_t)ldz, B, d_draws, (size_t)ldd, c->d_info, c->d_info + 2);
+    }
+    hipLaunchKernelGGL(k_merge_info, dim3(1), 64, 0, s, c->d_info, c->d_info + 2, n2, d_info);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_joint_predict_dev(gpmi_ctx *c, const double *dt, int n, const double *dyy, double alpha, double l, double sigma,
+                                      double jitter, const double *dts, int m, int orders, const double *post_jitter, double *d_mean,
+                                      double *d_cov, int ldc, const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info)
+{
+    ENTER(c);
+    if (!dt || !dyy || !dts || !post_jitter || !d_mean || !d_info || (B > 0 && (!dZ || !d_draws)))
+        return gpmi_fail(GPMI_EARG, "NULL argument");
+    int rc;
+    if ((rc = joint_predict_check(n, alpha, l, sigma, m, orders, post_jitter, d_cov != nullptr, ldc, B, ldz, ldd))) return rc;
+    return joint_predict_core(c, dt, n, dyy, alpha, l, sigma, jitter, dts, m, orders, post_jitter, d_mean, d_cov, ldc, dZ, B, ldz,
+                              d_draws, ldd, d_info);
+}
+
+extern "C" int gpmi_joint_predict(gpmi_ctx *c, const double *t, int n, const double *yy, double alpha, double l, double sigma,
+                                  double jitter, const double *ts, int m, int orders, const double *post_jitter, double *mean,
+                                  double *cov, int ldc, const double *Z, int B, int ldz, double *draws, int ldd)
+{
+    ENTER(c);
+    if (!t || !yy || !ts || !post_jitter || !mean || (B > 0 && (!Z || !draws))) return gpmi_fail(GPMI_EARG, "NULL argument");
+    int rc;
+    if ((rc = joint_predict_check(n, alpha, l, sigma, m, orders, post_jitter, cov != nullptr, ldc, B, ldz, ldd))) return rc;
+    const int p = __builtin_popcount(orders), pm = p * m;
+    if (small_joint_predict(c, n, m, p)) {
+        // ONE launch: inputs and results travel through the pinned, device-mapped buffer (each input is read once)
+        PinCall pc(c);
+        const size_t mean_ = pc.out(mean, pm, 1, pm), cov_ = cov ? pc.out(cov, pm, pm, ldc) : 0, draws_ = B ? pc.out(draws, pm, B, ldd) : 0,
+                     t_ = pc.in(t, n, 1, n), ts_ = pc.in(ts, m, 1, m), yy_ = pc.in(yy, 2 * n, 1, 2 * n), Z_ = B ? pc.in(Z, pm, B, ldz) : 0;
+        if ((rc = pc.begin(0, 2 * n + pm, 1))) return rc;
+        launch_joint_predict_wg(c->stream, pc.dev(t_), n, pc.dev(ts_), m, pc.dev(yy_), alpha * alpha, l, sigma * sigma, jitter, orders,
+                                post_jitter, c->W, pc.dev(mean_), cov ? pc.dev(cov_) : nullptr, (size_t)pm, B ? pc.dev(Z_) : nullptr, B,
+                                (size_t)pm, B ? pc.dev(draws_) : nullptr, (size_t)pm, pc.info(), c->d_info + 2, pc.flag(), pc.seq);
+        return pc.finish();
+    }
+    // the chain: inputs and results in staging buffer 0; cov == NULL: no p m x p m staging either
+    if ((rc = joint_predict_reserve(c, n, m, p))) return rc;
+    StageCall sc(c);
+    const size_t t_ = sc.in(t, n, 1, n), ts_ = sc.in(ts, m, 1, m), yy_ = sc.in(yy, 2 * n, 1, 2 * n), Z_ = B ? sc.in(Z, pm, B, ldz) : 0,
+                 mean_ = sc.out(mean, pm, 1, pm), cov_ = cov ? sc.out(cov, pm, pm, ldc) : 0, draws_ = B ? sc.out(draws, pm, B, ldd) : 0;
+    if ((rc = sc.begin())) return rc;
+    if ((rc = joint_predict_core(c, sc.dev(t_), n, sc.dev(yy_), alpha, l, sigma, jitter, sc.dev(ts_), m, orders, post_jitter,
+                                 sc.dev(mean_), cov ? sc.dev(cov_) : nullptr, pm, B ? sc.dev(Z_) : nullptr, B, pm,
+                                 B ? sc.dev(draws_) : nullptr, pm, c->d_info + 1)))
+        return rc;
+    return sc.finish(c->d_info + 1);
+}
+
 // ---- sequential conditional sampler -------------------------------------
 // create_p_dotXnS, R/ode_gp_library.R:43-93.  The reference re-derives, at every call, the joint
 // mean and covariance of ALL star points so far,
@@ -4648,6 +4769,56 @@ extern "C" int gpmi_probe_tril_draws(gpmi_ctx *c, int m, int B, int reps, double
                     launch_trmv_lower(s, c->W, ld, m, zd + (size_t)b * m, dr + (size_t)b * m, part);
                     hipLaunchKernelGGL(k_axpy1, dim3((m + 255) / 256), 256, 0, s, dr + (size_t)b * m, mu, m);
                 }
+        }
+        HIPCHK(hipEventRecord(c->ev[1], s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        ms2[mode] = (double)ms / reps;
+    }
+    return 0;
+}
+// the star blocks of gpmi_joint_predict's workspace for n training and m new times and the orders of the mask: ms2[0] =
+// launch_joint_star (one launch, one exponential per pair of points), ms2[1] = the launch_deriv_cov calls it replaces, one per
+// block (2 p of Ks, p (p + 1) / 2 of the lower-stored Kss: 12 at p = 3) into the same places; HIP events around `reps`
+// repetitions each, after one warm-up
+extern "C" int gpmi_probe_joint_star(gpmi_ctx *c, int n, int m, int orders, int reps, double *ms2)
+{
+    ENTER(c);
+    if (n < 1 || m < 1 || orders < 1 || orders > 7 || reps < 1 || !ms2) return gpmi_fail(GPMI_EARG, "bad argument");
+    int rc;
+    const int p = __builtin_popcount(orders), n2 = 2 * n, nt = n2 + p * m;
+    if ((rc = reserve_ws(c, nt + 1, nt))) return rc;
+    const size_t ld = (size_t)c->ld;
+    double *dt;
+    if ((rc = stage_buf(c, 0, (size_t)(n + m) * sizeof(double), &dt))) return rc;
+    double *dts = dt + n;
+    hipStream_t s = c->stream;
+    std::vector<double> h((size_t)n + m);
+    for (size_t i = 0; i < h.size(); ++i) h[i] = (double)((i * 2654435761u) % 2001u) * 1e-3 - 1.0;
+    HIPCHK(hipMemcpyAsync(dt, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    const double a2 = 1.21, l = 0.3;
+    for (int mode = 0; mode < 2; ++mode) {
+        for (int r = -1; r < reps; ++r) {
+            if (r == 0) HIPCHK(hipEventRecord(c->ev[0], s));
+            if (mode == 0) {
+                launch_joint_star(s, dt, n, dts, m, orders, a2, l, c->W, ld);
+                continue;
+            }
+            static const int kind[3][3] = {{GPMI_QQ, GPMI_QR, GPMI_QT}, {GPMI_RQ, GPMI_RR, GPMI_RT}, {GPMI_TQ, GPMI_TR, GPMI_TT}};
+            for (int a = 0, ia = 0; a < 3; ++a) {
+                if (!((orders >> a) & 1)) continue;
+                double *row = c->W + n2 + (size_t)ia * m;
+                launch_deriv_cov(s, kind[a][0], dts, m, dt, n, a2, l, 0, 0, row, ld);
+                launch_deriv_cov(s, kind[a][1], dts, m, dt, n, a2, l, 0, 0, row + (size_t)n * ld, ld);
+                for (int b = 0, ib = 0; b <= a; ++b) {
+                    if (!((orders >> b) & 1)) continue;
+                    launch_deriv_cov(s, kind[a][b], dts, m, dts, m, a2, l, 0, a == b, row + (size_t)(n2 + ib * m) * ld, ld);
+                    ++ib;
+                }
+                ++ia;
+            }
         }
         HIPCHK(hipEventRecord(c->ev[1], s));
         HIPCHK(hipStreamSynchronize(s));

@@ -69,6 +69,7 @@ struct gpmi_tuning {
     int small_pr;            // gpmi_gp_predict[_dev]: one workgroup, one launch, up to n + m + 1 <= small_pr rows and D <= GPMI_MAXD (0: off)
     int predict_mb;          // gpmi_gp_predict / gpmi_seq_marginals: rows of Xs per chunk of the blocked chain (0: auto)
     int small_pj;            // gpmi_gp_predict_joint[_dev]: one workgroup, one launch, up to n + m + 1 <= small_pj rows and D <= GPMI_MAXD (0: off)
+    int small_jp;            // gpmi_joint_predict[_dev]: one workgroup, one launch, up to 2n + p m + 1 <= small_jp rows (0: off)
     int small_sd, small_sdb; // sample_derivs_batch: one workgroup per draw when n + m + 1 <= small_sd rows and at least small_sdb (n + m + 1)^2 / 400^2 draws (0: off)
     int small_n2, small_g2;  // grids of >= small_g2 (n / 1024)^2 + 2 points: one workgroup per point up to n <= small_n2 (every CU a problem of its own)
 };
@@ -169,6 +170,12 @@ void launch_deriv_elem(hipStream_t s, int kind, const double *tj, const double *
 // joint 2n x 2n [[QQ+s2 I, QR],[RQ, RR]] + jitter I; lower != 0 writes i >= j only
 void launch_joint_cov(hipStream_t s, const double *dt, int n, double a2, double l, double s2,
                       double jitter, int compat, int lower, double *dK, size_t ldk);
+// star blocks of gpmi_joint_predict's workspace dW (order 2n + p m + 1, launch_joint_cov's S in its leading 2n x 2n block) for the
+// p derivative orders in the bit mask `orders` (1 .. 7) at the m times dts: rows 2n + ia m + i hold a2 kind(a_ia, Q | R)(ts_i, t_j)
+// in the columns j | n + j and a2 kind(a_ia, a_ib)(ts_i, ts_j) in the columns 2n + ib m + j, lower-stored; one exponential per
+// pair of points, every entry with the bits of launch_deriv_cov for its kind
+void launch_joint_star(hipStream_t s, const double *dt, int n, const double *dts, int m, int orders, double a2, double l, double *dW,
+                       size_t ldw);
 void launch_set_row(hipStream_t s, double *W, size_t ld, int row, const double *src, int n,
                     int ntotal);  // W[row, j] = j < n ? src[j] : 0, j < ntotal
 void launch_copy_matrix(hipStream_t s, const double *src, size_t lds, double *dst, size_t ldd,
@@ -276,6 +283,13 @@ void launch_gp_predict_joint_wg(hipStream_t s, const double *X, int n, int ldx, 
                                 const SeParams &p, double diag_add, double post_jitter, double *W, double *mean, double *cov, size_t ldc,
                                 const double *Z, int B, size_t ldz, double *draws, size_t ldd, int *info_out, int *d_info_work,
                                 int *done = nullptr, int seq = 0);
+// gpmi_joint_predict by one workgroup (workspace: one slice of small_ws_layout(2n + p m), 2n + p m <= 1023; d_info_work: 2 ints);
+// orders: bit mask of the p requested derivative orders, pj: their p post-jitters (host); every pointer but W and d_info_work
+// may be host-mapped (each input is read once); cov nullable, Z / draws unused at B == 0
+void launch_joint_predict_wg(hipStream_t s, const double *t, int n, const double *ts, int m, const double *yy, double a2, double l,
+                             double s2, double jitter, int orders, const double *pj, double *W, double *mean, double *cov, size_t ldc,
+                             const double *Z, int B, size_t ldz, double *draws, size_t ldd, int *info_out, int *d_info_work,
+                             int *done = nullptr, int seq = 0);
 // f = chol(K + diag_add I) z by one workgroup (n <= 256, D <= GPMI_MAXD); X, z / f, info_out may be host-mapped (stage != null)
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,
                            double *W, double *f, int *info_out, int *d_info_work, double *stage, int *done = nullptr, int seq = 0);
@@ -369,6 +383,9 @@ void launch_predict_mean(hipStream_t s, const double *X, int n, int ldx, const d
 // post_jitter is added to the diagonal of S IN PLACE, and cov (nullable; ldc) receives S mirrored; *info != 0 -> NaN outputs
 void launch_joint_readout(hipStream_t s, double *S, size_t ld, const double *row, int m, double post_jitter, double *mean, double *cov,
                           size_t ldc, const int *info);
+// ... with one post_jitter per block of mb rows (at most three blocks: m <= 3 mb): row r takes pj[r / mb]
+void launch_joint_readout_blocks(hipStream_t s, double *S, size_t ld, const double *row, int m, const double *pj, int mb, double *mean,
+                                 double *cov, size_t ldc, const int *info);
 // draws = mean 1^T + L Z for the m x m lower-triangular L (ldl; its strict upper part is never read) and B columns (Z: ldz,
 // draws: ldd), one MFMA product; a column's bits do not depend on B or on the other columns.  *info_a or *info_b (nullable)
 // non-zero -> every draw is NaN

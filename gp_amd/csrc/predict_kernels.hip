@@ -196,13 +196,18 @@ __global__ __launch_bounds__(256) void k_predict_mean_sum(const double *__restri
 // ---- the ends of the joint posterior's chain (gpmi_gp_predict_joint) -------------------------------------------------
 // After the augmented partial factorisation the workspace holds the Schur block S (m x m, lower) and, in the row below it,
 // -mean^T.  mean[r] = -row[r] and S[r, r] += post_jitter (thread = r: the only writer of that element) ...
+// pj: one post_jitter per block of mb rows (gpmi_joint_predict: a block per derivative order); gpmi_gp_predict_joint has one block
+struct BlockJitter {
+    double v[3];
+    int mb;
+};
 __global__ __launch_bounds__(256) void k_joint_mean_diag(double *__restrict__ S, size_t ld, const double *__restrict__ row, int m,
-                                                         double post_jitter, double *__restrict__ mean, const int *info)
+                                                         BlockJitter pj, double *__restrict__ mean, const int *info)
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= m) return;
     mean[r] = *info ? __builtin_nan("") : -row[(size_t)r * ld];
-    S[(size_t)r * (ld + 1)] += post_jitter;
+    S[(size_t)r * (ld + 1)] += r < pj.mb ? pj.v[0] : (r < 2 * pj.mb ? pj.v[1] : pj.v[2]);
 }
 
 // ... then cov = S mirrored (both triangles from the SAME stored element: bit-for-bit symmetric), NaN when *info != 0.
@@ -318,12 +323,19 @@ __global__ __launch_bounds__(256) void k_tril_draws(const double *__restrict__ L
 
 }  // namespace
 
+void launch_joint_readout_blocks(hipStream_t s, double *S, size_t ld, const double *row, int m, const double *pj, int mb, double *mean,
+                                 double *cov, size_t ldc, const int *info)
+{
+    if (m <= 0) return;
+    const BlockJitter bj = {{pj[0], m > mb ? pj[1] : 0.0, m > 2 * mb ? pj[2] : 0.0}, mb};
+    hipLaunchKernelGGL(k_joint_mean_diag, dim3((m + 255) / 256), 256, 0, s, S, ld, row, m, bj, mean, info);
+    if (cov) hipLaunchKernelGGL(k_joint_cov, dim3((m + 63) / 64, (m + 15) / 16), 256, 0, s, S, ld, m, cov, ldc, info);
+}
+
 void launch_joint_readout(hipStream_t s, double *S, size_t ld, const double *row, int m, double post_jitter, double *mean, double *cov,
                           size_t ldc, const int *info)
 {
-    if (m <= 0) return;
-    hipLaunchKernelGGL(k_joint_mean_diag, dim3((m + 255) / 256), 256, 0, s, S, ld, row, m, post_jitter, mean, info);
-    if (cov) hipLaunchKernelGGL(k_joint_cov, dim3((m + 63) / 64, (m + 15) / 16), 256, 0, s, S, ld, m, cov, ldc, info);
+    launch_joint_readout_blocks(s, S, ld, row, m, &post_jitter, m, mean, cov, ldc, info);   // one block: the same one addition
 }
 
 void launch_tril_draws(hipStream_t s, const double *L, size_t ldl, int m, const double *mean, const double *Z, size_t ldz, int B,

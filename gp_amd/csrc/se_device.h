@@ -146,15 +146,11 @@ __device__ __forceinline__ void se_cov_tile(const double *__restrict__ X, int n,
     }
 }
 
-// derivative_kernels.R:39-73 with unit amplitude; r = tj - tk, e = exp(-r^2/(2 l^2)).
-__device__ __forceinline__ double deriv_val(int kind, double tj, double tk, double l2)
+// derivative_kernels.R:39-73 with unit amplitude, the six kinds with the lower order first, from r = tj - tk and
+// e = exp(-r^2/(2 l^2)): the ONE statement of the per-kind expressions (deriv_val, and the builders that share an
+// exponential between several kinds of a pair of points)
+__device__ __forceinline__ double deriv_val_re(int kind, double r, double e, double l2)
 {
-    if (kind == GPMI_RQ || kind == GPMI_TQ || kind == GPMI_TR) {  // :47-49, :59-61, :67-69
-        const double t = tj; tj = tk; tk = t;
-        kind -= 1;
-    }
-    const double r = tj - tk;
-    const double e = exp(-(r * r / (2 * l2)));
     switch (kind) {
     case GPMI_QQ: return e;                                                       // :39-41
     case GPMI_QR: return (e * r) / l2;                                            // :43-45
@@ -165,6 +161,33 @@ __device__ __forceinline__ double deriv_val(int kind, double tj, double tk, doub
         return (3 * e) / (l2 * l2) - (6 * e * r * r) / (l2 * l2 * l2) +
                (e * r * r * r * r) / (l2 * l2 * l2 * l2);
     }
+}
+
+// derivative_kernels.R:39-73 with unit amplitude; r = tj - tk, e = exp(-r^2/(2 l^2)).
+__device__ __forceinline__ double deriv_val(int kind, double tj, double tk, double l2)
+{
+    if (kind == GPMI_RQ || kind == GPMI_TQ || kind == GPMI_TR) {  // :47-49, :59-61, :67-69
+        const double t = tj; tj = tk; tk = t;
+        kind -= 1;
+    }
+    const double r = tj - tk;
+    const double e = exp(-(r * r / (2 * l2)));
+    return deriv_val_re(kind, r, e, l2);
+}
+
+// order of differentiation (0, 1, 2 = Q, R, T) in the first and in the second argument -> GPMI_QQ .. GPMI_TT
+__device__ __forceinline__ constexpr int deriv_kind(int a, int b)
+{
+    return a == 0 ? (b == 0 ? GPMI_QQ : (b == 1 ? GPMI_QR : GPMI_QT))
+                  : (a == 1 ? (b == 0 ? GPMI_RQ : (b == 1 ? GPMI_RR : GPMI_RT)) : (b == 0 ? GPMI_TQ : (b == 1 ? GPMI_TR : GPMI_TT)));
+}
+
+// deriv_val(deriv_kind(a, b), x, y, l2) from dxy = x - y, dyx = y - x and e = exp(-(dxy^2 / (2 l2))): the three kinds with the
+// higher order first take dyx, as deriv_val's swap does, and dyx^2 has the bits of dxy^2 -- ONE exponential serves all nine
+// kinds of a pair of points and each of them keeps the bits of deriv_val
+__device__ __forceinline__ double deriv_val_pair(int a, int b, double dxy, double dyx, double e, double l2)
+{
+    return a > b ? deriv_val_re(deriv_kind(a, b) - 1, dyx, e, l2) : deriv_val_re(deriv_kind(a, b), dxy, e, l2);
 }
 
 // alpha^2 times a derivative kernel; compat (R/kernels.R:31 as written): for RR alpha^2 multiplies the first term only

@@ -189,6 +189,106 @@ __global__ __launch_bounds__(256) void k_joint_cov(const double *__restrict__ t,
     }
 }
 
+// Star blocks of the joint [y; y'] posterior's workspace (gpmi_joint_predict: order 2n + p m + 1 with k_joint_cov's S in the
+// leading 2n x 2n block) for the derivative orders a_1 < .. < a_p (bit mask ORD) at the m new times ts, K = the workspace:
+//   Ks : K[2n + ia m + i, j] = a2 kind(a_ia, Q)(ts_i, t_j),   K[2n + ia m + i, n + j] = a2 kind(a_ia, R)(ts_i, t_j)
+//   Kss: K[2n + ia m + i, 2n + ib m + j] = a2 kind(a_ia, a_ib)(ts_i, ts_j), lower-stored: the blocks ia > ib are full m x m,
+//        the blocks ia == ib hold i >= j
+// with the bits of k_deriv_cov for every kind (deriv_val_pair).  ONE exponential per pair of points: blockIdx.y < nct is a
+// 64 x 64 tile of pairs (ts_i, t_j) and feeds 2p entries per pair; the other tiles are pairs (ts_i, ts_j) with tile row >=
+// tile column.  There a pair i > j of two different tiles writes its p (p + 1) / 2 entries of the blocks ia >= ib, leaves
+// its exponential in LDS, and the same workgroup then writes the p (p - 1) / 2 entries of the transposed pair (j, i) of the
+// blocks ia > ib with the lanes along THEIR rows (the points of the column tile), so that these stores are 16-byte row pairs
+// as well: p^2 entries from one exponential.  A diagonal tile holds both (i, j) and (j, i) and writes each from its own.
+// The rows of a thread are 2 tx, 2 tx + 1 as in k_joint_cov; a block whose first row is odd (m and ia odd) takes 8-byte stores.
+template <int ORD>
+__global__ __launch_bounds__(256) void k_joint_star(const double *__restrict__ t, int n, const double *__restrict__ ts, int m,
+                                                    double a2, double l2, double *__restrict__ K, size_t ldk, int vec, int nct)
+{
+    constexpr int P = (ORD & 1) + ((ORD >> 1) & 1) + ((ORD >> 2) & 1);
+    __shared__ double s_e[P > 1 ? TILE : 1][TILE + 1];   // [point of the column tile][point of the row tile]
+    const int row0 = blockIdx.x * TILE;
+    const bool star = (int)blockIdx.y >= nct;
+    const int col0 = ((int)blockIdx.y - (star ? nct : 0)) * TILE;
+    if (star && col0 > row0) return;   // the pairs of this tile are the transposed ones of tile (col0, row0)
+    const bool twice = P > 1 && star && col0 < row0;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const double *__restrict__ yp = star ? ts : t;
+    const int ny = star ? m : n;
+    const size_t n2 = 2 * (size_t)n;
+    {
+        const int r = row0 + 2 * tx;
+        const bool ok0 = r < m, ok1 = r + 1 < m;
+        const double x0 = ok0 ? ts[r] : 0.0, x1 = ok1 ? ts[r + 1] : 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c = col0 + ty * 8 + q;
+            if (c >= ny) break;
+            const double yv = yp[c];
+            const double d0 = x0 - yv, d1 = x1 - yv, b0 = yv - x0, b1 = yv - x1;
+            const double e0 = exp(-(d0 * d0 / (2 * l2))), e1 = exp(-(d1 * d1 / (2 * l2)));   // deriv_val's argument
+            if (twice) {
+                s_e[ty * 8 + q][2 * tx] = e0;
+                s_e[ty * 8 + q][2 * tx + 1] = e1;
+            }
+            int ia = 0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (!((ORD >> a) & 1)) continue;
+                double *Kr = K + n2 + (size_t)ia * m + (size_t)r;
+                const bool v2 = vec != 0 && (((size_t)ia * m) % 2 == 0);
+                if (!star) {
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+                        store_pair(Kr + ((size_t)b * n + c) * ldk, a2 * deriv_val_pair(a, b, d0, b0, e0, l2),
+                                   a2 * deriv_val_pair(a, b, d1, b1, e1, l2), ok0, ok1, v2);
+                } else {
+                    int ib = 0;
+#pragma unroll
+                    for (int b = 0; b <= a; ++b) {
+                        if (!((ORD >> b) & 1)) continue;
+                        const bool w0 = ok0 && (b < a || r >= c), w1 = ok1 && (b < a || r + 1 >= c);
+                        store_pair(Kr + (n2 + (size_t)ib * m + c) * ldk, a2 * deriv_val_pair(a, b, d0, b0, e0, l2),
+                                   a2 * deriv_val_pair(a, b, d1, b1, e1, l2), w0, w1, v2);
+                        ++ib;
+                    }
+                }
+                ++ia;
+            }
+        }
+    }
+    if constexpr (P > 1) {
+        if (!twice) return;   // workgroup-uniform
+        __syncthreads();
+        const int r = col0 + 2 * tx;   // the column tile's points are the rows now (a whole tile: col0 + 64 <= row0 < m)
+        const double x0 = ts[r], x1 = ts[r + 1];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c = row0 + ty * 8 + q;
+            if (c >= m) break;
+            const double yv = ts[c];
+            const double d0 = x0 - yv, d1 = x1 - yv, b0 = yv - x0, b1 = yv - x1;
+            const double e0 = s_e[2 * tx][ty * 8 + q], e1 = s_e[2 * tx + 1][ty * 8 + q];   // (ts_c - ts_r)^2 has the bits of d^2
+            int ia = 0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (!((ORD >> a) & 1)) continue;
+                double *Kr = K + n2 + (size_t)ia * m + (size_t)r;
+                const bool v2 = vec != 0 && (((size_t)ia * m) % 2 == 0);
+                int ib = 0;
+#pragma unroll
+                for (int b = 0; b < a; ++b) {
+                    if (!((ORD >> b) & 1)) continue;
+                    store_pair(Kr + (n2 + (size_t)ib * m + c) * ldk, a2 * deriv_val_pair(a, b, d0, b0, e0, l2),
+                               a2 * deriv_val_pair(a, b, d1, b1, e1, l2), true, true, v2);
+                    ++ib;
+                }
+                ++ia;
+            }
+        }
+    }
+}
+
 __global__ void k_set_row(double *W, size_t ld, int row, const double *src, int n, int ntotal)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -422,6 +522,21 @@ void launch_joint_cov(hipStream_t s, const double *dt, int n, double a2, double 
     dim3 grid((n + TILE - 1) / TILE, (n + TILE - 1) / TILE);
     hipLaunchKernelGGL(k_joint_cov, grid, 256, 0, s, dt, n, a2, l * l, s2, jitter, compat, lower, dK, ldk,
                        (int)vec_ok(dK, ldk), h_exp);
+}
+
+void launch_joint_star(hipStream_t s, const double *dt, int n, const double *dts, int m, int orders, double a2, double l, double *dW,
+                       size_t ldw)
+{
+    if (n <= 0 || m <= 0) return;
+    const int nct = (n + TILE - 1) / TILE, mt = (m + TILE - 1) / TILE;
+    const dim3 grid(mt, nct + mt);
+    const int vec = (int)vec_ok(dW, ldw);
+#define GPMI_STAR(o) case o: hipLaunchKernelGGL(k_joint_star<o>, grid, 256, 0, s, dt, n, dts, m, a2, l * l, dW, ldw, vec, nct); break;
+    switch (orders) {
+        GPMI_STAR(1) GPMI_STAR(2) GPMI_STAR(3) GPMI_STAR(4) GPMI_STAR(5) GPMI_STAR(6) GPMI_STAR(7)
+    default: break;   // the entry points admit 1 .. 7 only
+    }
+#undef GPMI_STAR
 }
 
 void launch_set_row(hipStream_t s, double *W, size_t ld, int row, const double *src, int n, int ntotal)

@@ -1014,6 +1014,132 @@ __global__ __launch_bounds__(256, 2) void k_gp_predict_joint_wg(const double *__
     small_signal_done(done, seq);
 }
 
+// gpmi_joint_predict (the posterior of f, f', f'' at m new times given stacked observations yy = [y; y'] under the joint model
+// of R/ode_gp_library.R:29-30; pendulum_fit3.R:31-46 observes both series) by ONE workgroup, the composition of
+// k_gp_predict_joint_wg with the matrices of the joint model.  thread = POINT for the build: a training point i writes its
+// entries of S with the arithmetic of k_joint_cov (the bits of gpmi_joint_logml's matrix), a new point its rows of the p star
+// blocks (deriv_val_pair: the bits of k_deriv_cov) from one exponential per pair of points; t and ts are staged in LDS (read
+// once: every pointer but W and info_w may be host-mapped).  Then the partial factorisation of the first 2n columns, mean =
+// minus the last row, cov = the mirrored Schur block + pj[a] on block a, and for B > 0 the second factorisation and the row
+// loop of the draws, exactly as in k_gp_predict_joint_wg.  Workspace rows: 2n of S, m per requested order, the row [yy^T, 0].
+// status: 0, k (S not PD at order k: every output NaN), 2n + k (cov not PD: draws NaN, mean and cov as with B = 0).
+struct JointPredArgs {
+    double a2, l2, s2, jitter, pj0, pj1, pj2;   // pj*: post_jitter of the first, second, third REQUESTED order
+    int orders;
+};
+__global__ __launch_bounds__(256, 2) void k_joint_predict_wg(const double *__restrict__ t, int n, const double *__restrict__ ts, int m,
+                                                          const double *__restrict__ yy, JointPredArgs q, double *__restrict__ W,
+                                                          size_t ld, double *__restrict__ mean, double *__restrict__ cov, size_t ldc,
+                                                          const double *__restrict__ Z, int B, size_t ldz, double *__restrict__ draws,
+                                                          size_t ldd, int *info_out, int *info_w, ExpC ec, int *done, int seq)
+{
+    GPMI_SMALL_LDS
+    int tid = threadIdx.x;
+    const int n2 = 2 * n, p = __builtin_popcount(q.orders), pm = p * m, nt = n2 + pm;
+    if (tid < 2) info_w[tid] = 0;
+    {
+        double *xs = &smem[0][0][0][0];   // n + m <= 1023 doubles: t, then ts
+        for (int i = tid; i < n + m; i += 256) xs[i] = i < n ? t[i] : ts[i - n];
+        __syncthreads();
+        const double il2 = 1.0 / q.l2;
+        for (int i = tid; i < n + m; i += 256) {
+            const double xi = xs[i];
+            if (i < n) {   // rows i and n + i of S: QQ and RR lower, RQ in full (k_joint_cov with compat = 0)
+                for (int j = 0; j < n; ++j) {
+                    const double r0 = xi - xs[j];
+                    const double e0 = exp_nonpos(-(r0 * r0 / (2 * q.l2)), ec);
+                    W[(size_t)(n + i) + (size_t)j * ld] = -(q.a2 * e0 * r0 * il2);
+                    if (j <= i) {
+                        double qq = q.a2 * e0, rr = q.a2 * e0 * il2 - q.a2 * e0 * r0 * r0 * il2 * il2;
+                        if (i == j) { qq += q.s2 + q.jitter; rr += q.jitter; }
+                        W[(size_t)i + (size_t)j * ld] = qq;
+                        W[(size_t)(n + i) + (size_t)(n + j) * ld] = rr;
+                    }
+                }
+            } else {   // rows 2n + ia m + ii of the star blocks
+                const int ii = i - n;
+                const int jn = p > 1 ? n + m : i + 1;   // one order: its only block is lower-stored
+                for (int j = 0; j < jn; ++j) {
+                    const double yv = xs[j];
+                    const double d = xi - yv, b = yv - xi;
+                    const double e = exp(-(d * d / (2 * q.l2)));   // deriv_val's argument
+                    int ia = 0;
+                    for (int a = 0; a < 3; ++a) {
+                        if (!((q.orders >> a) & 1)) continue;
+                        double *Wr = W + (size_t)n2 + (size_t)ia * m + (size_t)ii;
+                        if (j < n) {
+                            Wr[(size_t)j * ld] = q.a2 * deriv_val_pair(a, 0, d, b, e, q.l2);
+                            Wr[(size_t)(n + j) * ld] = q.a2 * deriv_val_pair(a, 1, d, b, e, q.l2);
+                        } else {
+                            int ib = 0;
+                            for (int o = 0; o <= a; ++o) {
+                                if (!((q.orders >> o) & 1)) continue;
+                                if (o < a || j <= i) Wr[(size_t)(n2 + ib * m + j - n) * ld] = q.a2 * deriv_val_pair(a, o, d, b, e, q.l2);
+                                ++ib;
+                            }
+                        }
+                        ++ia;
+                    }
+                }
+            }
+        }
+    }
+    for (int j = tid; j < nt; j += 256) W[(size_t)nt + (size_t)j * ld] = j < n2 ? yy[j] : 0.0;
+    __syncthreads();
+    small_potrf_partial(smem, s_F, s_aux, W, ld, nt + 1, nt, n2, info_w, false);
+    __syncthreads();
+    asm volatile("" : "+v"(tid));
+    const int info = __hip_atomic_load(info_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double *S = W + (size_t)n2 + (size_t)n2 * ld;   // Schur complement (lower), rows 2n .. nt - 1
+    // thread = row: its own diagonal element takes its block's post_jitter (for the read-out and for the factorisation below);
+    // nothing else of the block is written here, so no thread reads what another one changes
+    for (int r = tid; r < pm; r += 256) {
+        mean[r] = info ? __builtin_nan("") : -W[(size_t)nt + (size_t)(n2 + r) * ld];
+        S[(size_t)r * (ld + 1)] += r < m ? q.pj0 : (r < 2 * m ? q.pj1 : q.pj2);
+        if (cov)
+            for (int c = 0; c < pm; ++c) {
+                const double v = (r >= c) ? S[(size_t)r + (size_t)c * ld] : S[(size_t)c + (size_t)r * ld];
+                cov[(size_t)r + (size_t)c * ldc] = info ? __builtin_nan("") : v;
+            }
+    }
+    int info2 = 0;
+    if (B > 0) {   // kernel argument: workgroup-uniform
+        __syncthreads();
+        if (!info) {
+            small_potrf_partial(smem, s_F, s_aux, S, ld, pm, pm, pm, info_w + 1, false);
+            __syncthreads();
+            asm volatile("" : "+v"(tid));
+            info2 = __hip_atomic_load(info_w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        const bool bad = info || info2;
+        double *zl = &smem[0][0][0][0];   // pm <= 1021 doubles
+        for (int b = 0; b < B; ++b) {
+            for (int j = tid; j < pm; j += 256) zl[j] = Z[(size_t)j + (size_t)b * ldz];
+            __syncthreads();
+            for (int i0 = 0; i0 < pm; i0 += 256) {
+                const int i = i0 + tid, ic = i < pm ? i : pm - 1;
+                double acc = 0.0;
+                const int jend = (i0 + 255 < pm ? i0 + 255 : pm - 1);   // workgroup-uniform bound; columns > i contribute nothing
+                for (int j0 = 0; j0 <= jend; j0 += 16) {
+                    double u[16];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const int j = j0 + k <= ic ? j0 + k : ic;
+                        u[k] = S[(size_t)ic + (size_t)j * ld];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 16; ++k)
+                        if (j0 + k <= ic) acc = fma(u[k], zl[j0 + k], acc);
+                }
+                if (i < pm) draws[(size_t)i + (size_t)b * ldd] = bad ? __builtin_nan("") : acc - W[(size_t)nt + (size_t)(n2 + i) * ld];
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) *info_out = info ? info : (info2 ? n2 + info2 : 0);
+    small_signal_done(done, seq);
+}
+
 // f = chol(cov_exp_quad(X, alpha, ell) + diag_add I) z (models/exact_gp.stan:17-25: the latent exact GP's transform, once per
 // leapfrog step with a new length-scale) by ONE workgroup for n <= 256: build (se_cov_tile), factorisation, and the row sums
 // f_i = sum_{j <= i} L_ij z_j in column order (the order of k_trmv_lower_part inside its first chunk).  stage (nullable): X, z
@@ -1899,6 +2025,19 @@ void launch_gp_predict_joint_wg(hipStream_t s, const double *X, int n, int ldx, 
     small_ws_layout(n + m, &ld, &stride);
     launch_small<k_gp_predict_joint_wg>(1, SMALL_LDS_DOUBLES, s, X, n, ldx, Xs, m, ldxs, y, p, diag_add, post_jitter, W, ld, mean, cov,
                        ldc, Z, B, ldz, draws, ldd, info_out, d_info_work, h_exp, done, seq);
+}
+
+void launch_joint_predict_wg(hipStream_t s, const double *t, int n, const double *ts, int m, const double *yy, double a2, double l,
+                             double s2, double jitter, int orders, const double *pj, double *W, double *mean, double *cov, size_t ldc,
+                             const double *Z, int B, size_t ldz, double *draws, size_t ldd, int *info_out, int *d_info_work, int *done,
+                             int seq)
+{
+    size_t ld, stride;
+    const int p = __builtin_popcount(orders);
+    small_ws_layout(2 * n + p * m, &ld, &stride);
+    const JointPredArgs q = {a2, l * l, s2, jitter, pj[0], p > 1 ? pj[1] : 0.0, p > 2 ? pj[2] : 0.0, orders};
+    launch_small<k_joint_predict_wg>(1, SMALL_LDS_DOUBLES, s, t, n, ts, m, yy, q, W, ld, mean, cov, ldc, Z, B, ldz, draws, ldd, info_out,
+                       d_info_work, h_exp, done, seq);
 }
 
 void launch_exact_gp_small(hipStream_t s, const double *X, int n, int ldx, const double *z, const SeParams &p, double diag_add,

@@ -90,7 +90,8 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * up to n <= small_ng <= 256), "grad_aug_n", "grad_aug_ng" (value + gradient through ONE augmented partial factorisation up
  * to this n: one evaluation / several at once), "small_gc" (gpmi_gp_condition in one launch up to n + m + 1 <= small_gc rows), "small_pr" (gpmi_gp_predict[_dev] in
  * one launch up to n + m + 1 <= small_pr rows and D <= 8; 0 sends every size to the blocked chain), "small_pj" (the same for
- * gpmi_gp_predict_joint[_dev], 0 .. 1024), "predict_mb" (rows of Xs per chunk of the
+ * gpmi_gp_predict_joint[_dev], 0 .. 1024), "small_jp" (gpmi_joint_predict[_dev] in one launch up to 2n + p m + 1 <= small_jp rows,
+ * 0 .. 1024; 0 sends every size to the chain; default 220: the measured crossover at B = 1 and three orders), "predict_mb" (rows of Xs per chunk of the
  * chains of gpmi_gp_predict / gpmi_seq_marginals; 0 = auto, about n / 4), "small_vjp" (gpmi_exact_gp_f_vjp[_dev] by
  * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_cen" (gpmi_centered_gp_lp_grad[_dev] by one
  * workgroup up to n <= small_cen <= 256 (default 192: the measured crossover), D <= 8, k <= 8; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
@@ -456,6 +457,43 @@ GPMI_API int gpmi_gp_predict_joint_dev(gpmi_ctx *ctx, const double *dX, int n, i
                     double *d_mean, double *d_cov /* nullable */, int ldc,
                     const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info);
 
+/* Prediction for the joint value-and-derivative model of gpmi_joint_logml (R/ode_gp_library.R:29-30): the posterior of f, f'
+ * and f'' at the m new times ts given the stacked observations yy = [y; y'] at the n times t -- both series of
+ * pendulum_fit3.R:31-46 conditioned on at once, where the reference differentiates each series on its own
+ * (pendulum_fit.R:227-268).  `orders` is a bit mask of the p requested derivative orders a_1 < .. < a_p; every output is stacked
+ * by order, m rows per block: [f(ts); f'(ts); f''(ts)] restricted to the requested orders.  S is exactly gpmi_joint_logml's
+ * matrix (alpha, l, sigma, jitter as there: fitted hyper-parameters go in unchanged).  With the kind letters Q, R, T for the
+ * orders 0, 1, 2, first argument first (derivative_kernels.R:39-73):
+ *   Ks block a = alpha^2 [kind(a, Q)(ts, t), kind(a, R)(ts, t)]  (p m x 2n),   Kss block (a, b) = alpha^2 kind(a, b)(ts, ts),
+ *   mean = Ks S^-1 yy,   C = Kss - Ks S^-1 Ks^T + diag(post_jitter[a] on block a),   draws[:, b] = mean + chol(C) Z[:, b].
+ * post_jitter (host memory in both forms) holds one finite value per requested order, negative allowed -- per order because f,
+ * f', f'' carry the units alpha^2, alpha^2 / l^2, alpha^2 / l^4; the caller's observation noise goes here.  cov (p m x p m, ldc;
+ * nullable) receives C with both triangles written, bit-for-bit symmetric; with cov == NULL the matrix never leaves the device.
+ * Z (p m x B, ldz) and draws (p m x B, ldd) may be NULL iff B == 0, and then C is not factored.  2n + p m + 1 <= small_jp rows:
+ * one launch of one workgroup; otherwise one workspace of (2n + p m + 1)^2 doubles, a fused builder of the star blocks (one
+ * exponential per pair of points, every entry with the bits gpmi_deriv_cov gives for its kind), two partial factorisations and
+ * one triangular matrix-matrix product (GPMI_ENOMEM when the workspace cannot be allocated).  The route depends on (n, m, p)
+ * and the options, never on B, and all sums run in a fixed order: repeated calls give identical bits, and column b of draws has
+ * the same bits whatever B is and whatever the other columns of Z hold.  Status: 0; k in 1..2n: S is not positive definite at
+ * order k and every output is NaN; 2n + k: C is not positive definite at order k, mean and cov are valid (the bits of the same
+ * call with B = 0) and draws are all NaN.  GPMI_EARG: n or m < 1, B < 0, orders outside 1..7, ldc < p m with cov, ldz or
+ * ldd < p m with B > 0, alpha <= 0, l <= 0 or not finite, sigma < 0, a non-finite post_jitter, a NULL pointer other than cov (and
+ * Z / draws when B == 0). */
+enum { GPMI_OUT_VALUE = 1, GPMI_OUT_DERIV = 2, GPMI_OUT_DERIV2 = 4 };   /* bit mask `orders` */
+GPMI_API int gpmi_joint_predict(gpmi_ctx *ctx, const double *t, int n, const double *yy /* 2n */,
+                    double alpha, double l, double sigma, double jitter,
+                    const double *ts, int m, int orders, const double *post_jitter /* p */,
+                    double *mean /* p m */, double *cov /* p m x p m, nullable */, int ldc,
+                    const double *Z /* p m x B */, int B, int ldz, double *draws /* p m x B */, int ldd);
+/* the same with device-resident t, yy, ts, mean, cov, Z, draws and d_info (1 int); post_jitter stays in host memory.  Enqueued on
+ * the context's stream, not synchronised; the return value says only whether the work was enqueued, the device writes d_info
+ * and the NaNs.  Nothing outside the p m rows of a column is written */
+GPMI_API int gpmi_joint_predict_dev(gpmi_ctx *ctx, const double *dt, int n, const double *dyy,
+                    double alpha, double l, double sigma, double jitter,
+                    const double *dts, int m, int orders, const double *post_jitter /* p, host */,
+                    double *d_mean, double *d_cov /* nullable */, int ldc,
+                    const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info);
+
 /* One draw of the derivative process given noisy values: sample_derivs(params = (l, a, sy), ynoise, ti),
  * pendulum_fit.R:227-255 (separate prediction times ts: lorenz.Rmd:80-107, jitter 1e-6 there, 1e-8 here):
  * draw = mu + chol(cov) z with the (QQ, RQ, RR) moments of gpmi_gp_condition, fused on the device -- the
@@ -555,6 +593,10 @@ GPMI_API int gpmi_probe_mfma_peak(gpmi_ctx *ctx, int iters, double *tflops, doub
  * memory: ms2[0] = milliseconds per call of the triangular matrix-matrix kernel, ms2[1] = of a loop of B one-column
  * products (what it replaced); HIP events around `reps` repetitions each. */
 GPMI_API int gpmi_probe_tril_draws(gpmi_ctx *ctx, int m, int B, int reps, double *ms2);
+/* The star blocks of gpmi_joint_predict's workspace for n training times, m new times and the order mask: ms2[0] = milliseconds
+ * per call of the fused builder, ms2[1] = of the gpmi_deriv_cov launches it replaces (12 at p = 3), into the same places; HIP
+ * events around `reps` repetitions each. */
+GPMI_API int gpmi_probe_joint_star(gpmi_ctx *ctx, int n, int m, int orders, int reps, double *ms2);
 #endif /* GPMI_PROBES */
 
 #ifdef __cplusplus

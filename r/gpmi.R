@@ -229,3 +229,16 @@ gp_predict_joint <- function(X, y, alpha, rho, sigma, Xs, jitter = 0, post_jitte
   r <- .Call("gpmi_R_gp_predict_joint", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter, Xs, post_jitter, Z)
   list(mean = r[[1]], cov = r[[2]], draws = r[[3]])
 }
+
+# prediction for the joint [y; y'] model of joint_logml: list(mean, cov, draws) of f, f', f'' (orders: bit mask 1 / 2 / 4, results
+# stacked by order, length(ts) rows each) at the times ts given yy = c(y, yp) observed at t -- both series of
+# pendulum_fit3.R:31-46 conditioned on at once.  post_jitter: one value per requested order (observation noise of new points;
+# units alpha^2, alpha^2 / l^2, alpha^2 / l^4); draws = mean + t(chol(cov)) %*% Z for n_draws columns of R's own rnorm
+joint_predict <- function(t, yy, alpha, l, sigma, ts, orders = 7L, jitter = 0, post_jitter = rep(0, sum(bitwAnd(orders, c(1L, 2L, 4L)) > 0)),
+                          n_draws = 0) {
+  pm <- sum(bitwAnd(orders, c(1L, 2L, 4L)) > 0) * length(ts)
+  Z <- matrix(rnorm(pm * n_draws), pm, n_draws)
+  r <- .Call("gpmi_R_joint_predict", as.double(t), as.double(yy), alpha, l, sigma, jitter, as.double(ts), as.integer(orders),
+             as.double(post_jitter), Z)
+  list(mean = r[[1]], cov = r[[2]], draws = r[[3]])
+}

@@ -550,6 +550,30 @@ SEXP gpmi_R_gp_predict_joint(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, S
     return out;
 }
 
+/* list(mean, cov, draws): the posterior of f, f', f'' at the times ts given yy = c(y, yp) at the times t under the joint model
+ * of gpmi_R_joint_logml -- orders: bit mask (1 f, 2 f', 4 f''), every result stacked by order; post_jitter: one value per
+ * requested order; Z = matrix(rnorm(p m B), p m, B) (R's own RNG stream); Z with zero columns: no draws, cov is not factored */
+SEXP gpmi_R_joint_predict(SEXP t, SEXP yy, SEXP alpha, SEXP l, SEXP sigma, SEXP jitter, SEXP ts, SEXP orders, SEXP post_jitter, SEXP Z)
+{
+    int n = Rf_length(t), m = Rf_length(ts), ord = Rf_asInteger(orders), B = Rf_ncols(Z);
+    need(is_real(t) && is_real(yy) && is_real(ts) && is_real(post_jitter) && is_real(Z), "t, yy, ts, post_jitter and Z must be double");
+    need(ord >= 1 && ord <= 7, "orders must be a bit mask in 1..7");
+    int p = (ord & 1) + ((ord >> 1) & 1) + ((ord >> 2) & 1), pm = p * m;
+    need(Rf_length(yy) == 2 * n, "length(yy) must equal 2 * length(t)");
+    need(Rf_length(post_jitter) == p, "post_jitter must hold one value per requested order");
+    need(Rf_nrows(Z) == pm, "Z must have one row per requested order and time");
+    SEXP mean = PROTECT(Rf_allocVector(REALSXP, pm)), cov = PROTECT(Rf_allocMatrix(REALSXP, pm, pm)),
+         draws = PROTECT(Rf_allocMatrix(REALSXP, pm, B));
+    int rc = gpmi_joint_predict(ctx(), REAL(t), n, REAL(yy), Rf_asReal(alpha), Rf_asReal(l), Rf_asReal(sigma), Rf_asReal(jitter),
+                                REAL(ts), m, ord, REAL(post_jitter), REAL(mean), REAL(cov), pm, B > 0 ? REAL(Z) : NULL, B, pm,
+                                B > 0 ? REAL(draws) : NULL, pm);
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, mean); SET_VECTOR_ELT(out, 1, cov); SET_VECTOR_ELT(out, 2, draws);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
 /* sample_derivs(params, ynoise, ti): pendulum_fit.R:227-255, one draw mu + chol(cov) z fused on the device; z = rnorm(m)
  * comes from R's own RNG (the reference's MASS::mvrnorm stream cannot be reproduced: eigen-decomposition draw) */
 SEXP gpmi_R_sample_derivs(SEXP t, SEXP ts, SEXP y, SEXP params, SEXP jitter, SEXP z)
