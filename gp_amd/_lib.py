@@ -34,7 +34,7 @@ SYMBOLS = (
     "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy", "gpmi_seq_marginals",
     "gpmi_gp_predict", "gpmi_gp_predict_dev", "gpmi_gp_predict_joint", "gpmi_gp_predict_joint_dev",
     "gpmi_joint_predict", "gpmi_joint_predict_dev",
-    "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex",
+    "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex", "gpmi_debug_fill", "gpmi_debug_counters",
 )
 # additionally exported by the probe build (libgpmi_probes.so, -DGPMI_PROBES; tools/ only)
 PROBE_SYMBOLS = ("gpmi_probe_syrk", "gpmi_probe_mfma", "gpmi_probe_mfma_peak", "gpmi_probe_clock", "gpmi_probe_fused", "gpmi_probe_small", "gpmi_probe_body",
@@ -101,6 +101,8 @@ def load():
         fn = getattr(lib, name)
         if name != "gpmi_last_error":
             fn.restype = C.c_int
+    lib.gpmi_debug_fill.argtypes = (C.c_void_p, C.c_int)
+    lib.gpmi_debug_counters.argtypes = (C.c_void_p, C.POINTER(C.c_int))
     _lib = lib
     return lib
 
@@ -214,6 +216,17 @@ class Context:
         out = np.zeros(12)
         _chk(self._lib.gpmi_kernel_timing_ex(self._h, int(bool(reset)), _p(out)))
         return {"build": tuple(out[0:3]), "syrk": tuple(out[3:6]), "panel": tuple(out[6:9]), "syrk_multi_round": tuple(out[9:12])}
+
+    def debug_fill(self, byte):
+        """Test hook: set every byte of the context's (and its lanes') floating-point scratch to `byte` (0..255), synchronised
+        on both sides; counters, info words, the completion flag and the interpolation tables are left alone."""
+        _chk(self._lib.gpmi_debug_fill(self._h, int(byte)))
+
+    def debug_counters(self):
+        """Number of non-zero device counters of the context and its lanes (0 between calls), read back with a copy."""
+        n = C.c_int(-1)
+        _chk(self._lib.gpmi_debug_counters(self._h, C.byref(n)))
+        return n.value
 
     # ---- covariance builders (host buffers) ----------------------------------
     def se_cov(self, X, Y, alpha, ell, diag_add=0.0, flags=FULL):

@@ -4419,7 +4419,9 @@ extern "C" int gpmi_seq_create(gpmi_ctx *c, gpmi_seq **out, const double *X, int
     const size_t ld = (size_t)c->ld;
     double *dKn, *U;
     SEQ_TRY(stage_buf(c, 0, ldm * (size_t)(n + 1) * sizeof(double), &dKn))
-    SEQ_TRY(stage_buf(c, 2, ldm * (size_t)(n + 1) * sizeof(double), &U))
+    // U is first the scratch of launch_diag_inverses (npan blocks of 128 x 128, whatever n: more than the matrix up to n = 160)
+    const size_t u_mat = ldm * (size_t)(n + 1), u_inv = (size_t)npan * GPMI_NB * GPMI_NB;
+    SEQ_TRY(stage_buf(c, 2, (u_mat > u_inv ? u_mat : u_inv) * sizeof(double), &U))
     auto fail_hip = [&](hipError_t e, const char *what) {
         gpmi_seq_destroy(q);
         return gpmi_fail(GPMI_EHIP, "%s failed: %s", what, hipGetErrorString(e));
@@ -4553,6 +4555,97 @@ extern "C" int gpmi_last_timing(gpmi_ctx *c, double *ms3)
     ENTER(c);
     if (!ms3) return gpmi_fail(GPMI_EARG, "ms3 is NULL");
     for (int i = 0; i < 3; ++i) ms3[i] = c->last_ms[i];
+    return 0;
+}
+
+// every stream a call on this context (root or lane) may have used
+static int debug_sync_all(gpmi_ctx *c)
+{
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->own_stream && c->own_stream != c->stream) HIPCHK(hipStreamSynchronize(c->own_stream));
+    if (c->pstream) HIPCHK(hipStreamSynchronize(c->pstream));
+    for (int q = 0; q < c->nq; ++q)
+        if (c->qstream[q]) HIPCHK(hipStreamSynchronize(c->qstream[q]));
+    for (int l = 0; l < 7; ++l)
+        if (c->lane[l]) {
+            int rc = debug_sync_all(c->lane[l]);
+            if (rc) return rc;
+        }
+    return 0;
+}
+
+// The invariant gpmi_debug_fill makes testable: NO RESULT DEPENDS ON THE CONTENTS OF CONTEXT-OWNED SCRATCH AT ENTRY.  A call
+// may over-read what it never wrote (tile loads past the last row or column, the slack behind W and the staging buffers, a
+// buffer kept from a larger call with another leading dimension laid over it), but whatever it over-reads is selected away
+// before it reaches a stored value, or lies in a region the call itself cleared.
+//
+// Filled (floating-point scratch, over the full allocation; values never index memory, so a fill can make a result wrong but
+// not an access go astray):
+//   W            the factorisation workspace and its slack
+//   stage[0..3]  staging of the host-buffer calls and chain intermediates; the info / status ints some calls carve out of them
+//                are outputs the call's own kernels write before the host reads them, never polled and never an index
+//   scratch      device scratch of the one-launch calls (same remark)
+//   Fpack        ring of packed panel factors: written by the diagonal-block kernel before the panel solve reads it
+//   d_fin        slice sums of the finalize kernels
+//   d_out        the three result doubles of the host-buffer evaluations
+//   d_spar       parameter records of the device-parameter grids, uploaded in stream order by each call (doubles only: the
+//                work ints of those grids live in d_sinfo)
+//   itp_part     partial sums of gpmi_approx_Lz*
+//   h_pin        the payload of the pinned buffer, i.e. everything behind its head of GPMI_HB_HEAD doubles
+// Not filled (state, integers, or polled words):
+//   d_ctr        counters the spin-waiting kernels poll (fused sub-tile wait [8], trsv ticket [32], arrive [40], work ints [64..])
+//   d_info, d_sinfo   integer work words: the factorisation's early-exit flag, zeroed by every call
+//   head of h_pin     word 0 is the info int, word 7 the completion flag pin_wait polls; pin_seq is its host-side sequence
+//   itp_L, itp_dL, igp_M, igp_aux   the interpolation tables are state between calls (igp_aux also holds the pivot ints)
+//   buffers of a gpmi_seq   a context keeps no list of its samplers, and nearly all they own is state (factor, B, committed draws)
+// The only doubles a kernel polls are the output vector of k_trsv_wave, which launch_trsv_lower pre-fills itself on every call.
+extern "C" int gpmi_debug_fill(gpmi_ctx *c, int byte)
+{
+    ENTER(c);
+    if (byte < 0 || byte > 255) return gpmi_fail(GPMI_EARG, "fill byte %d outside 0..255", byte);
+    int rc = debug_sync_all(c);
+    if (rc) return rc;
+    for (int l = -1; l < 7; ++l) {
+        gpmi_ctx *x = l < 0 ? c : c->lane[l];
+        if (!x) continue;
+        const size_t itp_bytes = x->itp_part ? 2 * (size_t)hermite_mv_chunks(x->itp_n) * x->itp_n * sizeof(double) : 0;
+        struct { double *p; size_t bytes; } bufs[] = {
+            {x->W, x->W_bytes},
+            {x->stage[0], x->stage_bytes[0]}, {x->stage[1], x->stage_bytes[1]},
+            {x->stage[2], x->stage_bytes[2]}, {x->stage[3], x->stage_bytes[3]},
+            {x->scratch, x->scratch_bytes},
+            {x->Fpack, (size_t)GPMI_FPACK_SLOTS * GPMI_FPACK * sizeof(double)},
+            {x->d_fin, 65536}, {x->d_out, 64},
+            {x->d_spar, (size_t)x->spar_pts * GPMI_SMALL_PAR * sizeof(double)},
+            {x->itp_part, itp_bytes},
+        };
+        for (const auto &b : bufs)
+            if (b.p && b.bytes) HIPCHK(hipMemsetAsync(b.p, byte, b.bytes, c->stream));
+        if (x->h_pin && x->h_pin_bytes > GPMI_HB_HEAD * sizeof(double))
+            memset(x->h_pin + GPMI_HB_HEAD, byte, x->h_pin_bytes - GPMI_HB_HEAD * sizeof(double));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// *nonzero = number of non-zero ints among the 512 of d_ctr, summed over the context and its lanes: the counters are zeroed at
+// creation and every kernel that uses one leaves it zero, so anything else is a stale counter the next waiting kernel would
+// meet.  Read with a copy, without launching anything that waits.
+extern "C" int gpmi_debug_counters(gpmi_ctx *c, int *nonzero)
+{
+    ENTER(c);
+    if (!nonzero) return gpmi_fail(GPMI_EARG, "nonzero is NULL");
+    int rc = debug_sync_all(c);
+    if (rc) return rc;
+    int count = 0;
+    for (int l = -1; l < 7; ++l) {
+        gpmi_ctx *x = l < 0 ? c : c->lane[l];
+        if (!x || !x->d_ctr) continue;
+        int h[512];
+        HIPCHK(hipMemcpy(h, x->d_ctr, sizeof(h), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 512; ++i) count += h[i] != 0;
+    }
+    *nonzero = count;
     return 0;
 }
 

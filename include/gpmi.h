@@ -559,6 +559,20 @@ GPMI_API int gpmi_kernel_timing(gpmi_ctx *ctx, int reset, double *out9);
  * block's factorisation and is bounded by that latency chain). */
 GPMI_API int gpmi_kernel_timing_ex(gpmi_ctx *ctx, int reset, double *out12);
 
+/* Test hook for the invariant "no result depends on the contents of context-owned scratch at entry": synchronises the
+ * context's streams, sets every byte of every buffer of the context and of its grid lanes that holds only floating-point
+ * scratch -- the workspace W, the staging buffers, the device scratch, the packed-factor ring, the finalize sums, the result
+ * doubles, the parameter records of the device-parameter grids, the partial sums of gpmi_approx_Lz and the payload of the
+ * pinned buffer, each over its full allocation -- to `byte` (0..255; 0xFF makes every double a NaN, 0x7F 1.38e306), and
+ * synchronises again.  Counters, info words, the completion flag of the pinned buffer, the interpolation tables and the
+ * buffers of a gpmi_seq are state and are left alone; buffers not allocated yet are skipped.  Never called by the library
+ * itself.  GPMI_EARG: byte outside 0..255. */
+GPMI_API int gpmi_debug_fill(gpmi_ctx *ctx, int byte);
+/* *nonzero = the number of non-zero words among the 512 device counters of the context plus those of each grid lane, after a
+ * synchronisation: the counters the waiting kernels poll are zeroed at creation and left zero by every call, and this reads
+ * them back with a copy, without launching a kernel that would wait on them. */
+GPMI_API int gpmi_debug_counters(gpmi_ctx *ctx, int *nonzero);
+
 /* ---- probes: tools/ only ------------------------------------------------
  * Built into libgpmi_probes.so (-DGPMI_PROBES: `python -m gp_amd._build --probes`), never into the
  * shipped libgpmi.so: micro-benchmarks, the A/B kernel variants and their option names

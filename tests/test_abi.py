@@ -106,6 +106,27 @@ def test_null_context_is_an_error_not_a_crash():
     assert b"NULL" in h.gpmi_last_error()
 
 
+def test_debug_hooks_reject_a_null_context_and_declare_their_arguments():
+    """gpmi_debug_fill / gpmi_debug_counters (the workspace-history tests' hooks): GPMI_EARG for a NULL context, whatever the other
+    argument, without touching it; and _lib.load() declares their argument types, so a Python int cannot pass for the counter
+    pointer."""
+    import ctypes as C
+    from gp_amd import _lib
+    h = _lib.load()
+    assert h.gpmi_debug_fill.argtypes == (C.c_void_p, C.c_int)
+    assert h.gpmi_debug_counters.argtypes == (C.c_void_p, C.POINTER(C.c_int))
+    for byte in (0, 0xFF, 300, -1):
+        assert h.gpmi_debug_fill(None, byte) == -1
+        assert b"NULL" in h.gpmi_last_error()
+    n = C.c_int(-5)
+    assert h.gpmi_debug_counters(None, C.byref(n)) == -1 and n.value == -5
+    assert b"NULL" in h.gpmi_last_error()
+    assert h.gpmi_debug_counters(None, None) == -1
+    with pytest.raises(C.ArgumentError):
+        h.gpmi_debug_counters(None, 7)
+    assert "gpmi_debug_fill" in _lib.SYMBOLS and "gpmi_debug_counters" in _lib.SYMBOLS
+
+
 def test_r_shim_parses_and_matches_the_r_wrappers():
     """r/gpmi_shim.c is what `.Call` binds (it replaces covariance.cpp:6-9's Rcpp export); there is no R in the
     image, so it is parsed and type-checked by gcc against tests/r_api/ -- declarations of the R API it uses,
