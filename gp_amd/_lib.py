@@ -28,6 +28,7 @@ SYMBOLS = (
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
     "gpmi_interp_free", "gpmi_logml_grad", "gpmi_logml_grad_grid",
     "gpmi_logml_grad_dev", "gpmi_logml_grad_grid_dev", "gpmi_logml_grad_grid_ard", "gpmi_logml_grad_grid_ard_dev",
+    "gpmi_logml_loo", "gpmi_logml_loo_dev",
     "gpmi_joint_logml_grad", "gpmi_joint_logml_grad_dev", "gpmi_joint_logml_grad_grid",
     "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
@@ -452,6 +453,24 @@ class Context:
                                        _d(jitter), _p(out), _p(g)))
         return out, g
 
+    def logml_loo(self, X, y, alpha, ell, sigma, jitter=0.0, want_grad=True, outputs=("mu", "var", "lpd")):
+        """Exact leave-one-out cross-validation (gpmi_logml_loo): a dict of out3 (3,), loo (sum_i lpd_i), mu, var, lpd (n each:
+        mean, variance -- of the observation, noise included -- and log density of y_i given all the others), grad
+        (d loo / d(alpha, ell.., sigma); None without want_grad) and info (k > 0: not positive definite, every LOO output NaN;
+        nothing is raised for that status).  outputs: which of mu, var, lpd to compute (the others are None)."""
+        X = _mat(X); y = _vec(y); ell = _vec(ell)
+        n, D = X.shape
+        if y.size != n:
+            raise GpmiError(-1, "X and y disagree on N")
+        out = np.empty(3); loo = np.empty(1)
+        vec = {k: (np.empty(n) if k in outputs else None) for k in ("mu", "var", "lpd")}
+        g = np.empty(2 + ell.size) if want_grad else None
+        opt = lambda a: None if a is None else _p(a)
+        info = _chk(self._lib.gpmi_logml_loo(self._h, _p(X), n, max(n, 1), D, _p(y), _d(alpha), _p(ell), ell.size, _d(sigma),
+                                             _d(jitter), _p(out), _p(loo), opt(vec["mu"]), opt(vec["var"]), opt(vec["lpd"]), opt(g)),
+                    allow_info=True)
+        return {"out3": out, "loo": float(loo[0]), "mu": vec["mu"], "var": vec["var"], "lpd": vec["lpd"], "grad": g, "info": info}
+
     def logml_grad_grid(self, X, y, alpha, rho, sigma, jitter=0.0):
         """(out (G, 3), grad (G, 3), info (G,)): value and (d/dalpha, d/drho, d/dsigma) at G points, on the lanes."""
         X = _mat(X); y = _vec(y)
@@ -841,6 +860,16 @@ class Context:
         ell = _vec(ell)
         _chk(self._lib.gpmi_logml_grad_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _d(alpha), _p(ell),
                                            int(ell.size), _d(sigma), _d(jitter), _vp(dout_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
+
+    def logml_loo_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, ell, sigma, jitter, dout_ptr, dloo_ptr, dmu_ptr, dvar_ptr, dlpd_ptr,
+                      dgrad_ptr, dinfo_ptr):
+        """gpmi_logml_loo_dev on device pointers: d_out3 (3), d_loo (1), d_mu, d_var, d_lpd (n each), d_grad (2 + len(ell)) and
+        d_info (1 int) are written by the device (NaN LOO outputs and info = k when the matrix is not positive definite);
+        d_mu, d_var, d_lpd, d_grad may be 0 / None.  Enqueued, not synchronised, nothing is raised for that status."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_logml_loo_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _d(alpha), _p(ell),
+                                          int(ell.size), _d(sigma), _d(jitter), _vp(dout_ptr), _vp(dloo_ptr), _vp(dmu_ptr),
+                                          _vp(dvar_ptr), _vp(dlpd_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
 
     def logml_grad_grid_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, rho, sigma, jitter, dout_ptr, dgrad_ptr, dinfo_ptr):
         """gpmi_logml_grad_grid_dev: d_out3 (3 G), d_grad (3 G), d_info (G ints); alpha, rho, sigma: host arrays of one length."""

@@ -1458,6 +1458,12 @@ void launch_syrk_uut(const gpmi_ctx *c, hipStream_t s, const double *U, size_t l
     launch_syrk_lower(c, s, U, ldu, C, ldc, n, n, n, nullptr, 0, 1);
 }
 
+// C(lower) -= P P^T for a full n x n P: the trailing update's launch (tile walk, tail split) with nothing fused
+void launch_syrk_ppt(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int n)
+{
+    launch_syrk_lower(c, s, P, ldp, C, ldc, n, n, n, c->d_ctr, c->ncu);
+}
+
 // tune.block_recursive  1: in-block updates by recursive halving; 0: 128 / 256 / rest-of-block levels
 
 // One 128-column panel [k, k + kb): diagonal block, then the rows [max(k + kb, row_lo), row_hi) below it.

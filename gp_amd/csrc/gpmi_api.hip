@@ -2167,9 +2167,10 @@ __global__ __launch_bounds__(256) void k_upper_mv_sum(const double *__restrict__
 constexpr int GRAD_NS = 2 + GPMI_MAXD;           // slots per tile of the D <= 8 kernel
 constexpr int GRAD_NS_MAX = 2 + GPMI_MAXD_BIG;   // ... and the most the generic one writes (D = 64)
 static inline int grad_ns(int D) { return 2 + ((D + 7) / 8) * 8; }
-// KC (gpmi_centered_gp_lp_grad): a holds kc columns (leading dimension lda) and g = (sum_c a_ic a_jc + kc Wij) / 2, the columns
-// added in index order; the plain instance is the statement it always was
-template <bool KC = false>
+// KC == 1 (gpmi_centered_gp_lp_grad): a holds kc columns (leading dimension lda) and g = (sum_c a_ic a_jc + kc Wij) / 2, the
+// columns added in index order; the plain instance is the statement it always was.  KC == 2 (gpmi_logml_loo): a holds the two
+// columns a and b, W the lower triangle of -A diag(v) A, and g = (a_i b_j + b_i a_j) / 2 + Wij
+template <int KC = 0>
 __global__ __launch_bounds__(256) void k_grad_partial(const double *__restrict__ X, int n, int ldx, SeParams p,
                                                       const double *__restrict__ a, const double *__restrict__ W,
                                                       size_t ld, double *__restrict__ part, int kc, size_t lda)
@@ -2199,11 +2200,13 @@ __global__ __launch_bounds__(256) void k_grad_partial(const double *__restrict__
             }
             const double kse = p.a2 * exp(-0.5 * e);
             double g;
-            if constexpr (KC) {
+            if constexpr (KC == 1) {
                 double aa = ai * a[j];
                 for (int c = 1; c < kc; ++c) aa += a[(size_t)i + (size_t)c * lda] * a[(size_t)j + (size_t)c * lda];
                 g = 0.5 * (aa + (double)kc * W[(size_t)i + (size_t)j * ld]);
-            } else
+            } else if constexpr (KC == 2)
+                g = 0.5 * (ai * a[(size_t)j + lda] + a[(size_t)i + lda] * a[j]) + W[(size_t)i + (size_t)j * ld];
+            else
                 g = 0.5 * (ai * a[j] + W[(size_t)i + (size_t)j * ld]);
             const double w = (i == j) ? 1.0 : 2.0;
             acc[0] += w * g * kse;
@@ -2232,7 +2235,7 @@ __global__ __launch_bounds__(256) void k_grad_partial(const double *__restrict__
 // over the workgroup, one fixed-shape tree per dimension (deterministic).  Slots per tile: ns = 2 + roundup(D, 8):
 // [0] sum c, [1 + d] per dimension, [ns - 1] the diagonal term -- the layout of k_grad_partial for D <= 8.
 // O(N^2 D) next to the O(N^3) of K^-1: 64 trees per tile at D = 64 are noise.
-template <bool KC = false>
+template <int KC = 0>
 __global__ __launch_bounds__(256) void k_grad_partial_big(const double *__restrict__ X, int n, int ldx, SeParams p,
                                                           const double *__restrict__ a, const double *__restrict__ W,
                                                           size_t ld, double *__restrict__ part, int ns, int kc, size_t lda)
@@ -2278,11 +2281,13 @@ __global__ __launch_bounds__(256) void k_grad_partial_big(const double *__restri
         double cq = 0.0;
         if (i < n && j < n && j <= i) {
             double g;
-            if constexpr (KC) {
+            if constexpr (KC == 1) {
                 double aa = a[i] * a[j];
                 for (int c = 1; c < kc; ++c) aa += a[(size_t)i + (size_t)c * lda] * a[(size_t)j + (size_t)c * lda];
                 g = 0.5 * (aa + (double)kc * W[(size_t)i + (size_t)j * ld]);
-            } else
+            } else if constexpr (KC == 2)
+                g = 0.5 * (a[i] * a[(size_t)j + lda] + a[(size_t)i + lda] * a[j]) + W[(size_t)i + (size_t)j * ld];
+            else
                 g = 0.5 * (a[i] * a[j] + W[(size_t)i + (size_t)j * ld]);
             cq = ((i == j) ? 1.0 : 2.0) * g * (p.a2 * exp(-0.5 * e[q]));
             if (i == j) cdiag += g;
@@ -2464,14 +2469,15 @@ static bool grad_augmented(const gpmi_ctx *c, int n, bool many)
 //   contract(s, a, Wk, ld, part)  reduces the tile slots into part (ns() x ntiles() doubles) and finishes them; a = +-S^-1 obs
 //                                 (only products a_p a_q may enter), Wk the lower triangle of -S^-1, both in device memory
 
-// every buffer grad_chain_core(c, model of order n, ...) uses, at its final size
-static int grad_chain_reserve(gpmi_ctx *c, int n, int ns, size_t ntiles, bool many)
+// every buffer grad_chain_core(c, model of order n, ...) uses, at its final size; extra: doubles of the model's own behind the
+// tile slots (gpmi_logml_loo)
+static int grad_chain_reserve(gpmi_ctx *c, int n, int ns, size_t ntiles, bool many, size_t extra = 0)
 {
     int rc;
     if (grad_augmented(c, n, many)) {
         if ((rc = reserve_ws(c, 2 * n + 1, 2 * n + 1))) return rc;
         double *b;
-        return stage_buf(c, 3, ((size_t)GRAD_NS_MAX + ntiles * ns) * sizeof(double), &b);
+        return stage_buf(c, 3, ((size_t)GRAD_NS_MAX + ntiles * ns + extra) * sizeof(double), &b);
     }
     if ((rc = reserve_ws(c, n + 1, n))) return rc;
     const size_t ldu = (size_t)(((n + 15) / 16) * 16 + 16);
@@ -2479,7 +2485,7 @@ static int grad_chain_reserve(gpmi_ctx *c, int n, int ns, size_t ntiles, bool ma
     const int nchunk = (n + UMV_COLS - 1) / UMV_COLS;
     double *b;
     if ((rc = stage_buf(c, 2, ldu * (size_t)(n + 1) * sizeof(double), &b))) return rc;
-    if ((rc = stage_buf(c, 3, (2 * (size_t)n + GRAD_NS_MAX + ntiles * ns + (size_t)nchunk * n) * sizeof(double), &b))) return rc;
+    if ((rc = stage_buf(c, 3, (2 * (size_t)n + GRAD_NS_MAX + ntiles * ns + (size_t)nchunk * n + extra) * sizeof(double), &b))) return rc;
     return scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &b);
 }
 
@@ -3320,6 +3326,152 @@ extern "C" int gpmi_logml_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx
     launch_logml_grad_finish(c->stream, dres, GRAD_RES, d_info, 1, D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- exact leave-one-out cross-validation (Rasmussen & Williams 5.4.2) ---------------------------------------------------
+// All n hold-out predictions from A = S^-1 and a = A y, which grad_chain_core leaves on the device: d = diag A,
+// mu_i = y_i - a_i / d_i, var_i = 1 / d_i, lpd_i = -1/2 log(2 pi) + 1/2 log d_i - a_i^2 / (2 d_i), loo = sum_i lpd_i, and with
+// u = a / d, v = (1 + a^2 / d) / (2 d), b = A u:  d loo / d theta = <G, dS/dtheta>,  G = (b a' + a b') / 2 - A diag(v) A
+// (DESIGN.md section 8).  The model is SeGradModel's matrix and observations with this contraction:
+//   1. the point kernel (mu, var, lpd, loo; a with its sign, u, sqrt v);
+//   2. one pass over the 64 x 64 lower tiles of -A: M = A diag(sqrt v), both triangles, and b;
+//   3. C(lower) = -M M^T by the trailing update's SYRK, the target zeroed first;
+//   4. k_grad_partial[_big]<2> with g = (a_i b_j + b_i a_j) / 2 + C_ij, then k_grad_final.
+// Buffers: the three-chain route has M in U (stage[2], free after launch_syrk_uut) and C over the lower triangle of W, once b
+// and M are done; the augmented route has M in the top-left n x n block of W (L, no longer needed) and C in the rows n + 1 ..
+// of the columns 0 .. n - 1 (L^-T).  The vectors live behind the tile slots (and behind the mat-vec partials of the
+// three-chain route): a, b (2 n: the two columns of the contraction), u, sqrt v (n each), the tile partials of b
+// (loo_bpart_doubles), then mu, var, lpd of the host form (3 n).  Everything is written before it is read.
+static size_t loo_extra_doubles(int n) { return 7 * (size_t)n + loo_bpart_doubles(n); }
+static size_t loo_extra_offset(int n, size_t slots, bool aug)   // from the first tile slot
+{
+    return slots + (aug ? 0 : (size_t)((n + UMV_COLS - 1) / UMV_COLS) * n);
+}
+
+struct LooOut {
+    double *loo, *mu, *var, *lpd;   // mu, var, lpd nullable
+    bool grad;                      // false: the SYRK and the contraction are skipped (se.sums stays unwritten)
+};
+struct SeLooModel {
+    SeGradModel se;
+    gpmi_ctx *c;
+    bool aug;          // the augmented route: av = -a, and its buffer plan
+    LooOut o;
+    hipError_t *err;   // the first failure of a runtime call inside contract()
+    int order() const { return se.order(); }
+    int ns() const { return se.ns(); }
+    size_t ntiles() const { return se.ntiles(); }
+    const double *obs() const { return se.obs(); }
+    void build(gpmi_ctx *cc, hipStream_t s, double *W, size_t ld) const { se.build(cc, s, W, ld); }
+    void contract(hipStream_t s, const double *av, const double *Wk, size_t ld, double *part) const
+    {
+        const int n = se.n;
+        double *ab = part + loo_extra_offset(n, ntiles() * ns(), aug), *u = ab + 2 * (size_t)n, *sv = u + n, *bpart = sv + n;
+        launch_loo_points(s, Wk, ld, n, av, aug ? -1.0 : 1.0, se.dy, c->d_info, o.mu, o.var, o.lpd, ab, u, sv, o.loo);
+        if (!o.grad) return;
+        double *M = aug ? c->W : c->stage[2], *C = aug ? c->W + (n + 1) : c->W;
+        const size_t ldm = aug ? ld : (size_t)(((n + 15) / 16) * 16 + 16);
+        launch_loo_tiles(s, Wk, ld, n, u, sv, M, ldm, bpart, ab + n);
+        if (aug)
+            *err = hipMemset2DAsync(C, ld * sizeof(double), 0, (size_t)n * sizeof(double), (size_t)n, s);
+        else
+            *err = hipMemsetAsync(C, 0, ld * (size_t)n * sizeof(double), s);
+        if (*err != hipSuccess) return;
+        launch_syrk_ppt(c, s, M, ldm, C, ld, n);
+        const unsigned T = (unsigned)((n + 63) / 64);
+        if (se.p.D <= GPMI_MAXD)
+            hipLaunchKernelGGL(k_grad_partial<2>, dim3(T, T), 256, 0, s, se.dX, n, se.ldx, se.p, ab, C, ld, part, 2, (size_t)n);
+        else
+            hipLaunchKernelGGL(k_grad_partial_big<2>, dim3(T, T), 256, 0, s, se.dX, n, se.ldx, se.p, ab, C, ld, part, ns(), 2, (size_t)n);
+        hipLaunchKernelGGL(k_grad_final, dim3(1), 1024, 0, s, part, ntiles(), se.sums, ns());
+    }
+};
+
+static int logml_loo_reserve(gpmi_ctx *c, int n, int D, bool many = false)
+{
+    const size_t T = (size_t)((n + 63) / 64);
+    return grad_chain_reserve(c, n, grad_ns(D), T * (T + 1) / 2, many, loo_extra_doubles(n));
+}
+
+// the host form's mu, var, lpd (3 n doubles) once logml_loo_reserve has run
+static double *logml_loo_host_vectors(const gpmi_ctx *c, int n, int D, bool many = false)
+{
+    const bool aug = grad_augmented(c, n, many);
+    const size_t T = (size_t)((n + 63) / 64);
+    double *part = c->stage[3] + (aug ? 0 : 2 * (size_t)n) + GRAD_NS_MAX;
+    return part + loo_extra_offset(n, T * (T + 1) / 2 * grad_ns(D), aug) + 4 * (size_t)n + loo_bpart_doubles(n);
+}
+
+static int logml_loo_check(int n, int ldx, int D, double alpha, double sigma, bool ptrs)
+{
+    if (n < 1 || ldx < n || D < 1 || D > GPMI_MAXD_BIG || !ptrs) return gpmi_fail(GPMI_EARG, "bad argument");
+    if (!(alpha > 0.0)) return gpmi_fail(GPMI_EARG, "alpha must be positive");
+    if (!(sigma >= 0.0)) return gpmi_fail(GPMI_EARG, "sigma must not be negative");
+    return 0;
+}
+
+// The device part, enqueued on c->stream without synchronisation; d_mu, d_var, d_lpd, d_grad nullable.  The contraction sums
+// go through the second half of the finalize scratch, as gpmi_logml_grad's do.
+static int logml_loo_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double alpha,
+                          const double *ell, int n_ell, double sigma, double jitter, double *d_out3, double *d_loo, double *d_mu,
+                          double *d_var, double *d_lpd, double *d_grad, int *d_info, bool many = false)
+{
+    int rc;
+    if ((rc = logml_loo_reserve(c, n, p.D, many))) return rc;
+    double *sums = c->d_fin + 4096 + 3;
+    hipError_t err = hipSuccess;
+    const SeLooModel m{SeGradModel{dX, n, ldx, dy, p, sigma * sigma + jitter, sums}, c, grad_augmented(c, n, many),
+                       LooOut{d_loo, d_mu, d_var, d_lpd, d_grad != nullptr}, &err};
+    if ((rc = grad_chain_core(c, m, d_out3, d_info, many))) return rc;
+    HIPCHK(err);
+    if (d_grad) launch_loo_grad_finish(c->stream, sums, p.D, grad_ns(p.D), alpha, ell, n_ell, sigma, d_info, d_grad);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_logml_loo_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, double alpha,
+                                  const double *ell, int n_ell, double sigma, double jitter, double *d_out3, double *d_loo,
+                                  double *d_mu, double *d_var, double *d_lpd, double *d_grad, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = logml_loo_check(n, ldx, D, alpha, sigma, dX && dy && d_out3 && d_loo && d_info))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    return logml_loo_core(c, dX, n, ldx, dy, p, alpha, ell, n_ell, sigma, jitter, d_out3, d_loo, d_mu, d_var, d_lpd, d_grad, d_info);
+}
+
+extern "C" int gpmi_logml_loo(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double alpha, const double *ell,
+                              int n_ell, double sigma, double jitter, double *out3, double *loo, double *mu, double *var, double *lpd,
+                              double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = logml_loo_check(n, ldx, D, alpha, sigma, X && y && out3 && loo))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    double *dX, *dy;
+    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
+    if ((rc = logml_loo_reserve(c, n, D))) return rc;
+    // the record: out3, the contraction sums, loo, grad
+    constexpr int LOO_RES = GRAD_RES + 1 + GRAD_NS_MAX;
+    double *dres = c->d_fin + 4096, *dv = logml_loo_host_vectors(c, n, D);
+    double *dmu = mu ? dv : nullptr, *dvar = var ? dv + n : nullptr, *dlpd = lpd ? dv + 2 * (size_t)n : nullptr;
+    if ((rc = logml_loo_core(c, dX, n, n, dy, p, alpha, ell, n_ell, sigma, jitter, dres, dres + GRAD_RES, dmu, dvar, dlpd,
+                             grad ? dres + GRAD_RES + 1 : nullptr, c->d_info + 1)))
+        return rc;
+    double hr[LOO_RES];
+    if ((rc = d2h_matrix(c, dres, LOO_RES, LOO_RES, 1, hr, LOO_RES))) return rc;
+    if (mu && (rc = d2h_matrix(c, dmu, n, n, 1, mu, n))) return rc;
+    if (var && (rc = d2h_matrix(c, dvar, n, n, 1, var, n))) return rc;
+    if (lpd && (rc = d2h_matrix(c, dlpd, n, n, 1, lpd, n))) return rc;
+    const int info = staged_finish(c, c->d_info + 1);
+    if (info < 0) return info;
+    for (int k = 0; k < 3; ++k) out3[k] = hr[k];
+    *loo = hr[GRAD_RES];
+    if (grad)
+        for (int k = 0; k < 2 + n_ell; ++k) grad[k] = hr[GRAD_RES + 1 + k];
+    return info;
 }
 
 // The device part of every value + gradient grid that the device finishes: G points with n_ell (1 or D) length-scales each

@@ -229,7 +229,21 @@ void launch_gemm_tri_lower(hipStream_t s, const double *A, size_t lda, const dou
 void launch_gemm_nt(const gpmi_ctx *c, hipStream_t s, const double *A, size_t lda, const double *B, size_t ldb,
                     double *C, size_t ldc, int M, int N, int K, int accumulate_minus);
 void launch_syrk_uut(const gpmi_ctx *c, hipStream_t s, const double *U, size_t ldu, double *C, size_t ldc, int n);
+// C(lower) -= P P^T for a full n x n P (the general form of the trailing update's launch)
+void launch_syrk_ppt(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int n);
 void launch_pack_factors(hipStream_t s, const double *L, size_t ldl, int n, double *Fpack_all);
+// ---- kernel launchers (loo_kernels.hip): leave-one-out cross-validation from -S^-1 (lower triangle, Wk) and +-S^-1 y (av) ----
+// mu, var, lpd (n each, nullable), *loo, and the vectors of the gradient: ab[0 .. n) = a = asign av, u = a / d, sv = sqrt(v);
+// NaN outputs when *info != 0
+void launch_loo_points(hipStream_t s, const double *Wk, size_t ld, int n, const double *av, double asign, const double *y,
+                       const int *info, double *mu, double *var, double *lpd, double *ab, double *u, double *sv, double *loo);
+// M (n x n, both triangles, ldm) = S^-1 diag(sv) and b = S^-1 u; bpart: loo_bpart_doubles(n) doubles of scratch
+size_t loo_bpart_doubles(int n);
+void launch_loo_tiles(hipStream_t s, const double *Wk, size_t ld, int n, const double *u, const double *sv, double *M, size_t ldm,
+                      double *bpart, double *b);
+// grad (2 + n_ell) from the contraction sums (ns slots), NaN when *info != 0
+void launch_loo_grad_finish(hipStream_t s, const double *sums, int D, int ns, double alpha, const double *ell, int n_ell, double sigma,
+                            const int *info, double *grad);
 // ---- kernel launchers (small_kernels.hip): a whole evaluation by ONE workgroup of one launch -----------------
 // the partial factorisation alone (what launch_potrf_partial runs at M <= tune.small_m)
 void launch_potrf_small(hipStream_t s, double *W, size_t ld, int M, int ncol, int nfac, int *d_info);

@@ -260,6 +260,28 @@ GPMI_API int gpmi_logml_grad_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx
                                  double alpha, const double *ell, int n_ell, double sigma, double jitter,
                                  double *d_out3, double *d_grad, int *d_info);
 
+/* Exact leave-one-out cross-validation of the same model (Rasmussen and Williams, section 5.4.2): how well the fit predicts
+ * each observation from all the others, in closed form from S^-1 and a = S^-1 y (d = diag S^-1), by ONE factorisation.
+ *   out3       as gpmi_logml
+ *   loo   (1)  sum_i lpd_i, the LOO log pseudo-likelihood
+ *   mu    (n)  E[y_i | y_-i]   = y_i - a_i / d_i
+ *   var   (n)  Var[y_i | y_-i] = 1 / d_i, of the OBSERVATION (noise and jitter included)
+ *   lpd   (n)  log p(y_i | y_-i) = -1/2 log(2 pi) + 1/2 log d_i - a_i^2 / (2 d_i): the pointwise values loo::loo takes
+ *   grad  (2 + n_ell)  d loo / d(alpha, ell.., sigma), in the order of gpmi_logml_grad
+ * mu, var, lpd and grad may be NULL; without grad the call costs what gpmi_logml_grad costs, with it one more n^3-flop
+ * symmetric product.  Status codes as gpmi_logml_grad: k > 0 (not positive definite) leaves out3 as gpmi_logml_grad does
+ * and NaN in every LOO output.  GPMI_EARG: n < 1, D outside 1..64, ldx < n, alpha <= 0, a length-scale <= 0, sigma < 0, a
+ * NULL pointer other than mu, var, lpd, grad.  Sums run in a fixed order: repeated calls give identical bits. */
+GPMI_API int gpmi_logml_loo(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, const double *y,
+                            double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                            double *out3, double *loo, double *mu, double *var, double *lpd, double *grad);
+/* ... with device-resident X, y and outputs (d_info: 1 int): enqueued on the context's stream, no synchronisation; the
+ * device writes every output, NaN when the matrix is not positive definite (ell: host).  The bits of the host form. */
+GPMI_API int gpmi_logml_loo_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                                double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                                double *d_out3, double *d_loo, double *d_mu, double *d_var, double *d_lpd, double *d_grad,
+                                int *d_info);
+
 /* gpmi_logml_grad_grid on device-resident data: d_out3 3 G, d_grad 3 G, d_info G (alpha, rho, sigma: host arrays) */
 GPMI_API int gpmi_logml_grad_grid_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
                                       const double *alpha, const double *rho, const double *sigma, int G, double jitter,

@@ -137,7 +137,14 @@ gp_log_marginal <- function(X, y, alpha, rho, sigma, jitter = 0)
 gp_log_marginal_grad <- function(X, y, alpha, rho, sigma, jitter = 0)
   .Call("gpmi_R_logml_grad", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)
 
-# the same for several chains' (alpha, rho, sigma) at once (rstan: chains = 4), concurrently on the GPU
+# exact leave-one-out cross-validation of the fitted model (Rasmussen & Williams 5.4.2), one factorisation for all n points:
+# list(value, loo = sum(lpd), mu, var, lpd, grad).  lpd is the pointwise log predictive density log p(y_i | y_-i):
+# loo::loo(matrix(fit$lpd, nrow = 1)) takes it as a 1 x n pointwise matrix; grad = d loo / d(alpha, rho.., sigma) makes the
+# LOO log pseudo-likelihood a second objective for optim()
+gp_loo <- function(X, y, alpha, rho, sigma, jitter = 0, want_grad = TRUE)
+  .Call("gpmi_R_logml_loo", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter, as.integer(want_grad))
+
+# gp_log_marginal_grad for several chains' (alpha, rho, sigma) at once (rstan: chains = 4), concurrently on the GPU
 gp_log_marginal_grad_chains <- function(X, y, alpha, rho, sigma, jitter = 0) {
   G <- max(length(alpha), length(rho), length(sigma))   # R recycling: gp_log_marginal_grad_chains(X, y, 1, rho_vec, 0.1)
   .Call("gpmi_R_logml_grad_grid", as.matrix(X), as.double(y), rep_len(as.double(alpha), G), rep_len(as.double(rho), G),

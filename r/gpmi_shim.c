@@ -381,6 +381,31 @@ SEXP gpmi_R_logml_grad(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP ji
     return out;
 }
 
+/* exact leave-one-out cross-validation (gpmi_logml_loo): list(value = c(logml, sum log L_ii, z'z), loo = sum(lpd), mu, var, lpd
+ * (length n: mean, variance of the observation and log density of y_i given the others), grad = d loo / d(alpha, ell.., sigma)
+ * or NULL when want_grad is 0) */
+SEXP gpmi_R_logml_loo(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter, SEXP want_grad)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), ne = Rf_length(ell), wg = Rf_asInteger(want_grad) != 0;
+    need(is_real(X) && is_real(y) && is_real(ell), "X, y and the length-scales must be double");
+    need(Rf_length(y) == n, "length(y) must equal nrow(X)");
+    need(ne == 1 || ne == D, "length-scale must have length 1 or ncol(X)");
+    SEXP val = PROTECT(Rf_allocVector(REALSXP, 3)), loo = PROTECT(Rf_allocVector(REALSXP, 1));
+    SEXP mu = PROTECT(Rf_allocVector(REALSXP, n)), var = PROTECT(Rf_allocVector(REALSXP, n)), lpd = PROTECT(Rf_allocVector(REALSXP, n));
+    SEXP g = PROTECT(wg ? Rf_allocVector(REALSXP, 2 + ne) : R_NilValue);
+    int rc = gpmi_logml_loo(ctx(), REAL(X), n, n, D, REAL(y), Rf_asReal(alpha), REAL(ell), ne, Rf_asReal(sigma), Rf_asReal(jitter),
+                            REAL(val), REAL(loo), REAL(mu), REAL(var), REAL(lpd), wg ? REAL(g) : NULL);
+    static const char *nm[6] = {"value", "loo", "mu", "var", "lpd", "grad"};
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 6)), names = PROTECT(Rf_allocVector(STRSXP, 6));
+    SET_VECTOR_ELT(out, 0, val); SET_VECTOR_ELT(out, 1, loo); SET_VECTOR_ELT(out, 2, mu); SET_VECTOR_ELT(out, 3, var);
+    SET_VECTOR_ELT(out, 4, lpd); SET_VECTOR_ELT(out, 5, g);
+    for (int i = 0; i < 6; ++i) SET_STRING_ELT(names, i, Rf_mkChar(nm[i]));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(8);
+    check(rc);
+    return out;
+}
+
 /* value + gradient at G points (one per chain): list(value = 3 x G, grad = 3 x G (d/dalpha, d/drho, d/dsigma), info) */
 SEXP gpmi_R_logml_grad_grid(SEXP X, SEXP y, SEXP alpha, SEXP rho, SEXP sigma, SEXP jitter)
 {
