@@ -28,7 +28,7 @@ SYMBOLS = (
     "gpmi_interp_build", "gpmi_interp_load", "gpmi_approx_L", "gpmi_approx_Lz", "gpmi_approx_Lz_dev", "gpmi_approx_Lz_grad", "gpmi_approx_Lz_grad_dev",
     "gpmi_interp_free", "gpmi_logml_grad", "gpmi_logml_grad_grid",
     "gpmi_logml_grad_dev", "gpmi_logml_grad_grid_dev", "gpmi_logml_grad_grid_ard", "gpmi_logml_grad_grid_ard_dev",
-    "gpmi_logml_loo", "gpmi_logml_loo_dev",
+    "gpmi_logml_loo", "gpmi_logml_loo_dev", "gpmi_logml_hess", "gpmi_logml_hess_dev",
     "gpmi_joint_logml_grad", "gpmi_joint_logml_grad_dev", "gpmi_joint_logml_grad_grid",
     "gpmi_approx_Lz_vjp", "gpmi_approx_Lz_vjp_dev", "gpmi_interp_gp_build", "gpmi_interp_gp_load", "gpmi_interp_gp_L",
     "gpmi_interp_gp_Lz", "gpmi_interp_gp_Lz_vjp", "gpmi_interp_gp_Lz_vjp_dev", "gpmi_interp_gp_free",
@@ -471,6 +471,22 @@ class Context:
                     allow_info=True)
         return {"out3": out, "loo": float(loo[0]), "mu": vec["mu"], "var": vec["var"], "lpd": vec["lpd"], "grad": g, "info": info}
 
+    def logml_hess(self, X, y, alpha, ell, sigma, jitter=0.0, want_grad=True):
+        """Value, gradient and exact Hessian of the log marginal likelihood in theta = (alpha, ell.., sigma) (gpmi_logml_hess): a
+        dict of out3 (3,), grad (q = 2 + len(ell); None without want_grad), hess (q x q, symmetric, natural parameters) and info
+        (k > 0: not positive definite, grad and hess all NaN; nothing is raised for that status).  One length-scale for any D, or
+        one per dimension up to D = 8."""
+        X = _mat(X); y = _vec(y); ell = _vec(ell)
+        n, D = X.shape
+        if y.size != n:
+            raise GpmiError(-1, "X and y disagree on N")
+        q = 2 + ell.size
+        out = np.empty(3); H = np.empty((q, q), order="F")
+        g = np.empty(q) if want_grad else None
+        info = _chk(self._lib.gpmi_logml_hess(self._h, _p(X), n, max(n, 1), D, _p(y), _d(alpha), _p(ell), ell.size, _d(sigma),
+                                              _d(jitter), _p(out), None if g is None else _p(g), _p(H), q), allow_info=True)
+        return {"out3": out, "grad": g, "hess": H, "info": info}
+
     def logml_grad_grid(self, X, y, alpha, rho, sigma, jitter=0.0):
         """(out (G, 3), grad (G, 3), info (G,)): value and (d/dalpha, d/drho, d/dsigma) at G points, on the lanes."""
         X = _mat(X); y = _vec(y)
@@ -870,6 +886,15 @@ class Context:
         _chk(self._lib.gpmi_logml_loo_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _d(alpha), _p(ell),
                                           int(ell.size), _d(sigma), _d(jitter), _vp(dout_ptr), _vp(dloo_ptr), _vp(dmu_ptr),
                                           _vp(dvar_ptr), _vp(dlpd_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
+
+    def logml_hess_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, ell, sigma, jitter, dout_ptr, dgrad_ptr, dhess_ptr, ldh, dinfo_ptr):
+        """gpmi_logml_hess_dev on device pointers: d_out3 (3), d_grad (2 + len(ell); may be 0 / None), d_hess (q x q, leading
+        dimension ldh) and d_info (1 int) are written by the device (NaN grad and hess and info = k when the matrix is not positive
+        definite).  Enqueued, not synchronised, nothing is raised for that status."""
+        ell = _vec(ell)
+        _chk(self._lib.gpmi_logml_hess_dev(self._h, _vp(dX_ptr), int(n), int(ldx), int(D), _vp(dy_ptr), _d(alpha), _p(ell),
+                                           int(ell.size), _d(sigma), _d(jitter), _vp(dout_ptr), _vp(dgrad_ptr), _vp(dhess_ptr),
+                                           int(ldh), _vp(dinfo_ptr)))
 
     def logml_grad_grid_dev(self, dX_ptr, n, ldx, D, dy_ptr, alpha, rho, sigma, jitter, dout_ptr, dgrad_ptr, dinfo_ptr):
         """gpmi_logml_grad_grid_dev: d_out3 (3 G), d_grad (3 G), d_info (G ints); alpha, rho, sigma: host arrays of one length."""

@@ -300,7 +300,7 @@ extern "C" int gpmi_destroy(gpmi_ctx *c)
         for (int l = 0; l < 7; ++l)
             if (c->lane[l]) gpmi_destroy(c->lane[l]);
         double *dev_bufs[] = {c->W, c->Fpack, c->itp_L, c->itp_dL, c->itp_part, c->d_out, c->d_fin, c->scratch,
-                              c->stage[0], c->stage[1], c->stage[2], c->stage[3], c->igp_M, c->igp_aux};
+                              c->stage[0], c->stage[1], c->stage[2], c->stage[3], c->igp_M, c->igp_aux, c->hess_buf};
         for (double *b : dev_bufs)
             if (b) (void)hipFree(b);
         if (c->d_info) (void)hipFree(c->d_info);
@@ -3474,6 +3474,129 @@ extern "C" int gpmi_logml_loo(gpmi_ctx *c, const double *X, int n, int ldx, int 
     return info;
 }
 
+// ---- the exact Hessian of the log marginal likelihood in (alpha, ell.., sigma) ---------------------------------------------
+// H_ij = <G, S_ij> - b_i' A b_j + 1/2 sum_kl P_i[k,l] P_j[l,k] with A = S^-1, a = A y, G = (a a' - A) / 2, b_i = S_i a, P_i = A S_i
+// (the kernels and their order: hess_kernels.hip).  The model is SeGradModel's matrix, observations AND
+// contraction -- the gradient's launches are the ones gpmi_logml_grad_dev makes, hence its bits -- followed by the Hessian's
+// launches on the A and a the chain leaves behind.  Both chain routes, every n; the matrices (the full A, n_ell weighted
+// matrices, n_ell products), vectors and partial sums live in a buffer of their own (c->hess_buf), reserved with the chain's
+// buffers before anything is enqueued.  Everything is written before it is read.
+static int hess_buf_reserve(gpmi_ctx *c, int n, int n_ell)
+{
+    const size_t bytes = (hess_buf_doubles(n, n_ell) + 4096) * sizeof(double);   // slack for tile over-reads
+    if (bytes > c->hess_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->hess_buf) HIPCHK(hipFree(c->hess_buf));
+        c->hess_buf = nullptr;
+        c->hess_bytes = 0;
+        if (hipMalloc((void **)&c->hess_buf, bytes) != hipSuccess)
+            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes for the Hessian's matrices", bytes);
+        c->hess_bytes = bytes;
+    }
+    return 0;
+}
+
+struct SeHessModel {
+    SeGradModel se;
+    gpmi_ctx *c;
+    bool aug;          // the augmented route hands over -a
+    double alpha;
+    const double *ell;
+    int n_ell;
+    double sigma;
+    double *d_hess;
+    int ldh;
+    int order() const { return se.order(); }
+    int ns() const { return se.ns(); }
+    size_t ntiles() const { return se.ntiles(); }
+    const double *obs() const { return se.obs(); }
+    void build(gpmi_ctx *cc, hipStream_t s, double *W, size_t ld) const { se.build(cc, s, W, ld); }
+    void contract(hipStream_t s, const double *av, const double *Wk, size_t ld, double *part) const
+    {
+        se.contract(s, av, Wk, ld, part);   // the gradient's sums, as gpmi_logml_grad leaves them
+        launch_hess(c, s, c->hess_buf, se.dX, se.n, se.ldx, se.p, alpha, ell, n_ell, sigma, se.diag_add, se.dy, av, aug ? -1.0 : 1.0,
+                    Wk, ld, se.sums, se.ns(), c->d_info, d_hess, ldh);
+    }
+};
+
+// the arguments logml_loo_check and fill_params do not cover: n_ell <= GPMI_MAXD, ldh >= 2 + n_ell
+static int logml_hess_check_ell(int n_ell, int ldh)
+{
+    if (n_ell > GPMI_MAXD)
+        return gpmi_fail(GPMI_EARG, "the Hessian takes one length-scale, or one per dimension up to D = %d", GPMI_MAXD);
+    if (ldh < 2 + n_ell) return gpmi_fail(GPMI_EARG, "ldh = %d is below 2 + n_ell = %d", ldh, 2 + n_ell);
+    return 0;
+}
+
+static int logml_hess_reserve(gpmi_ctx *c, int n, int D, int n_ell)
+{
+    int rc;
+    if ((rc = logml_grad_reserve(c, n, D))) return rc;
+    return hess_buf_reserve(c, n, n_ell);
+}
+
+// The device part, enqueued on c->stream without synchronisation; d_grad nullable.  The record of the chain (value triple,
+// contraction sums) goes through the second half of the finalize scratch, as gpmi_logml_grad_dev's does.
+static int logml_hess_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double alpha,
+                           const double *ell, int n_ell, double sigma, double jitter, double *d_out3, double *d_grad, double *d_hess,
+                           int ldh, int *d_info)
+{
+    int rc;
+    if ((rc = logml_hess_reserve(c, n, p.D, n_ell))) return rc;
+    double *dres = c->d_fin + 4096;
+    const SeHessModel m{SeGradModel{dX, n, ldx, dy, p, sigma * sigma + jitter, dres + 3}, c, grad_augmented(c, n, false),
+                        alpha, ell, n_ell, sigma, d_hess, ldh};
+    if ((rc = grad_chain_core(c, m, dres, d_info, false))) return rc;
+    if (!d_grad) d_grad = hess_record(c->hess_buf, n, n_ell) + 3;   // the record's own slot: nobody reads it
+    launch_logml_grad_finish(c->stream, dres, GRAD_RES, d_info, 1, p.D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_logml_hess_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, const double *dy, double alpha,
+                                   const double *ell, int n_ell, double sigma, double jitter, double *d_out3, double *d_grad,
+                                   double *d_hess, int ldh, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = logml_loo_check(n, ldx, D, alpha, sigma, dX && dy && d_out3 && d_hess && d_info))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    if ((rc = logml_hess_check_ell(n_ell, ldh))) return rc;
+    return logml_hess_core(c, dX, n, ldx, dy, p, alpha, ell, n_ell, sigma, jitter, d_out3, d_grad, d_hess, ldh, d_info);
+}
+
+// The host form downloads what the device form's kernels wrote: the same bits.
+extern "C" int gpmi_logml_hess(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double alpha, const double *ell,
+                               int n_ell, double sigma, double jitter, double *out3, double *grad, double *hess, int ldh)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = logml_loo_check(n, ldx, D, alpha, sigma, X && y && out3 && hess))) return rc;
+    SeParams p;
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    if ((rc = logml_hess_check_ell(n_ell, ldh))) return rc;
+    double *dX, *dy;
+    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
+    if ((rc = logml_hess_reserve(c, n, D, n_ell))) return rc;
+    // the record: out3, grad, hess (packed)
+    constexpr int QMAX = 2 + GPMI_MAXD;
+    const int q = 2 + n_ell, len = 3 + q + q * q;
+    double *rec = hess_record(c->hess_buf, n, n_ell);
+    if ((rc = logml_hess_core(c, dX, n, n, dy, p, alpha, ell, n_ell, sigma, jitter, rec, rec + 3, rec + 3 + q, q, c->d_info + 1)))
+        return rc;
+    double hr[3 + QMAX + QMAX * QMAX];
+    if ((rc = d2h_matrix(c, rec, len, len, 1, hr, len))) return rc;
+    const int info = staged_finish(c, c->d_info + 1);
+    if (info < 0) return info;
+    for (int k = 0; k < 3; ++k) out3[k] = hr[k];
+    if (grad)
+        for (int k = 0; k < q; ++k) grad[k] = hr[3 + k];
+    for (int j = 0; j < q; ++j)
+        for (int i = 0; i < q; ++i) hess[(size_t)i + (size_t)j * ldh] = hr[3 + q + i + j * q];
+    return info;
+}
+
 // The device part of every value + gradient grid that the device finishes: G points with n_ell (1 or D) length-scales each
 // (ell: G x n_ell, point-major), grad: G x (2 + n_ell).  One workgroup per point (n <= small_ng, or small_ng1 for one point,
 // and D <= GPMI_MAXD: the isotropic kernel with its parameters as kernel arguments, the ARD one with them in device memory),
@@ -4736,6 +4859,7 @@ static int debug_sync_all(gpmi_ctx *c)
 //   W            the factorisation workspace and its slack
 //   stage[0..3]  staging of the host-buffer calls and chain intermediates; the info / status ints some calls carve out of them
 //                are outputs the call's own kernels write before the host reads them, never polled and never an index
+//   hess_buf     matrices, vectors and partial sums of gpmi_logml_hess
 //   scratch      device scratch of the one-launch calls (same remark)
 //   Fpack        ring of packed panel factors: written by the diagonal-block kernel before the panel solve reads it
 //   d_fin        slice sums of the finalize kernels
@@ -4765,6 +4889,7 @@ extern "C" int gpmi_debug_fill(gpmi_ctx *c, int byte)
             {x->W, x->W_bytes},
             {x->stage[0], x->stage_bytes[0]}, {x->stage[1], x->stage_bytes[1]},
             {x->stage[2], x->stage_bytes[2]}, {x->stage[3], x->stage_bytes[3]},
+            {x->hess_buf, x->hess_bytes},
             {x->scratch, x->scratch_bytes},
             {x->Fpack, (size_t)GPMI_FPACK_SLOTS * GPMI_FPACK * sizeof(double)},
             {x->d_fin, 65536}, {x->d_out, 64},

@@ -142,6 +142,9 @@ struct gpmi_ctx {
     int cal_want;            // ... the largest number a calibration run has searched for so far
     int lanes_active;        // inside a multi-lane call (grid, table build, batch): other lanes' kernels share the chip
     int calibrate;           // 1: run grid lanes on qstream[]; 0: on the lanes' plain streams
+    // gpmi_logml_hess: the full S^-1, the weighted matrices K o R_d, the products P_d and the vectors of the second-order terms
+    double *hess_buf;
+    size_t hess_bytes;
 };
 
 // event-pair recorder; begin/end bracket one launch on the context's stream
@@ -244,6 +247,16 @@ void launch_loo_tiles(hipStream_t s, const double *Wk, size_t ld, int n, const d
 // grad (2 + n_ell) from the contraction sums (ns slots), NaN when *info != 0
 void launch_loo_grad_finish(hipStream_t s, const double *sums, int D, int ns, double alpha, const double *ell, int n_ell, double sigma,
                             const int *info, double *grad);
+// ---- kernel launchers (hess_kernels.hip): the Hessian of the log marginal likelihood from -S^-1 (lower triangle, Wk), +-S^-1 y
+// (av, a = asign av) and the finished sums of the gradient's contraction (gsums, gns slots) ----
+// doubles of the Hessian's own buffer (the full S^-1, n_ell weighted matrices, n_ell products, vectors, partial sums, record)
+size_t hess_buf_doubles(int n, int n_ell);
+// the result record inside that buffer: 3 + (2 + n_ell) + (2 + n_ell)^2 doubles for out3, grad and a packed hess
+double *hess_record(double *buf, int n, int n_ell);
+// hess (q x q, ldh, q = 2 + n_ell; both triangles, NaN when *info != 0), every launch on s
+void launch_hess(const gpmi_ctx *c, hipStream_t s, double *buf, const double *X, int n, int ldx, const SeParams &p, double alpha,
+                 const double *ell, int n_ell, double sigma, double diag_add, const double *y, const double *av, double asign,
+                 const double *Wk, size_t ld, const double *gsums, int gns, const int *info, double *hess, int ldh);
 // ---- kernel launchers (small_kernels.hip): a whole evaluation by ONE workgroup of one launch -----------------
 // the partial factorisation alone (what launch_potrf_partial runs at M <= tune.small_m)
 void launch_potrf_small(hipStream_t s, double *W, size_t ld, int M, int ncol, int nfac, int *d_info);

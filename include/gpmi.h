@@ -282,6 +282,27 @@ GPMI_API int gpmi_logml_loo_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx,
                                 double *d_out3, double *d_loo, double *d_mu, double *d_var, double *d_lpd, double *d_grad,
                                 int *d_info);
 
+/* Value, gradient AND exact Hessian of gpmi_logml in theta = (alpha, ell[0 .. n_ell), sigma), q = 2 + n_ell, by ONE
+ * factorisation and one dense n x n x n product per length-scale: standard errors of fitted hyper-parameters (the inverse of
+ * -hess at the maximum), their Laplace approximation, Newton and trust-region steps.
+ *   out3  as gpmi_logml;  grad (q, nullable) as gpmi_logml_grad, with its bits wherever that call runs the chain
+ *   hess  (q x q, column-major, ldh >= q): hess[i + j ldh] = d^2 out3[0] / dtheta_i dtheta_j, both triangles written,
+ *         bit-for-bit symmetric; nothing outside the q rows of a column is written
+ * The parameters are the natural ones, in the order of grad; for log-parameters H_log = diag(theta) H diag(theta) +
+ * diag(theta o grad).  Status codes as gpmi_logml_grad: k > 0 (not positive definite) leaves out3 as gpmi_logml_grad does
+ * and NaN in every entry of grad and hess.  n_ell is 1 (any D <= 64) or D (D <= 8).  GPMI_EARG: n < 1, ldx < n, ldh < q,
+ * D outside 1..64, n_ell neither 1 nor D or above 8, alpha <= 0, a length-scale <= 0, sigma < 0, a NULL pointer other than
+ * grad; nothing is launched then.  GPMI_ENOMEM: the 2 n_ell + 1 matrices of n x n doubles cannot be allocated.  Sums run in
+ * a fixed order, without atomics: repeated calls give identical bits. */
+GPMI_API int gpmi_logml_hess(gpmi_ctx *ctx, const double *X, int n, int ldx, int D, const double *y,
+                             double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                             double *out3, double *grad /* nullable */, double *hess, int ldh);
+/* ... with device-resident X, y and outputs (d_info: 1 int; ell: host): enqueued on the context's stream, no
+ * synchronisation; the device writes every output, the NaNs and d_info = k included.  The bits of the host form. */
+GPMI_API int gpmi_logml_hess_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
+                             double alpha, const double *ell, int n_ell, double sigma, double jitter,
+                             double *d_out3, double *d_grad /* nullable */, double *d_hess, int ldh, int *d_info);
+
 /* gpmi_logml_grad_grid on device-resident data: d_out3 3 G, d_grad 3 G, d_info G (alpha, rho, sigma: host arrays) */
 GPMI_API int gpmi_logml_grad_grid_dev(gpmi_ctx *ctx, const double *dX, int n, int ldx, int D, const double *dy,
                                       const double *alpha, const double *rho, const double *sigma, int G, double jitter,

@@ -137,6 +137,12 @@ gp_log_marginal <- function(X, y, alpha, rho, sigma, jitter = 0)
 gp_log_marginal_grad <- function(X, y, alpha, rho, sigma, jitter = 0)
   .Call("gpmi_R_logml_grad", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)
 
+# value, gradient and the exact Hessian in c(alpha, rho.., sigma): list(value, grad, hess).  At the optimum of optim(),
+# sqrt(diag(solve(-fit$hess))) are the standard errors of the fitted hyper-parameters -- what optim(..., hessian = TRUE) gets
+# from 2 (2 + length(rho)) gradient calls to about half the digits.  One length-scale for any ncol(X), or one per column up to 8
+gp_log_marginal_hess <- function(X, y, alpha, rho, sigma, jitter = 0)
+  .Call("gpmi_R_logml_hess", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)
+
 # exact leave-one-out cross-validation of the fitted model (Rasmussen & Williams 5.4.2), one factorisation for all n points:
 # list(value, loo = sum(lpd), mu, var, lpd, grad).  lpd is the pointwise log predictive density log p(y_i | y_-i):
 # loo::loo(matrix(fit$lpd, nrow = 1)) takes it as a 1 x n pointwise matrix; grad = d loo / d(alpha, rho.., sigma) makes the

@@ -406,6 +406,27 @@ SEXP gpmi_R_logml_loo(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jit
     return out;
 }
 
+/* value, gradient and exact Hessian in (alpha, ell.., sigma) (gpmi_logml_hess): list(value = c(logml, sum log L_ii, z'z), grad,
+ * hess = the q x q matrix of second derivatives, q = 2 + length(ell)) */
+SEXP gpmi_R_logml_hess(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP jitter)
+{
+    int n = Rf_nrows(X), D = Rf_ncols(X), ne = Rf_length(ell), q = 2 + ne;
+    need(is_real(X) && is_real(y) && is_real(ell), "X, y and the length-scales must be double");
+    need(Rf_length(y) == n, "length(y) must equal nrow(X)");
+    need(ne == 1 || ne == D, "length-scale must have length 1 or ncol(X)");
+    SEXP val = PROTECT(Rf_allocVector(REALSXP, 3)), g = PROTECT(Rf_allocVector(REALSXP, q)), H = PROTECT(Rf_allocMatrix(REALSXP, q, q));
+    int rc = gpmi_logml_hess(ctx(), REAL(X), n, n, D, REAL(y), Rf_asReal(alpha), REAL(ell), ne, Rf_asReal(sigma), Rf_asReal(jitter),
+                             REAL(val), REAL(g), REAL(H), q);
+    static const char *nm[3] = {"value", "grad", "hess"};
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3)), names = PROTECT(Rf_allocVector(STRSXP, 3));
+    SET_VECTOR_ELT(out, 0, val); SET_VECTOR_ELT(out, 1, g); SET_VECTOR_ELT(out, 2, H);
+    for (int i = 0; i < 3; ++i) SET_STRING_ELT(names, i, Rf_mkChar(nm[i]));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(5);
+    check(rc);
+    return out;
+}
+
 /* value + gradient at G points (one per chain): list(value = 3 x G, grad = 3 x G (d/dalpha, d/drho, d/dsigma), info) */
 SEXP gpmi_R_logml_grad_grid(SEXP X, SEXP y, SEXP alpha, SEXP rho, SEXP sigma, SEXP jitter)
 {
