@@ -7,7 +7,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["se_kernels.hip", "chol_kernels.hip", "small_kernels.hip", "interp_kernels.hip", "latent_kernels.hip", "predict_kernels.hip", "loo_kernels.hip", "hess_kernels.hip", "gpmi_api.hip"]
+SOURCES = ["se_kernels.hip", "chol_kernels.hip", "small_kernels.hip", "interp_kernels.hip", "latent_kernels.hip", "predict_kernels.hip", "loo_kernels.hip", "hess_kernels.hip", "lowrank_kernels.hip", "gpmi_api.hip"]
 LIB = os.path.join(CSRC, "libgpmi.so")
 PROBES_LIB = os.path.join(CSRC, "libgpmi_probes.so")  # -DGPMI_PROBES: tools/ only, never loaded by the product
 

@@ -35,6 +35,8 @@ SYMBOLS = (
     "gpmi_seq_create", "gpmi_seq_step", "gpmi_seq_commit", "gpmi_seq_count", "gpmi_seq_destroy", "gpmi_seq_marginals",
     "gpmi_gp_predict", "gpmi_gp_predict_dev", "gpmi_gp_predict_joint", "gpmi_gp_predict_joint_dev",
     "gpmi_joint_predict", "gpmi_joint_predict_dev",
+    "gpmi_hermite_basis", "gpmi_hermite_basis_dev", "gpmi_lowrank_logml_grad", "gpmi_lowrank_logml_grad_dev",
+    "gpmi_lowrank_latent_lp_grad", "gpmi_lowrank_latent_lp_grad_dev",
     "gpmi_last_timing", "gpmi_kernel_timing", "gpmi_kernel_timing_ex", "gpmi_debug_fill", "gpmi_debug_counters",
 )
 # additionally exported by the probe build (libgpmi_probes.so, -DGPMI_PROBES; tools/ only)
@@ -358,6 +360,52 @@ class Context:
         sq = (lambda A: None if A is None else (A[:, 0] if one else A))
         return {"lik": float(out[0]), "dlik_dsigma": float(out[1]), "F": sq(F), "Fbar": sq(Fb), "Zbar": sq(Zb), "grad": g,
                 "info": int(info)}
+
+    # ---- low-rank (Hermite-eigenfunction) GP ------------------------------------------------------------------------------
+    def hermite_basis(self, x, M, scale, amp, l, want_dl=False):
+        """approx_L(M, scale, x, amp, l) of models/westbrook.stan:2-30 (gpmi_hermite_basis): Phi (n x M) with Phi Phi^T ->
+        amp^2 exp(-(x_i - x_j)^2 / (2 l^2)) as M grows; with want_dl also dPhi / dl.  x is 1-D."""
+        x = _vec(x)
+        n = x.size
+        Phi = np.empty((n, int(M)), order="F")
+        dPhi = np.empty((n, int(M)), order="F") if want_dl else None
+        ld = max(n, 1)
+        _chk(self._lib.gpmi_hermite_basis(self._h, _p(x), n, int(M), _d(scale), _d(amp), _d(l), _p(Phi), ld,
+                                          _p(dPhi) if want_dl else None, ld))
+        return (Phi, dPhi) if want_dl else Phi
+
+    def lowrank_logml_grad(self, x, y, M, scale, amp, l, sigma, want_grad=True, raise_not_pd=True):
+        """Log marginal likelihood of y ~ N(0, Phi Phi^T + sigma^2 I), Phi = hermite_basis(x, M, scale, amp, l), and its gradient
+        in (amp, l, sigma) (gpmi_lowrank_logml_grad).  Returns (out3, grad, info): out3 laid out as logml's.  A not positive
+        definite: raises NotPositiveDefinite, or with raise_not_pd=False returns the NaN outputs and info = the order."""
+        x = _vec(x); y = _vec(y)
+        if x.size != y.size:
+            raise GpmiError(-1, "x and y disagree on N")
+        out3 = np.empty(3)
+        g = np.empty(3) if want_grad else None
+        info = _chk(self._lib.gpmi_lowrank_logml_grad(self._h, _p(x), int(x.size), _p(y), int(M), _d(scale), _d(amp), _d(l), _d(sigma),
+                                                      _p(out3), _p(g) if want_grad else None), allow_info=not raise_not_pd)
+        return out3, g, int(info)
+
+    def lowrank_latent_lp_grad(self, x, M, scale, amp, l, z, family, Y, sigma=None, want_q=True, want_qbar=False):
+        """The likelihood part of a low-rank latent model's lp__ and its gradient (gpmi_lowrank_latent_lp_grad): q = Phi z, the
+        head `family` ("normal", "bernoulli_logit") on q against the columns of Y (n or n x m).  Returns a dict: lik,
+        dlik_dsigma, q, qbar (None unless asked for), zbar = Phi^T qbar, grad = (d lik / d amp, d lik / d l)."""
+        x = _vec(x); z = _vec(z)
+        n = x.size
+        Ym = _mat(Y)
+        if Ym.shape[0] != n or z.size != int(M):
+            raise GpmiError(-1, "x, z and Y disagree on N or M")
+        fam = lik_family(family)
+        if fam == LIK_FAMILIES["normal"] and sigma is None:
+            raise GpmiError(-1, "the normal head needs sigma")
+        out = np.empty(2); g = np.empty(2); zb = np.empty(int(M))
+        q = np.empty(n) if want_q else None
+        qb = np.empty(n) if want_qbar else None
+        _chk(self._lib.gpmi_lowrank_latent_lp_grad(self._h, _p(x), n, int(M), _d(scale), _d(amp), _d(l), _p(z), fam, _p(Ym),
+                                                   int(Ym.shape[1]), max(n, 1), _d(0.0 if sigma is None else sigma), _p(out),
+                                                   _p(q) if want_q else None, _p(qb) if want_qbar else None, _p(zb), _p(g)))
+        return {"lik": float(out[0]), "dlik_dsigma": float(out[1]), "q": q, "qbar": qb, "zbar": zb, "grad": g}
 
     def centered_gp_lp_grad(self, X, alpha, ell, F, family, Y=None, sigma=None, jitter=1e-9, raise_not_pd=True):
         """The centred latent GP's log-density and gradient with one factorisation (gpmi_centered_gp_lp_grad): the columns of F
@@ -832,6 +880,25 @@ class Context:
                                                   C.c_void_p(dout_ptr), C.c_void_p(dF_ptr) if dF_ptr else None, int(ldf),
                                                   C.c_void_p(dFbar_ptr) if dFbar_ptr else None, int(ldfb), C.c_void_p(dZbar_ptr),
                                                   int(ldzb), C.c_void_p(dgrad_ptr), C.c_void_p(dinfo_ptr)))
+
+    def hermite_basis_dev(self, dx_ptr, n, M, scale, amp, l, dPhi_ptr, ldp, ddPhi_ptr=None, lddp=0):
+        """gpmi_hermite_basis_dev on device pointers (ddPhi_ptr may be None); enqueued, not synchronised."""
+        _chk(self._lib.gpmi_hermite_basis_dev(self._h, _vp(dx_ptr), int(n), int(M), _d(scale), _d(amp), _d(l), _vp(dPhi_ptr), int(ldp),
+                                              _vp(ddPhi_ptr), int(lddp)))
+
+    def lowrank_logml_grad_dev(self, dx_ptr, n, dy_ptr, M, scale, amp, l, sigma, dout_ptr, dgrad_ptr, dinfo_ptr):
+        """gpmi_lowrank_logml_grad_dev on device pointers: d_out3 (3), d_grad (3; may be None) and d_info (1 int) are written by the
+        device (NaN and info = k when A is not positive definite); enqueued, not synchronised, nothing is raised for that status."""
+        _chk(self._lib.gpmi_lowrank_logml_grad_dev(self._h, _vp(dx_ptr), int(n), _vp(dy_ptr), int(M), _d(scale), _d(amp), _d(l),
+                                                   _d(sigma), _vp(dout_ptr), _vp(dgrad_ptr), _vp(dinfo_ptr)))
+
+    def lowrank_latent_lp_grad_dev(self, dx_ptr, n, M, scale, amp, l, dz_ptr, family, dY_ptr, m, ldy, sigma, dout_ptr, dq_ptr, dqbar_ptr,
+                                   dzbar_ptr, dgrad_ptr):
+        """gpmi_lowrank_latent_lp_grad_dev on device pointers (dq_ptr and dqbar_ptr may be None); enqueued, not synchronised."""
+        _chk(self._lib.gpmi_lowrank_latent_lp_grad_dev(self._h, _vp(dx_ptr), int(n), int(M), _d(scale), _d(amp), _d(l), _vp(dz_ptr),
+                                                       lik_family(family), _vp(dY_ptr), int(m), int(ldy),
+                                                       _d(0.0 if sigma is None else sigma), _vp(dout_ptr), _vp(dq_ptr), _vp(dqbar_ptr),
+                                                       _vp(dzbar_ptr), _vp(dgrad_ptr)))
 
     def centered_gp_lp_grad_dev(self, dX_ptr, n, ldx, D, alpha, ell, jitter, dF_ptr, k, ldf, family, dY_ptr, m, ldy, sigma, dout_ptr,
                                 dFgrad_ptr, ldfg, dgrad_ptr, dinfo_ptr):

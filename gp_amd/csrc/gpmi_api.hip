@@ -4823,6 +4823,134 @@ extern "C" int gpmi_seq_marginals(gpmi_seq *q, const double *Xs, int m, int ldxs
     return 0;
 }
 
+// ---- low-rank (Hermite-eigenfunction) GP: models/westbrook.stan:2-30 and its copies, spectral_test.R:6-27 ----------------------
+static bool pos_finite(double v) { return v > 0.0 && isfinite(v); }
+static int lowrank_check(int n, int M, double scale, double amp, double l)
+{
+    if (n < 1) return gpmi_fail(GPMI_EARG, "n must be at least 1");
+    if (M < 1 || M > GPMI_LR_MMAX) return gpmi_fail(GPMI_EARG, "M = %d unsupported (1..%d)", M, GPMI_LR_MMAX);
+    if (!pos_finite(scale) || !pos_finite(amp) || !pos_finite(l)) return gpmi_fail(GPMI_EARG, "scale, amp and l must be positive and finite");
+    return 0;
+}
+
+extern "C" int gpmi_hermite_basis_dev(gpmi_ctx *c, const double *dx, int n, int M, double scale, double amp, double l, double *dPhi,
+                                      int ldp, double *d_dPhi_dl, int lddp)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
+    if (ldp < n || (d_dPhi_dl && lddp < n)) return gpmi_fail(GPMI_EARG, "leading dimension below n");
+    if (!dx || !dPhi) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    launch_lr_basis(c->stream, dx, n, M, lr_params(scale, amp, l), dPhi, (size_t)ldp, d_dPhi_dl, (size_t)lddp);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_hermite_basis(gpmi_ctx *c, const double *x, int n, int M, double scale, double amp, double l, double *Phi, int ldp,
+                                  double *dPhi_dl, int lddp)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
+    if (ldp < n || (dPhi_dl && lddp < n)) return gpmi_fail(GPMI_EARG, "leading dimension below n");
+    if (!x || !Phi) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    StageCall sc(c);
+    const size_t x_ = sc.in(x, n, 1, n), P_ = sc.out(Phi, n, M, ldp), D_ = sc.out(dPhi_dl, n, M, lddp);
+    if ((rc = sc.begin())) return rc;
+    launch_lr_basis(c->stream, sc.dev(x_), n, M, lr_params(scale, amp, l), sc.dev(P_), (size_t)n, dPhi_dl ? sc.dev(D_) : nullptr, (size_t)n);
+    HIPCHK(hipGetLastError());
+    return sc.finish(nullptr);
+}
+
+static int lowrank_logml_core(gpmi_ctx *c, const double *dx, int n, const double *dy, int M, double scale, double amp, double l,
+                              double sigma, double *d_out3, double *d_grad, int *d_info)
+{
+    int rc;
+    double *scratch;
+    if ((rc = scratch_buf(c, lr_scratch_doubles(n, M) * sizeof(double), &scratch))) return rc;
+    launch_lr_logml(c->stream, dx, n, dy, M, lr_params(scale, amp, l), amp, sigma, scratch, d_out3, d_grad, d_info);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_lowrank_logml_grad_dev(gpmi_ctx *c, const double *dx, int n, const double *dy, int M, double scale, double amp,
+                                           double l, double sigma, double *d_out3, double *d_grad, int *d_info)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
+    if (!pos_finite(sigma)) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
+    if (!dx || !dy || !d_out3 || !d_info) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    return lowrank_logml_core(c, dx, n, dy, M, scale, amp, l, sigma, d_out3, d_grad, d_info);
+}
+
+extern "C" int gpmi_lowrank_logml_grad(gpmi_ctx *c, const double *x, int n, const double *y, int M, double scale, double amp, double l,
+                                       double sigma, double *out3, double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
+    if (!pos_finite(sigma)) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
+    if (!x || !y || !out3) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    StageCall sc(c);
+    const size_t x_ = sc.in(x, n, 1, n), y_ = sc.in(y, n, 1, n), o_ = sc.out(out3, 3, 1, 3), g_ = sc.out(grad, 3, 1, 3);
+    if ((rc = sc.begin())) return rc;
+    if ((rc = lowrank_logml_core(c, sc.dev(x_), n, sc.dev(y_), M, scale, amp, l, sigma, sc.dev(o_), grad ? sc.dev(g_) : nullptr, sc.info())))
+        return rc;
+    return sc.finish(sc.info());
+}
+
+static int lowrank_latent_check(int n, int M, double scale, double amp, double l, int family, int m, int ldy, double sigma)
+{
+    int rc;
+    if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
+    if (family != GPMI_LIK_NORMAL && family != GPMI_LIK_BERNOULLI_LOGIT)
+        return gpmi_fail(GPMI_EARG, "the low-rank latent form has the NORMAL and BERNOULLI_LOGIT heads");
+    return lik_head_check(family, 1, m, ldy, n, sigma, false);
+}
+
+static int lowrank_latent_core(gpmi_ctx *c, const double *dx, int n, int M, double scale, double amp, double l, const double *dz,
+                               const LatentHead &lh, double *d_out, double *dq, double *dqbar, double *dzbar, double *d_grad)
+{
+    int rc;
+    double *part;
+    if ((rc = scratch_buf(c, (size_t)lr_latent_blocks(n) * (4 + M) * sizeof(double), &part))) return rc;
+    launch_lr_latent(c->stream, dx, n, M, lr_params(scale, amp, l), amp, dz, lh, dq, dqbar, part, d_out, dzbar, d_grad);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gpmi_lowrank_latent_lp_grad_dev(gpmi_ctx *c, const double *dx, int n, int M, double scale, double amp, double l,
+                                               const double *dz, int family, const double *dY, int m, int ldy, double sigma,
+                                               double *d_out, double *dq, double *dqbar, double *dzbar, double *d_grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = lowrank_latent_check(n, M, scale, amp, l, family, m, ldy, sigma))) return rc;
+    if (!dx || !dz || !dY || !d_out || !dzbar || !d_grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    const LatentHead lh{family, dY, m, ldy, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    return lowrank_latent_core(c, dx, n, M, scale, amp, l, dz, lh, d_out, dq, dqbar, dzbar, d_grad);
+}
+
+extern "C" int gpmi_lowrank_latent_lp_grad(gpmi_ctx *c, const double *x, int n, int M, double scale, double amp, double l, const double *z,
+                                           int family, const double *Y, int m, int ldy, double sigma, double *out, double *q,
+                                           double *qbar, double *zbar, double *grad)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = lowrank_latent_check(n, M, scale, amp, l, family, m, ldy, sigma))) return rc;
+    if (!x || !z || !Y || !out || !zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
+    if (family == GPMI_LIK_BERNOULLI_LOGIT && (rc = bernoulli_y_check(Y, n, m, ldy))) return rc;
+    StageCall sc(c);
+    const size_t x_ = sc.in(x, n, 1, n), z_ = sc.in(z, M, 1, M), Y_ = sc.in(Y, n, m, ldy), o_ = sc.out(out, 2, 1, 2),
+                 q_ = sc.out(q, n, 1, n), qb_ = sc.out(qbar, n, 1, n), zb_ = sc.out(zbar, M, 1, M), g_ = sc.out(grad, 2, 1, 2);
+    if ((rc = sc.begin())) return rc;
+    const LatentHead lh{family, sc.dev(Y_), m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if ((rc = lowrank_latent_core(c, sc.dev(x_), n, M, scale, amp, l, sc.dev(z_), lh, sc.dev(o_), q ? sc.dev(q_) : nullptr,
+                                  qbar ? sc.dev(qb_) : nullptr, sc.dev(zb_), sc.dev(g_))))
+        return rc;
+    return sc.finish(nullptr);
+}
 
 // ---- diagnostics ---------------------------------------------------------------
 extern "C" int gpmi_last_timing(gpmi_ctx *c, double *ms3)

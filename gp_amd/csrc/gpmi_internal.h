@@ -257,6 +257,32 @@ double *hess_record(double *buf, int n, int n_ell);
 void launch_hess(const gpmi_ctx *c, hipStream_t s, double *buf, const double *X, int n, int ldx, const SeParams &p, double alpha,
                  const double *ell, int n_ell, double sigma, double diag_add, const double *y, const double *av, double asign,
                  const double *Wk, size_t ld, const double *gsums, int gns, const int *info, double *hess, int ldh);
+// ---- kernel launchers (lowrank_kernels.hip): the Hermite-eigenfunction low-rank GP ------------------------------------------
+// the scalars of one (scale, amp, l) the kernels build their recurrence coefficients from, kernel-argument resident
+struct LrPar {
+    double c0, dc0;   // psi_0 = c0 exp(-d2 x^2) and d c0 / d l
+    double d2, dd2;   // delta^2 and its l-derivative
+    double ab;        // alpha beta
+    double pl;        // d log p_k / d l (the same for every column)
+    double r, dr;     // eps^2 / (alpha^2 + delta^2 + eps^2) and its l-derivative
+};
+LrPar lr_params(double scale, double amp, double l);
+void launch_lr_basis(hipStream_t s, const double *x, int n, int M, const LrPar &P, double *Phi, size_t ldp, double *dPhi /* nullable */,
+                     size_t lddp);
+// rows per chunk and chunks of the Gram kernel (functions of n and M alone), doubles of one partial, and of the whole scratch
+// (partials and S) launch_lr_logml needs
+int lr_gram_rows(int n, int M);
+int lr_gram_chunks(int n, int M);
+size_t lr_part_doubles(int M);
+size_t lr_scratch_doubles(int n, int M);
+// out3, grad (3, nullable) and *info of gpmi_lowrank_logml_grad: the Gram kernel, then the finishing kernel
+void launch_lr_logml(hipStream_t s, const double *x, int n, const double *y, int M, const LrPar &P, double amp, double sigma,
+                     double *scratch, double *out3, double *grad, int *info);
+// gpmi_lowrank_latent_lp_grad; part: lr_latent_blocks(n) * (4 + M) doubles (unused by a single workgroup)
+struct LatentHead;
+int lr_latent_blocks(int n);
+void launch_lr_latent(hipStream_t s, const double *x, int n, int M, const LrPar &P, double amp, const double *z, const LatentHead &lh,
+                      double *q, double *qbar, double *part, double *out, double *zbar, double *grad);
 // ---- kernel launchers (small_kernels.hip): a whole evaluation by ONE workgroup of one launch -----------------
 // the partial factorisation alone (what launch_potrf_partial runs at M <= tune.small_m)
 void launch_potrf_small(hipStream_t s, double *W, size_t ld, int M, int ncol, int nfac, int *d_info);

@@ -269,3 +269,42 @@ def interpolated_gp_log_prob_grad(interp, y, l, sigma, z):
     [min(lp), max(lp)], :32) for a GPFactorInterpolator `interp`; lbar and Zbar from gpmi_interp_gp_Lz_vjp."""
     lp_ = np.asarray(interp.lp, float)
     return _interpolated_log_prob_grad(interp.ctx.interp_gp_Lz, interp.ctx.interp_gp_Lz_vjp, float(lp_.min()), float(lp_.max()), y, l, sigma, z)
+
+
+def fit_approx_gp_log_prob_grad(x, y, l, alpha, sigma, zm, M=None, scale=1.0, ctx=None):
+    """(lp__, d lp__/d(l, alpha, sigma, zm)) of models/fit_approx_gp.stan (zh = approx_L(M, scale, x, alpha, l) zm, the
+    Hermite-eigenfunction low-rank GP; no prior on sigma):
+        lp = 3 log l - 4 l - alpha^2 / 2 - zm'zm / 2 - N log sigma - |y - zh|^2 / (2 sigma^2) + log l + log alpha + log sigma.
+    One call of gpmi_lowrank_latent_lp_grad; conventions of exact_gp_log_prob_grad (`~` drops constants, the <lower=0> Jacobians
+    are included)."""
+    c = ctx or default_context()
+    zm = np.asarray(zm, float).ravel()
+    M = zm.size if M is None else int(M)
+    r = c.lowrank_latent_lp_grad(x, M, scale, alpha, l, zm, "normal", np.asarray(y, float).ravel(), sigma, want_q=False)
+    lp = (3.0 * math.log(l) - 4.0 * l - 0.5 * alpha * alpha - 0.5 * float(zm @ zm) + r["lik"] + math.log(l) + math.log(alpha)
+          + math.log(sigma))
+    grad = np.empty(3 + M)
+    grad[0] = r["grad"][1] + 4.0 / l - 4.0
+    grad[1] = r["grad"][0] - alpha + 1.0 / alpha
+    grad[2] = r["dlik_dsigma"] + 1.0 / sigma
+    grad[3:] = r["zbar"] - zm
+    return lp, grad
+
+
+def westbrook_log_prob_grad(x, y, z, sigma, l, M=None, scale=0.25, ctx=None):
+    """(lp__, d lp__/d(z, sigma, l)) of models/westbrook.stan (q = approx_L(M, scale, x, sigma, l) z; sigma is the basis'
+    amplitude; y in {0, 1}):
+        lp = 3 log l - 4 l - z_1^2 / (2 0.01^2) - sum_{k > 1} z_k^2 / 2 - sigma^2 / 2 + sum(y q - softplus(q)) + log sigma + log l.
+    One call of gpmi_lowrank_latent_lp_grad; conventions of westbrook_exact_log_prob_grad."""
+    c = ctx or default_context()
+    z = np.asarray(z, float).ravel()
+    M = z.size if M is None else int(M)
+    r = c.lowrank_latent_lp_grad(x, M, scale, sigma, l, z, "bernoulli_logit", np.asarray(y, float).ravel(), None, want_q=False)
+    w = np.ones(M)
+    w[0] = 1.0 / (0.01 * 0.01)
+    lp = 3.0 * math.log(l) - 4.0 * l - 0.5 * float(z @ (w * z)) - 0.5 * sigma * sigma + r["lik"] + math.log(sigma) + math.log(l)
+    grad = np.empty(M + 2)
+    grad[:M] = r["zbar"] - w * z
+    grad[M] = r["grad"][0] - sigma + 1.0 / sigma
+    grad[M + 1] = r["grad"][1] + 4.0 / l - 4.0
+    return lp, grad

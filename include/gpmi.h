@@ -585,6 +585,64 @@ GPMI_API int gpmi_seq_destroy(gpmi_seq *seq);
  * factor, hence no positive-definiteness status), or GPMI_EARG: m < 1, ldxs < m, a NULL pointer. */
 GPMI_API int gpmi_seq_marginals(gpmi_seq *seq, const double *Xs, int m, int ldxs, double *mean, double *var);
 
+/* ---- low-rank (Hermite-eigenfunction) GP -------------------------------- */
+
+/* The Mercer expansion of the squared-exponential kernel in 1-D: with a = 1 / (4 scale^2), eps^2 = 1 / (2 l^2), alpha^2 = 2 a,
+ * beta = (1 + 4 eps^2 / alpha^2)^(1/4), delta^2 = alpha^2 (beta^2 - 1) / 2 and Dn = alpha^2 + delta^2 + eps^2, for k = 1 .. M
+ *   Phi[i, k] = amp sqrt(lambda_k) phi_k(x_i),  lambda_k = sqrt(alpha^2 / Dn) (eps^2 / Dn)^(k-1),
+ *   phi_k(x) = sqrt(beta / (2^(k-1) (k-1)!)) exp(-delta^2 x^2) H_(k-1)(alpha beta x)   (physicists' Hermite polynomials),
+ * and Phi Phi^T -> amp^2 exp(-(x_i - x_j)^2 / (2 l^2)) as M grows.  `amp` is the `sigma` argument of the models' approx_L
+ * (renamed: sigma stays the noise), `scale` its `scale`.  The device evaluates the three-term recurrence of the columns and,
+ * for dPhi_dl, its forward tangent in l; every entry point below generates Phi with the same statements, hence the same bits.
+ * M <= GPMI_LR_MMAX.  GPMI_EARG for every function of this section: n < 1, M outside 1..GPMI_LR_MMAX, scale, amp or l not
+ * positive and finite, sigma not positive and finite where a noise is used, a leading dimension below n, m < 1, a NULL pointer
+ * not marked nullable; nothing is launched then.
+ *
+ * gpmi_hermite_basis: Phi (n x M, column-major, ldp) and optionally dPhi_dl (lddp); nothing outside the n rows of a column is
+ * written.  Replaces approx_L of models/westbrook.stan:2-30 (and its copies in fit_approx_gp, density_gp, diffusion_gp,
+ * diffusion_state_gp, fit_ko_approx, multiple_players) and bH of spectral_test.R:6-27. */
+#define GPMI_LR_MMAX 128
+GPMI_API int gpmi_hermite_basis(gpmi_ctx *ctx, const double *x, int n, int M, double scale, double amp, double l, double *Phi,
+                       int ldp, double *dPhi_dl /* nullable */, int lddp);
+/* the same with device-resident x, Phi, dPhi_dl, enqueued on the context's stream and not synchronised */
+GPMI_API int gpmi_hermite_basis_dev(gpmi_ctx *ctx, const double *dx, int n, int M, double scale, double amp, double l, double *dPhi,
+                           int ldp, double *d_dPhi_dl /* nullable */, int lddp);
+
+/* The marginal form y ~ N(0, Phi Phi^T + sigma^2 I) (the model westbrook.stan:72 compares with cov_exp_quad, marginalised over
+ * z) and its gradient.  With G = Phi^T Phi, A = sigma^2 I_M + G, b = Phi^T y, u = A^-1 b:
+ *   log|Sigma| = (n - M) log sigma^2 + log|A|,  y^T Sigma^-1 y = (y^T y - b^T u) / sigma^2.
+ *   out3[0] = log marginal likelihood (with -n/2 log 2 pi), out3[1] = 1/2 log|Sigma|, out3[2] = y^T Sigma^-1 y: the layout of
+ *   gpmi_logml, comparable entry by entry with the exact call once M has converged;
+ *   grad (3, nullable) = d out3[0] / d (amp, l, sigma).
+ * No n x M or n x n matrix is stored: the Gram products [Phi y]^T [Phi y dPhi/dl] are reduced over chunks of rows on the f64
+ * matrix cores with the basis generated on the fly, one partial per chunk (the number of chunks depends on n and M alone), and
+ * one workgroup adds the partials in chunk order, factors A and finishes.  No atomics: repeated calls and the two forms give
+ * identical bits.  Returns 0, or k in 1..M when A is not positive definite at order k (out3 and grad all NaN). */
+GPMI_API int gpmi_lowrank_logml_grad(gpmi_ctx *ctx, const double *x, int n, const double *y, int M, double scale, double amp, double l,
+                            double sigma, double *out3, double *grad /* 3, nullable */);
+/* the same with device-resident x, y, out3, grad and d_info (1 int: the status; the device writes the NaNs), enqueued on the
+ * context's stream and not synchronised */
+GPMI_API int gpmi_lowrank_logml_grad_dev(gpmi_ctx *ctx, const double *dx, int n, const double *dy, int M, double scale, double amp,
+                                double l, double sigma, double *d_out3, double *d_grad /* 3, nullable */, int *d_info);
+
+/* The latent form the models evaluate per leapfrog step: q = Phi z (z: M), then a likelihood head of gpmi_latent_gp_lp_grad on
+ * q against the m replicate columns of Y (n x m, ldy):
+ *   GPMI_LIK_NORMAL (fit_approx_gp.stan:46-58), GPMI_LIK_BERNOULLI_LOGIT (westbrook.stan:51-61, multiple_players.stan); the
+ *   other families return GPMI_EARG.
+ *   out[0] = lik, out[1] = d lik / d sigma; q and qbar = d lik / d q (n each, both nullable); zbar (M) = Phi^T qbar;
+ *   grad[0] = d lik / d amp = qbar^T q / amp, grad[1] = d lik / d l = qbar^T (dPhi/dl z).
+ * Priors (z[1] ~ normal(0, 0.01) among them) and Jacobians stay with the caller.  Phi is regenerated for the second pass, not
+ * stored.  There is no factorisation, hence no positive-definiteness status: returns 0 or an error.  On this host-buffer form y
+ * outside {0, 1} is GPMI_EARG for the Bernoulli head.  Fixed-order sums: repeated calls and the two forms give identical bits. */
+GPMI_API int gpmi_lowrank_latent_lp_grad(gpmi_ctx *ctx, const double *x, int n, int M, double scale, double amp, double l,
+                                const double *z, int family, const double *Y, int m, int ldy, double sigma, double *out /* 2 */,
+                                double *q /* nullable */, double *qbar /* nullable */, double *zbar, double *grad /* 2 */);
+/* the same with device-resident x, z, Y, out, q, qbar, zbar, grad, enqueued on the context's stream and not synchronised */
+GPMI_API int gpmi_lowrank_latent_lp_grad_dev(gpmi_ctx *ctx, const double *dx, int n, int M, double scale, double amp, double l,
+                                    const double *dz, int family, const double *dY, int m, int ldy, double sigma,
+                                    double *d_out /* 2 */, double *dq /* nullable */, double *dqbar /* nullable */,
+                                    double *dzbar, double *d_grad /* 2 */);
+
 /* ---- diagnostics (tests / bench) -------------------------------------- */
 
 /* Elapsed ms of the most recent evaluation's stages, measured with HIP events

@@ -137,6 +137,13 @@ gp_log_marginal <- function(X, y, alpha, rho, sigma, jitter = 0)
 gp_log_marginal_grad <- function(X, y, alpha, rho, sigma, jitter = 0)
   .Call("gpmi_R_logml_grad", as.matrix(X), as.double(y), alpha, as.double(rho), sigma, jitter)
 
+# approx_L(M, scale, x, sigma, l) of models/westbrook.stan:2-30 -- the Hermite-eigenfunction basis.  The name approx_L is taken
+# above by the interpolated factor of models/approx_gp.stan, so the low-rank one is hermite_approx_L here.
+hermite_approx_L <- function(M, scale, x, sigma, l) .Call("gpmi_R_hermite_basis", as.integer(M), scale, as.double(x), sigma, l)
+# log marginal likelihood of y ~ N(0, L L' + sigma^2 I), L = hermite_approx_L(M, scale, x, amp, l), and its gradient in (amp, l, sigma)
+lowrank_logml_grad <- function(x, y, M, scale, amp, l, sigma)
+  .Call("gpmi_R_lowrank_logml_grad", as.double(x), as.double(y), as.integer(M), scale, amp, l, sigma)
+
 # value, gradient and the exact Hessian in c(alpha, rho.., sigma): list(value, grad, hess).  At the optimum of optim(),
 # sqrt(diag(solve(-fit$hess))) are the standard errors of the fitted hyper-parameters -- what optim(..., hessian = TRUE) gets
 # from 2 (2 + length(rho)) gradient calls to about half the digits.  One length-scale for any ncol(X), or one per column up to 8

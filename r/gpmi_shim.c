@@ -381,6 +381,39 @@ SEXP gpmi_R_logml_grad(SEXP X, SEXP y, SEXP alpha, SEXP ell, SEXP sigma, SEXP ji
     return out;
 }
 
+/* approx_L(M, scale, x, sigma, l) of models/westbrook.stan:2-30 (and bH of spectral_test.R:6-27): the n x M Hermite-eigenfunction
+ * basis with Phi Phi' -> sigma^2 exp(-(x_i - x_j)^2 / (2 l^2)); `sigma` is the models' amplitude argument (gpmi.h: amp) */
+SEXP gpmi_R_hermite_basis(SEXP M, SEXP scale, SEXP x, SEXP amp, SEXP l)
+{
+    int n = Rf_length(x), m = Rf_asInteger(M);
+    need(is_real(x), "x must be double");
+    need(n >= 1 && m >= 1 && m <= GPMI_LR_MMAX, "need length(x) >= 1 and M in 1..128");
+    SEXP Phi = PROTECT(Rf_allocMatrix(REALSXP, n, m));
+    int rc = gpmi_hermite_basis(ctx(), REAL(x), n, m, Rf_asReal(scale), Rf_asReal(amp), Rf_asReal(l), REAL(Phi), n, NULL, 0);
+    UNPROTECT(1);
+    check(rc);
+    return Phi;
+}
+
+/* list(value = c(logml, 1/2 log|Sigma|, y' Sigma^-1 y), grad = c(d/damp, d/dl, d/dsigma)) of y ~ N(0, Phi Phi' + sigma^2 I) with
+ * Phi the basis above (gpmi_lowrank_logml_grad) */
+SEXP gpmi_R_lowrank_logml_grad(SEXP x, SEXP y, SEXP M, SEXP scale, SEXP amp, SEXP l, SEXP sigma)
+{
+    int n = Rf_length(x), m = Rf_asInteger(M);
+    need(is_real(x) && is_real(y), "x and y must be double");
+    need(Rf_length(y) == n, "length(y) must equal length(x)");
+    SEXP val = PROTECT(Rf_allocVector(REALSXP, 3)), g = PROTECT(Rf_allocVector(REALSXP, 3));
+    int rc = gpmi_lowrank_logml_grad(ctx(), REAL(x), n, REAL(y), m, Rf_asReal(scale), Rf_asReal(amp), Rf_asReal(l), Rf_asReal(sigma),
+                                     REAL(val), REAL(g));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2)), names = PROTECT(Rf_allocVector(STRSXP, 2));
+    SET_VECTOR_ELT(out, 0, val); SET_VECTOR_ELT(out, 1, g);
+    SET_STRING_ELT(names, 0, Rf_mkChar("value")); SET_STRING_ELT(names, 1, Rf_mkChar("grad"));
+    Rf_setAttrib(out, R_NamesSymbol, names);
+    UNPROTECT(4);
+    check(rc);
+    return out;
+}
+
 /* exact leave-one-out cross-validation (gpmi_logml_loo): list(value = c(logml, sum log L_ii, z'z), loo = sum(lpd), mu, var, lpd
  * (length n: mean, variance of the observation and log density of y_i given the others), grad = d loo / d(alpha, ell.., sigma)
  * or NULL when want_grad is 0) */
