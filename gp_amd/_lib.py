@@ -88,7 +88,7 @@ def _share_hip_runtime_with_torch():
 
 def load():
     """Load libgpmi.so; loud failure when it has not been built.  GPMI_USE_PROBES=1 (tools/ only)
-    loads the probe build instead: same library plus the A/B kernels and gpmi_probe_* entry points."""
+    loads the probe build instead: same library plus the instruments and gpmi_probe_* entry points."""
     global _lib
     if _lib is not None:
         return _lib

@@ -14,7 +14,6 @@
 // Kernels
 //   k_potrf_diag4 one workgroup: factor a <=128x128 diagonal block, emit its
 //                 factors packed in fragment order (Fpack) for the panel solve
-//                 (k_potrf_diag: the 5-wave form of round 1, kept as an option)
 //   k_trsm_panel  rows below the block: X = A21 L11^-T by blocked substitution,
 //                 each wave owns 16 rows and chains MFMAs through registers
 //   k_gemm_nt     C -= A B^T / C = A B^T, 128x128 tiles, LDS-staged with
@@ -23,132 +22,12 @@
 // The device functions behind these kernels (potrf_diag4_body, trsm_panel_body, gemm_tile, gemm_quad64) live in
 // chol_device.h: the one-workgroup kernels of small_kernels.hip inline them too.  This file keeps the blocked kernels,
 // the triangular helpers (k_trsv_wave, k_trmv_*, k_logml_partial / finalize, k_get_row, k_pack_factors, ...), the
-// probe-only A/B kernels, gpmi_tuning_defaults and the panel scheduler.
+// probe build's instruments, gpmi_tuning_defaults and the panel scheduler.
 // Reference: Stan cholesky_decompose (models/fit_hyperparameters.stan:25),
 // multi_normal_cholesky (:31), L*z (models/exact_gp.stan:25).
 #include "chol_device.h"
 
 namespace {
-
-#ifdef GPMI_PROBES  // the 5-wave / 3-barrier diagonal-block kernel of round 1 (diag_waves = 5): A/B material only
-// ---------------------------------------------------------------------------
-// Diagonal block (<= 128 x 128).  One workgroup of 5 waves:
-//   waves 0-3 "tile waves": wave w owns block-rows w and 7-w (9 register tiles, balanced),
-//             held transposed in the MFMA accumulator layout T[jb][reg] = A[row][jb*16+col];
-//             fully unrolled over the 8 block columns (compile-time tile indices);
-//   wave 4    "factor wave": runs the sequential 16x16 factor + inverse (factor16) for every
-//             block column out of LDS; it holds no tiles, so the register-hungry broadcast
-//             code exists once and never forces tile copies at control-flow joins.
-// Right-looking over the block columns; three workgroup barriers per column.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(320) void k_potrf_diag(double *__restrict__ A, size_t lda, int nb_act,
-                                                    double *__restrict__ Fpack, int *info, int col0)
-{
-    __shared__ double s_pub[2][8][256];
-    __shared__ double s_inv[8][256];  // L16^-1 of every block column (kept: written to Fpack at the end)
-    __shared__ double s_d16[16][17];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lr = lane & 15, lq = lane >> 4;
-    // No global store is issued inside the column loop: a __syncthreads() behind a store waits
-    // for its acknowledgement (~us).  The packed factors go out after the loop -- the -L tiles
-    // ARE the final tile registers, the inverses wait in LDS.
-
-    if (w == 4) {
-#pragma unroll 1
-        for (int kb = 0; kb < 8; ++kb) {
-            __syncthreads();  // B1: the owner's diagonal tile is in s_d16
-            const int bad = factor16(s_d16, s_inv[kb], lane);
-            if (bad && lane == 0) atomicCAS(info, 0, col0 + kb * 16 + bad);
-            __syncthreads();  // B2: L16 in s_d16, L16^-1 in s_inv
-            __syncthreads();  // B3: -X tiles published
-        }
-        return;
-    }
-
-    const int ra = w, rb = 7 - w;  // the two block-rows of this wave, ra < rb
-    d4 TA[8], TB[8];
-#define GPMI_LOAD_ROW(T, br)                                                                           \
-    _Pragma("unroll") for (int jb = 0; jb < 8; ++jb) {                                                 \
-        T[jb] = d4{0.0, 0.0, 0.0, 0.0};                                                                \
-        if (jb <= (br)) {                                                                              \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
-                const int col = jb * 16 + lq + 4 * i, row = (br) * 16 + lr;                            \
-                const int rr = row > col ? row : col, cc = row > col ? col : row;                      \
-                T[jb][i] = (rr < nb_act) ? A[(size_t)rr + (size_t)cc * lda] : (row == col ? 1.0 : 0.0); \
-            }                                                                                          \
-        }                                                                                              \
-    }
-    GPMI_LOAD_ROW(TA, ra)
-    GPMI_LOAD_ROW(TB, rb)
-
-#define GPMI_SOLVE_ROW(T, br, X)                                                                       \
-    if ((br) == kb) {                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) T[kb][i] = s_d16[lr][lq + 4 * i];                \
-    } else if ((br) > kb) {                                                                            \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                               \
-            X = mfma(s_inv[kb][kg * 64 + lane], T[kb][kg], X);                                         \
-        T[kb] = X;                                                                                     \
-        _Pragma("unroll") for (int kg = 0; kg < 4; ++kg) s_pub[kb & 1][br][kg * 64 + lane] = -X[kg];   \
-    }
-#define GPMI_UPDATE_ROW(T, br, X)                                                                      \
-    _Pragma("unroll") for (int jb = kb + 1; jb < 8; ++jb) {                                            \
-        if (jb <= (br)) {                                                                              \
-            _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                           \
-                T[jb] = mfma(s_pub[kb & 1][jb][kg * 64 + lane], X[kg], T[jb]);                         \
-        }                                                                                              \
-    }
-
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb) {
-        // (a) the owner hands its updated diagonal tile to the factor wave in matrix order
-        if (ra == kb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s_d16[lr][lq + 4 * i] = TA[kb][i];
-        } else if (rb == kb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s_d16[lr][lq + 4 * i] = TB[kb][i];
-        }
-        __syncthreads();  // B1
-        __syncthreads();  // B2: factor wave done
-        // (a3) the owner reloads L16 in tile layout; (b) rows below: X = Linv16 * T[kb], publish -X
-        d4 XA = d4{0.0, 0.0, 0.0, 0.0}, XB = XA;
-        GPMI_SOLVE_ROW(TA, ra, XA)
-        GPMI_SOLVE_ROW(TB, rb, XB)
-        __syncthreads();  // B3
-        // (c) trailing tiles of both block-rows: T[jb] -= L[jb][kb] * X_kb
-        if (ra > kb) { GPMI_UPDATE_ROW(TA, ra, XA) }
-        if (rb > kb) { GPMI_UPDATE_ROW(TB, rb, XB) }
-    }
-
-#define GPMI_STORE_ROW(T, br)                                                                          \
-    _Pragma("unroll") for (int jb = 0; jb < 8; ++jb) {                                                 \
-        if (jb <= (br)) {                                                                              \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
-                const int col = jb * 16 + lq + 4 * i, row = (br) * 16 + lr;                            \
-                if (row < nb_act && col <= row) A[(size_t)row + (size_t)col * lda] = T[jb][i];         \
-            }                                                                                          \
-            if (jb < (br)) {                                                                           \
-                _Pragma("unroll") for (int kg = 0; kg < 4; ++kg)                                       \
-                    Fpack[(size_t)((br) * ((br) - 1) / 2 + jb) * 256 + kg * 64 + lane] = -T[jb][kg];   \
-            }                                                                                          \
-        }                                                                                              \
-    }
-    GPMI_STORE_ROW(TA, ra)
-    GPMI_STORE_ROW(TB, rb)
-    // the two inverses this wave's block-rows belong to
-#pragma unroll
-    for (int kg = 0; kg < 4; ++kg) {
-        Fpack[(size_t)fp_inv(ra) * 256 + kg * 64 + lane] = s_inv[ra][kg * 64 + lane];
-        Fpack[(size_t)fp_inv(rb) * 256 + kg * 64 + lane] = s_inv[rb][kg * 64 + lane];
-    }
-#undef GPMI_LOAD_ROW
-#undef GPMI_SOLVE_ROW
-#undef GPMI_UPDATE_ROW
-#undef GPMI_STORE_ROW
-}
-
-#endif  // GPMI_PROBES
 
 __global__ __launch_bounds__(256, 2) void k_potrf_diag4(double *__restrict__ A, size_t lda, int nb_act,
                                                      double *__restrict__ Fpack, int *info, int col0)
@@ -178,16 +57,9 @@ __global__ __launch_bounds__(256) void k_trsm_panel(double *__restrict__ Acol, s
         trsm_panel_body<false>(s_F, Acol, lda, r, r < M, nb_act);
 }
 
-// SYRK tile order.  Workgroups are dealt round-robin to the 8 XCDs (observed dispatch
-// behaviour; performance only), so block b runs on XCD-group b % 8 as that group's (b / 8)-th
-// workgroup.  Each group walks 8x8 SUPER-TILES of the lower triangle: the 64 tiles that are
-// resident on one XCD at a time then share 8 row-blocks and 8 column-blocks of the panel
-// through that XCD's L2 (16 blocks per 64 tiles instead of ~65 in row-major order), which
-// takes the operand stream off HBM / Infinity Cache.  Tiles of a super-tile that fall outside
-// the triangle exit at once.
-// TN < T: the lower TRAPEZOID of a T x TN tile grid (a block column of the trailing matrix, the
-// first part of a look-ahead update): the TN x TN triangle first, then the rows below it.
-constexpr int ST = 8;
+// SYRK tile order 0: block b is tile b of the row-major walk of the lower triangle.
+// TN < T: the lower TRAPEZOID of a T x TN tile grid (a trailing matrix with more rows than columns,
+// e.g. the augmented row): the TN x TN triangle first, then the rows below it.
 __device__ __forceinline__ bool syrk_tile(int b, int T, int TN, int order, int &ti, int &tj)
 {
     if (order == 0) {  // plain row-major walk of the lower triangle / trapezoid
@@ -205,30 +77,9 @@ __device__ __forceinline__ bool syrk_tile(int b, int T, int TN, int order, int &
         tj = b - i * (i + 1) / 2;
         return ti < T;
     }
-#ifndef GPMI_PROBES
-    return false;  // the XCD-grouped super-tile walk (measured slower in place) exists in the probe build only
-#else
-    const int xcd = b & 7, q = b >> 3;
-    const int s = (q / (ST * ST)) * 8 + xcd;       // super-tile index, row-major over the triangle
-    const int local = q % (ST * ST);
-    const int nst = (T + ST - 1) / ST;
-    if (s >= nst * (nst + 1) / 2) return false;
-    int I = (int)((sqrt(8.0 * (double)s + 1.0) - 1.0) * 0.5);
-    while ((I + 1) * (I + 2) / 2 <= s) ++I;
-    while (I * (I + 1) / 2 > s) --I;
-    const int J = s - I * (I + 1) / 2;
-    ti = I * ST + (local % ST);
-    tj = J * ST + (local / ST);
-    return ti < T && tj <= ti;
-#endif
+    return false;  // walk 2 has its own enumeration (syrk_tile_bands); no other walk exists
 }
-__host__ inline int syrk_grid(int T, int TN, int order)
-{
-    if (order == 0) return TN * (TN + 1) / 2 + (T - TN) * TN;
-    const int nst = (T + ST - 1) / ST;
-    const int ns = nst * (nst + 1) / 2;
-    return ((ns + 7) / 8) * 8 * ST * ST;
-}
+__host__ inline int syrk_grid(int T, int TN) { return TN * (TN + 1) / 2 + (T - TN) * TN; }  // tiles of the triangle / trapezoid
 
 // XCD-partitioned band walk (order 2) of the lower triangle / trapezoid, WITHOUT a padded grid: the valid tiles are
 // enumerated band by band (8 tile rows), inside a band column by column -- 64 consecutive tiles are an 8 x 8 patch --
@@ -580,350 +431,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const double *__restrict__ A
     }
 }
 
-#ifdef GPMI_PROBES  // A/B kernels of tools/ (libgpmi_probes.so); the product library ships without them
-// ---------------------------------------------------------------------------
-// GEMM NT v2: same 128x128 tile and LDS image, 8 waves (2 m x 4 n, 64 x 32 outputs per
-// wave = 8 accumulator tiles) so that 64 VGPRs are free to PREFETCH the wave's share of the
-// C tile while the main loop runs: the read-modify-write epilogue of v1 (4 dependent
-// load->store round trips per tile, ~40 % of a K=256 tile's time) becomes subtract + store.
-// Waits are counted by hand: the C loads are issued in four 8-load pieces AFTER the LDS-DMA
-// of the next stage, so `s_waitcnt vmcnt(8)` retires the stage while the piece stays in
-// flight across the raw s_barrier (hipcc's __syncthreads would drain everything).
-// Register budget <= 168 (3 waves/SIMD): one workgroup per CU leaves a third wave slot per
-// SIMD and 87 KB of LDS for the panel kernels of the look-ahead stream.
-// ---------------------------------------------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(512, 2) void k_gemm8(const double *__restrict__ A, size_t lda,
-                                                  const double *__restrict__ B, size_t ldb,
-                                                  double *__restrict__ C, size_t ldc, int M, int N, int K, int order)
-{
-    __shared__ __attribute__((aligned(16))) double smem[2][2][GK][GP];
-    int ti, tj;
-    if (MODE == 1) {
-        const int Tr = (M + GT - 1) / GT, Tc = (N + GT - 1) / GT;  // M = N + 1 (augmented row): a trapezoid
-        if (!syrk_tile(blockIdx.x, Tr, Tc < Tr ? Tc : Tr, order, ti, tj)) return;
-    } else {
-        ti = blockIdx.x;
-        tj = blockIdx.y;
-    }
-    const int m0 = ti * GT, n0 = tj * GT;
-    if (MODE == 1 && n0 >= N) return;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lr = lane & 15, lq = lane >> 4;
-    const int wm = w & 1, wn = w >> 1;
-    // a tile wholly inside the matrix takes the branch-free path; for SYRK the diagonal tiles
-    // are computed in full (their strictly-upper outputs land in the unused upper triangle)
-    const bool interior = (m0 + GT <= M) && (n0 + GT <= N);
-
-    // staging: waves 0-3 stream the A tile (m index), waves 4-7 the B tile (n index); 4 k-rows each
-    const int op = w >> 2;
-    const double *gsrc = (op ? B + n0 : A + m0) + 2 * lane;
-    const size_t gld = op ? ldb : lda;
-    const int krow0 = (w & 3) * 4;
-
-    d4 acc[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-
-    const int nk = (K + GK - 1) / GK;
-    auto issue = [&](int stage, int k0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int kr = krow0 + q;
-            int kc = k0 + kr;
-            kc = kc < K ? kc : K - 1;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(gsrc + (size_t)kc * gld),
-                (__attribute__((address_space(3))) void *)&smem[stage][op][kr][0], 16, 0, 0);
-        }
-    };
-
-    // this lane's corner of the C tile; element (tn, tm, i) = cbase[tm*16 + (tn*16 + 4 i) * ldc]
-    double *const cbase = C + (size_t)(m0 + wm * 64 + lr) + (size_t)(n0 + wn * 32 + lq) * ldc;
-    double cv[2][4][4];
-    auto prefetch = [&](auto pc) {  // piece P: tn = P>>1, tm in {2(P&1), 2(P&1)+1}: 8 loads
-        constexpr int P = decltype(pc)::value;
-        constexpr int tn = P >> 1;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                constexpr int dummy = 0;
-                (void)dummy;
-                const int tm = 2 * (P & 1) + h;
-                cv[tn][tm][i] = cbase[tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc];
-            }
-    };
-    auto compute = [&](int st, int klim) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int kr = kk * 4 + lq;
-            const bool kv = kr < klim;
-            double af[2], bf[4];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const double a = smem[st][1][kr][wn * 32 + t * 16 + lr];
-                af[t] = kv ? a : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const double b = smem[st][0][kr][wm * 64 + t * 16 + lr];
-                bf[t] = kv ? b : 0.0;
-            }
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(af[tn], bf[tm], acc[tn][tm]);
-        }
-    };
-    // one k-step: retire stage kt (leaving WAITN younger loads in flight), barrier, start the
-    // DMA of stage kt+1, optionally issue C-prefetch piece P behind it, multiply stage kt
-    auto step = [&](int kt, auto wn_, auto pc) {
-        constexpr int WAITN = decltype(wn_)::value;
-        constexpr int P = decltype(pc)::value;
-        // lgkmcnt(0): every LDS read of the stage about to be overwritten has returned before
-        // any wave can start the DMA into it (WAR across the barrier)
-        if constexpr (WAITN == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + 1 < nk) issue((kt + 1) & 1, (kt + 1) * GK);
-        if constexpr (P >= 0) prefetch(ic<P>{});
-        compute(kt & 1, K - kt * GK);
-    };
-
-    issue(0, 0);
-    const bool pf = (MODE != 2) && interior;
-    int kt = 0;
-    if (pf && nk >= 5) {
-        step(0, ic<0>{}, ic<0>{});
-        step(1, ic<8>{}, ic<1>{});
-        step(2, ic<8>{}, ic<2>{});
-        step(3, ic<8>{}, ic<3>{});
-        step(4, ic<8>{}, ic<-1>{});
-        kt = 5;
-    } else if (pf) {
-        prefetch(ic<0>{}); prefetch(ic<1>{}); prefetch(ic<2>{}); prefetch(ic<3>{});
-    }
-#pragma unroll 1
-    for (; kt < nk; ++kt) step(kt, ic<0>{}, ic<-1>{});
-
-    if (interior) {
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    double *p = cbase + tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc;
-                    *p = (MODE == 2) ? acc[tn][tm][i] : cv[tn][tm][i] - acc[tn][tm][i];
-                }
-    } else {
-        // edge tile: loads from clamped (always valid) addresses, guarded stores
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn) {
-            double ce[4][4];
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    int n = n0 + wn * 32 + tn * 16 + lq + 4 * i, m = m0 + wm * 64 + tm * 16 + lr;
-                    n = n < N ? n : N - 1;
-                    m = m < M ? m : M - 1;
-                    if (MODE != 2) ce[tm][i] = C[(size_t)m + (size_t)n * ldc];
-                }
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int n = n0 + wn * 32 + tn * 16 + lq + 4 * i, m = m0 + wm * 64 + tm * 16 + lr;
-                    if (m < M && n < N && (MODE != 1 || n <= m))
-                        C[(size_t)m + (size_t)n * ldc] = (MODE == 2) ? acc[tn][tm][i] : ce[tm][i] - acc[tn][tm][i];
-                }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// GEMM NT v3: v2's wave layout and C prefetch with a 3-buffer LDS ring, DMA issued TWO
-// k-steps ahead.  A stage has two full k-steps (~8k cycles) to land, so the counted wait at
-// the top of a step does not stall on HBM / Infinity-Cache latency.  Issue order per step:
-// [DMA stage kt+2] [C piece kt]; the wait lets everything younger than stage kt stay in
-// flight (4 DMA + up to two 8-load pieces).  One workgroup per CU (110 KB LDS).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void wait_vm_lgkm0(int n)
-{
-    // immediates only; n is wave-uniform.  lgkmcnt(0): the buffer the next DMA overwrites was
-    // read in the previous step -- those LDS reads must have returned before any wave passes
-    // the barrier and starts that DMA.
-    if (n >= 20) asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory");
-    else if (n >= 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-    else if (n >= 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-    else if (n >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-}
-
-template <int MODE>
-__global__ __launch_bounds__(512, 2) void k_gemm9(const double *__restrict__ A, size_t lda,
-                                                  const double *__restrict__ B, size_t ldb,
-                                                  double *__restrict__ C, size_t ldc, int M, int N, int K, int order)
-{
-    __shared__ __attribute__((aligned(16))) double smem[3][2][GK][GP];
-    int ti, tj;
-    if (MODE == 1) {
-        const int Tr = (M + GT - 1) / GT, Tc = (N + GT - 1) / GT;  // M = N + 1 (augmented row): a trapezoid
-        if (!syrk_tile(blockIdx.x, Tr, Tc < Tr ? Tc : Tr, order, ti, tj)) return;
-    } else {
-        ti = blockIdx.x;
-        tj = blockIdx.y;
-    }
-    const int m0 = ti * GT, n0 = tj * GT;
-    if (MODE == 1 && n0 >= N) return;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lr = lane & 15, lq = lane >> 4;
-    const int wm = w & 1, wn = w >> 1;
-    const bool interior = (m0 + GT <= M) && (n0 + GT <= N);
-
-    const int op = w >> 2;
-    const double *gsrc = (op ? B + n0 : A + m0) + 2 * lane;
-    const size_t gld = op ? ldb : lda;
-    const int krow0 = (w & 3) * 4;
-
-    d4 acc[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-
-    const int nk = (K + GK - 1) / GK;
-    auto issue = [&](int stage, int k0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int kr = krow0 + q;
-            int kc = k0 + kr;
-            kc = kc < K ? kc : K - 1;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(gsrc + (size_t)kc * gld),
-                (__attribute__((address_space(3))) void *)&smem[stage][op][kr][0], 16, 0, 0);
-        }
-    };
-
-    double *const cbase = C + (size_t)(m0 + wm * 64 + lr) + (size_t)(n0 + wn * 32 + lq) * ldc;
-    double cv[2][4][4];
-    auto prefetch = [&](auto pc) {
-        constexpr int P = decltype(pc)::value;
-        constexpr int tn = P >> 1;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int tm = 2 * (P & 1) + h;
-                cv[tn][tm][i] = cbase[tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc];
-            }
-    };
-    auto compute = [&](int st, int klim) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int kr = kk * 4 + lq;
-            const bool kv = kr < klim;
-            double af[2], bf[4];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const double a = smem[st][1][kr][wn * 32 + t * 16 + lr];
-                af[t] = kv ? a : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const double b = smem[st][0][kr][wm * 64 + t * 16 + lr];
-                bf[t] = kv ? b : 0.0;
-            }
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma(af[tn], bf[tm], acc[tn][tm]);
-        }
-    };
-
-    const bool pf = (MODE != 2) && interior;
-    int st = 0, st2 = 2;  // buffer of stage kt, buffer of stage kt+2
-    // one k-step with compile-time wait count and prefetch piece (straight-line code: hipcc
-    // then keeps the prefetched C values in place instead of copying them at branch joins)
-    auto step = [&](int kt, auto wn_, auto pc) {
-        constexpr int WAITN = decltype(wn_)::value;
-        constexpr int P = decltype(pc)::value;
-        wait_vm_lgkm0(WAITN);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + 2 < nk) issue(st2, (kt + 2) * GK);
-        if constexpr (P >= 0) prefetch(ic<P>{});
-        compute(st, K - kt * GK);
-        st = (st == 2) ? 0 : st + 1;
-        st2 = (st2 == 2) ? 0 : st2 + 1;
-    };
-    issue(0, 0);
-    if (nk > 1) issue(1, GK);
-    int kt = 0;
-    if (pf && nk >= 8) {
-        // younger than stage kt and allowed to stay in flight: DMA kt+1 (4) + the C pieces of
-        // steps kt-1 and kt-2 (8 each)
-        step(0, ic<4>{}, ic<0>{});
-        step(1, ic<12>{}, ic<1>{});
-        step(2, ic<20>{}, ic<2>{});
-        step(3, ic<20>{}, ic<3>{});
-        step(4, ic<20>{}, ic<-1>{});
-        step(5, ic<12>{}, ic<-1>{});
-        kt = 6;
-    } else if (pf) {
-        prefetch(ic<0>{}); prefetch(ic<1>{}); prefetch(ic<2>{}); prefetch(ic<3>{});
-        step(0, ic<0>{}, ic<-1>{});  // drains the C loads too (short-K path)
-        kt = 1;
-    }
-#pragma unroll 1
-    for (; kt + 1 < nk; ++kt) step(kt, ic<4>{}, ic<-1>{});
-    if (kt < nk) step(kt, ic<0>{}, ic<-1>{});
-
-    if (interior) {
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    double *p = cbase + tm * 16 + (size_t)(tn * 16 + 4 * i) * ldc;
-                    *p = (MODE == 2) ? acc[tn][tm][i] : cv[tn][tm][i] - acc[tn][tm][i];
-                }
-    } else {
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn) {
-            double ce[4][4];
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    int n = n0 + wn * 32 + tn * 16 + lq + 4 * i, m = m0 + wm * 64 + tm * 16 + lr;
-                    n = n < N ? n : N - 1;
-                    m = m < M ? m : M - 1;
-                    if (MODE != 2) ce[tm][i] = C[(size_t)m + (size_t)n * ldc];
-                }
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int n = n0 + wn * 32 + tn * 16 + lq + 4 * i, m = m0 + wm * 64 + tm * 16 + lr;
-                    if (m < M && n < N && (MODE != 1 || n <= m))
-                        C[(size_t)m + (size_t)n * ldc] = (MODE == 2) ? acc[tn][tm][i] : ce[tm][i] - acc[tn][tm][i];
-                }
-        }
-    }
-}
-
-#endif  // GPMI_PROBES
-
 // Packed factors (Fpack) of an ALREADY factored diagonal block: -L tiles in fragment
 // order and the inverse of every 16x16 diagonal tile.  Used by solves against a given L.
 __global__ __launch_bounds__(512) void k_pack_factors(const double *__restrict__ L11, size_t ldl,
@@ -1242,7 +749,6 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->syrk_order = 2;
     t->stagger = (2 << 16) | 4;
     t->fuse_diag = 15;
-    t->diag_waves = 4;
     t->nb_adapt = 1;
     t->nb_thr[0] = 8192;
     t->nb_thr[1] = 4608;
@@ -1251,8 +757,6 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->ksplit_max = 100;
     t->block_recursive = 1;
     t->se_nt = 1;
-    t->gemm_variant = 3;
-    t->rect_auto = 0;
     t->small_n = 256;
     t->small_n1 = 128;
     t->small_m = 160;
@@ -1281,29 +785,6 @@ void launch_gemm_nt(const gpmi_ctx *c, hipStream_t s, const double *A, size_t ld
 {
     if (M <= 0 || N <= 0 || K <= 0) return;
     dim3 grid((M + GT - 1) / GT, (N + GT - 1) / GT);
-#ifdef GPMI_PROBES
-    // Launches with fewer tiles than workgroup slots are latency-bound (one tile per CU, every
-    // k-step exposes the DMA latency): the 3-buffer-ring kernel (DMA two steps ahead, C tile
-    // prefetched) has the shorter per-tile time there; the 2-workgroup-per-CU kernel wins once
-    // several rounds of tiles keep each CU's pair of workgroups busy.
-    const bool few_tiles = c->tune.rect_auto && (int)(grid.x * grid.y) <= 384;
-    if (c->tune.gemm_variant == 2 || (c->tune.gemm_variant == 3 && few_tiles)) {
-        if (accumulate_minus)
-            hipLaunchKernelGGL(k_gemm9<0>, grid, 512, 0, s, A, lda, B, ldb, C, ldc, M, N, K, 0);
-        else
-            hipLaunchKernelGGL(k_gemm9<2>, grid, 512, 0, s, A, lda, B, ldb, C, ldc, M, N, K, 0);
-        return;
-    }
-    if (c->tune.gemm_variant == 1) {
-        if (accumulate_minus)
-            hipLaunchKernelGGL(k_gemm8<0>, grid, 512, 0, s, A, lda, B, ldb, C, ldc, M, N, K, 0);
-        else
-            hipLaunchKernelGGL(k_gemm8<2>, grid, 512, 0, s, A, lda, B, ldb, C, ldc, M, N, K, 0);
-        return;
-    }
-#else
-    (void)c;
-#endif
     if (accumulate_minus)
         hipLaunchKernelGGL(k_gemm_nt<0>, grid, 256, 0, s, A, lda, B, ldb, C, ldc, M, N, K, 0, 0, FuseDiag{}, KSplit{});
     else
@@ -1316,7 +797,7 @@ void launch_gemm_tri_lower(hipStream_t s, const double *A, size_t lda, const dou
 {
     if (n <= 0) return;
     const int T = (n + GT - 1) / GT;
-    hipLaunchKernelGGL(k_gemm_nt<2>, dim3(syrk_grid(T, T, 0)), 256, 0, s, A, lda, B, ldb, C, ldc, n, n, n, 0x400, 0, FuseDiag{},
+    hipLaunchKernelGGL(k_gemm_nt<2>, dim3(syrk_grid(T, T)), 256, 0, s, A, lda, B, ldb, C, ldc, n, n, n, 0x400, 0, FuseDiag{},
                        KSplit{});
 }
 
@@ -1335,7 +816,7 @@ void launch_gemm_tri_lower(hipStream_t s, const double *A, size_t lda, const dou
 static bool launch_gemm_nt_fused(const gpmi_ctx *c, hipStream_t s, const double *A, size_t lda, const double *B, size_t ldb, double *C,
                                  size_t ldc, int M, int N, int K, const FuseDiag &fd)
 {
-    if (!(c->tune.fuse_diag & 1) || (c->tune.gemm_variant != 3 && c->tune.gemm_variant != 0) || M <= 0 || N <= 0 || K <= 0) return false;
+    if (!(c->tune.fuse_diag & 1) || M <= 0 || N <= 0 || K <= 0) return false;
     dim3 grid((M + GT - 1) / GT, (N + GT - 1) / GT);
     if ((c->tune.fuse_diag & 4) && fd.ctr && M >= GT && N >= GT && K % 64 == 0) {  // tile (0, 0) interior: sub-tiled
         hipLaunchKernelGGL(k_gemm_nt<0>, dim3(grid.x * grid.y + SUBWG - 1), 256, 0, s, A, lda, B, ldb, C, ldc, M, N, K, 0x200, 0, fd, KSplit{});
@@ -1345,8 +826,6 @@ static bool launch_gemm_nt_fused(const gpmi_ctx *c, hipStream_t s, const double 
     return true;
 }
 
-// tune.diag_waves  4 (default): k_potrf_diag4 (3 tile waves + factor wave, two barriers per block column; fits beside a
-//                  resident SYRK workgroup), 5: k_potrf_diag (4 tile waves + factor wave, three barriers)
 // tune.nb_adapt    1 (default): the auto outer-block width is re-chosen per block from the order of the matrix still to
 //                  update (tune.nb_thr: >= 8192 -> 1024 columns, >= 4608 -> 512, >= 3584 -> 256, below -> 128): the last
 //                  blocks of a large matrix are a small matrix.  Pays since single-round trailing updates carry the next
@@ -1364,42 +843,26 @@ static bool launch_syrk_lower(const gpmi_ctx *c, hipStream_t s, const double *P,
 {
     if (tri && M > 0 && N > 0 && K > 0) {  // upper-triangular panel: plain kernel, row-major tiles, zero K-range skipped
         const int T = (M + GT - 1) / GT;
-        hipLaunchKernelGGL(k_gemm_nt<1>, dim3(syrk_grid(T, T, 0)), 256, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, 0x100, 0,
+        hipLaunchKernelGGL(k_gemm_nt<1>, dim3(syrk_grid(T, T)), 256, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, 0x100, 0,
                            FuseDiag{}, KSplit{});
         return false;
     }
     if (M <= 0 || N <= 0 || K <= 0) return false;
     const int T = (M + GT - 1) / GT;
-    // N < M: lower trapezoid (block column of a look-ahead update), row-major order only
+    // N < M: lower trapezoid
     const int TNf = (N + GT - 1) / GT, TN = TNf < T ? TNf : T;
     const int slots = 2 * (ncu > 0 ? ncu : 256);
     // tile walk: 0 row-major; 2 XCD-partitioned bands (launches of more than one round of tiles: that is where the
-    // operand re-reads that miss the XCD L2s come from); 1 (probe build) the padded 8 x 8 super-tile grid of round 1
+    // operand re-reads that miss the XCD L2s come from).
     // Walk 2 is the default for an evaluation that has the chip to itself (N = 16384: L2 hit rate 53 -> 79 %, L2-miss
     // traffic 1.27 -> 0.65 GB per launch, 27.31 -> 27.07 ms); under the grid lanes, where four launches share every
     // XCD, its static per-XCD partition loses 1.6 % (23.09 -> 23.45 ms per point) and the row-major walk stays.
-    int syrk_order = (c->tune.syrk_order == 2 && !c->lanes_active && syrk_grid(T, TN, 0) > slots) ? 2 : 0;
-#ifdef GPMI_PROBES
-    if (c->tune.syrk_order == 1 && TN == T) syrk_order = 1;
-#endif
-    const int ntiles = syrk_grid(T, TN, syrk_order == 1 ? 1 : 0);
+    const int syrk_order = (c->tune.syrk_order == 2 && !c->lanes_active && syrk_grid(T, TN) > slots) ? 2 : 0;
+    const int ntiles = syrk_grid(T, TN);
     const int stg = ntiles >= 1024 ? c->tune.stagger : 0;  // only when every CU holds two workgroups for many rounds
-#ifdef GPMI_PROBES
-    if (c->tune.gemm_variant == 2) {
-        hipLaunchKernelGGL(k_gemm9<1>, dim3(ntiles), 512, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, syrk_order);
-        return false;
-    }
-    if (c->tune.gemm_variant == 1) {
-        hipLaunchKernelGGL(k_gemm8<1>, dim3(ntiles), 512, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, syrk_order);
-        return false;
-    }
-#else
-    (void)ctr;
-#endif
-    // tile (0, 0) is block 0 only in the row-major order
     // only in launches of more than one round of tiles, where workgroup 0's extra 27 us do not
     // lengthen the kernel
-    bool fuse = fd && fd->Fp && (c->tune.fuse_diag & 2) && syrk_order != 1 && ntiles > slots;  // tile (0, 0) is block 0 in walks 0 and 2
+    bool fuse = fd && fd->Fp && (c->tune.fuse_diag & 2) && ntiles > slots;  // tile (0, 0) is block 0 in walks 0 and 2
     // Single-round launches: the next diagonal block rides along as well, sub-tiled like in the in-block products
     // (fused_subtiles_and_diag) -- its 36 sub-tiles and the block's factorisation (~6 + 21 us) run beside the other
     // tiles instead of in a kernel of their own behind the launch (tune.fuse_diag bit 3).
@@ -1477,14 +940,8 @@ static void panel_one(gpmi_ctx *c, double *W, size_t ld, int *d_info, double *Fp
                       int row_lo, int row_hi, bool with_diag, hipStream_t s)
 {
     double *Fp = fpack_slot(c, Fpack_all, ko, k);
-    if (with_diag) {
-#ifdef GPMI_PROBES
-        if (c->tune.diag_waves == 5)
-            hipLaunchKernelGGL(k_potrf_diag, dim3(1), 320, 0, s, W + (size_t)k + (size_t)k * ld, ld, kb, Fp, d_info, k);
-        else
-#endif
-            hipLaunchKernelGGL(k_potrf_diag4, dim3(1), 256, 0, s, W + (size_t)k + (size_t)k * ld, ld, kb, Fp, d_info, k);
-    }
+    if (with_diag)
+        hipLaunchKernelGGL(k_potrf_diag4, dim3(1), 256, 0, s, W + (size_t)k + (size_t)k * ld, ld, kb, Fp, d_info, k);
     const int r0 = k + kb;
     const int rlo = r0 > row_lo ? r0 : row_lo;
     if (rlo >= row_hi) return;
@@ -1525,7 +982,7 @@ static void panel_rec(gpmi_ctx *c, double *W, size_t ld, int *d_info, double *Fp
 // panel.  with_diag: also factor the 128 x 128 diagonal blocks (their factors go to the block's
 // Fpack slots); without it the slots written by an earlier call are used.
 //   (0, M, true)   : the whole panel phase, full height
-//   (0, ke, true)  : only the NBO x NBO diagonal block -- the latency chain of the look-ahead
+//   (0, ke, true)  : only the NBO x NBO diagonal block -- the latency chain
 //   (ke, M, false) : the rows below it -- wide, throughput-bound kernels
 // tune.block_recursive == 0 keeps the earlier three fixed levels: 128-column panels grouped into
 // middle blocks of NBM columns; a panel's K = 128 update reaches only to the end of its middle
@@ -1577,129 +1034,36 @@ int launch_potrf_partial(gpmi_ctx *c, double *W, size_t ld, int M, int ncol, int
         return cols >= c->tune.nb_thr[0] ? 1024 : (cols >= c->tune.nb_thr[1] ? 512 : (cols >= c->tune.nb_thr[2] ? 256 : 128));
     };
     const int NBO = c->nb_outer > 0 ? c->nb_outer : nbo_for(ncol);
-#ifdef GPMI_PROBES
-    // (probe build) two-stream look-ahead over outer blocks: needs at least three outer blocks to pay, a second
-    // stream, and the block's packed factors in the ring (or all kept); measured not to pay, DESIGN section 4
-    bool la = c->lookahead > 0 && nfac >= 3 * NBO && (Fpack_all || NBO / GPMI_NB <= GPMI_FPACK_SLOTS);
-    if (la) {
-        int rc = gpmi_lookahead_streams(c);
-        if (rc) return rc;
-        la = c->nq >= 2 || c->pstream;
-    }
-    if (!la)
-#endif
-    {
-        hipStream_t s = c->stream;
-        // auto width follows the order of the matrix still to update (tune.nb_adapt): the last blocks of a
-        // large matrix are a small matrix, whose few trailing tiles do not fill the chip at K = 1024
-        bool diag_done = false;
-        for (int ko = 0, nbo = NBO; ko < nfac; ko += nbo) {
-            nbo = (c->nb_outer > 0 || !c->tune.nb_adapt) ? NBO : nbo_for(ncol - ko);
-            const int ke = (ko + nbo < nfac) ? ko + nbo : nfac;
-            kt_begin(c, 2, s);
-            panel_rows(c, W, ld, d_info, Fpack_all, ko, ke, nbo, 0, M, true, s, diag_done);
-            {   // algorithmic flops of the panel phase: diagonal block w^3/3 + rows below (m - w) w^2
-                const double w = (double)(ke - ko), m = (double)(M - ko);
-                kt_end(c, 2, w * w * (m - w) + w * w * w / 3.0, s);
-            }
-            diag_done = false;
-            if (ke >= M || ke >= ncol) continue;
-            const double mt = (double)(ncol - ke), extra = (double)(M - ncol);
-            // the first diagonal block of the next outer block rides in this trailing update
-            FuseDiag fd{};
-            if (ke < nfac)
-                fd = FuseDiag{fpack_slot(c, Fpack_all, ke, ke), d_info, ke, (nfac - ke < GPMI_NB) ? nfac - ke : GPMI_NB, nullptr};
-            kt_begin(c, 1, s);
-            diag_done = launch_syrk_lower(c, s, W + (size_t)ke + (size_t)ko * ld, ld, W + (size_t)ke + (size_t)ke * ld, ld,
-                                          M - ke, ncol - ke, ke - ko, c->d_ctr, c->ncu, 0, &fd);
-            // algorithmic flops: lower triangle (incl. diagonal) of the square part + extra rows
-            {   // flag: more than one round of tiles (throughput-bound launch)
-                const int T = (M - ke + GT - 1) / GT, TNf = (ncol - ke + GT - 1) / GT, TN = TNf < T ? TNf : T;
-                kt_end(c, 1, (mt * (mt + 1.0) + 2.0 * extra * mt) * (double)(ke - ko), s,
-                       syrk_grid(T, TN, 0) > 2 * (c->ncu > 0 ? c->ncu : 256));
-            }
+    hipStream_t s = c->stream;
+    // auto width follows the order of the matrix still to update (tune.nb_adapt): the last blocks of a
+    // large matrix are a small matrix, whose few trailing tiles do not fill the chip at K = 1024
+    bool diag_done = false;
+    for (int ko = 0, nbo = NBO; ko < nfac; ko += nbo) {
+        nbo = (c->nb_outer > 0 || !c->tune.nb_adapt) ? NBO : nbo_for(ncol - ko);
+        const int ke = (ko + nbo < nfac) ? ko + nbo : nfac;
+        kt_begin(c, 2, s);
+        panel_rows(c, W, ld, d_info, Fpack_all, ko, ke, nbo, 0, M, true, s, diag_done);
+        {   // algorithmic flops of the panel phase: diagonal block w^3/3 + rows below (m - w) w^2
+            const double w = (double)(ke - ko), m = (double)(M - ko);
+            kt_end(c, 2, w * w * (m - w) + w * w * w / 3.0, s);
+        }
+        diag_done = false;
+        if (ke >= M || ke >= ncol) continue;
+        const double mt = (double)(ncol - ke), extra = (double)(M - ncol);
+        // the first diagonal block of the next outer block rides in this trailing update
+        FuseDiag fd{};
+        if (ke < nfac)
+            fd = FuseDiag{fpack_slot(c, Fpack_all, ke, ke), d_info, ke, (nfac - ke < GPMI_NB) ? nfac - ke : GPMI_NB, nullptr};
+        kt_begin(c, 1, s);
+        diag_done = launch_syrk_lower(c, s, W + (size_t)ke + (size_t)ko * ld, ld, W + (size_t)ke + (size_t)ke * ld, ld,
+                                      M - ke, ncol - ke, ke - ko, c->d_ctr, c->ncu, 0, &fd);
+        // algorithmic flops: lower triangle (incl. diagonal) of the square part + extra rows
+        {   // flag: more than one round of tiles (throughput-bound launch)
+            const int T = (M - ke + GT - 1) / GT, TNf = (ncol - ke + GT - 1) / GT, TN = TNf < T ? TNf : T;
+            kt_end(c, 1, (mt * (mt + 1.0) + 2.0 * extra * mt) * (double)(ke - ko), s,
+                   syrk_grid(T, TN) > 2 * (c->ncu > 0 ? c->ncu : 256));
         }
     }
-#ifdef GPMI_PROBES
-    else {
-        // Look-ahead over outer blocks on TWO streams.  With U(j) the trailing update by block j,
-        // split by columns into U1(j) (block column j + 1, all rows below) and U2(j) (the rest):
-        //   sB (panel stream): P(0) | U1(0) P(1) | U1(1) P(2) | ...   U1(j) waits for U2(j - 1)
-        //   sA (bulk stream):        | U2(0)      | U2(1)      | ...   U2(j) waits for P(j)
-        // The latency-bound panel phase P(j + 1) -- 8 x (diagonal block, panel solve, in-block
-        // product) per 1024 columns, a chain of small kernels -- and the thin U1(j) run while U2(j)
-        // fills the chip from the other stream: sA goes from one bulk update straight into the next
-        // as long as U1(j) + P(j + 1) take less time than U2(j).  The two streams are the context's
-        // calibrated dispatch streams (hardware queues on different command-processor pipes: kernels
-        // of queues that share a pipe are time-sliced instead of overlapped).
-        hipStream_t const caller = c->stream;
-        hipStream_t sA = caller, sB = c->pstream;
-        if (c->nq >= 2) {
-            sA = c->qstream[0];
-            sB = c->qstream[1];
-        }
-        (void)hipEventRecord(c->evM, caller);
-        if (sA != caller) (void)hipStreamWaitEvent(sA, c->evM, 0);
-        (void)hipStreamWaitEvent(sB, c->evM, 0);
-        {
-            const int ke0 = NBO < nfac ? NBO : nfac;
-            kt_begin(c, 2, sB);
-            panel_rows(c, W, ld, d_info, Fpack_all, 0, ke0, NBO, 0, M, true, sB);
-            const double w = (double)ke0, m = (double)M;
-            kt_end(c, 2, w * w * (m - w) + w * w * w / 3.0, sB);
-            (void)hipEventRecord(c->evP, sB);
-        }
-        bool u2_pending = false;
-        for (int ko = 0; ko < nfac; ko += NBO) {
-            const int ke = (ko + NBO < nfac) ? ko + NBO : nfac;
-            const int K = ke - ko;
-            if (ke >= M || ke >= ncol) break;
-            const double *Pj = W + (size_t)ko * ld;   // panel j: rows [ke, M) of columns [ko, ke)
-            if (ke >= nfac) {  // last factored block: Schur complement / augmented rows, nothing follows
-                (void)hipStreamWaitEvent(sA, c->evP, 0);
-                const double mt = (double)(ncol - ke), extra = (double)(M - ncol);
-                kt_begin(c, 1, sA);
-                launch_syrk_lower(c, sA, Pj + ke, ld, W + (size_t)ke + (size_t)ke * ld, ld, M - ke, ncol - ke, K, c->d_ctr, c->ncu);
-                kt_end(c, 1, (mt * (mt + 1.0) + 2.0 * extra * mt) * (double)K, sA);
-                break;
-            }
-            const int ke2 = (ke + NBO < nfac) ? ke + NBO : nfac;
-            const int w1 = ke2 - ke;
-            // U1(j) on sB: rows [ke, M) x columns [ke, ke2); its tile (0, 0) is the next diagonal block
-            if (u2_pending) (void)hipStreamWaitEvent(sB, c->evU, 0);
-            FuseDiag fd{fpack_slot(c, Fpack_all, ke, ke), d_info, ke, (nfac - ke < GPMI_NB) ? nfac - ke : GPMI_NB, nullptr};
-            kt_begin(c, 1, sB);
-            const bool fused = launch_syrk_lower(c, sB, Pj + ke, ld, W + (size_t)ke + (size_t)ke * ld, ld, M - ke, w1, K, c->d_ctr,
-                                                 c->ncu, 0, &fd);
-            kt_end(c, 1, ((double)w1 * ((double)w1 + 1.0) + 2.0 * (double)(M - ke2) * (double)w1) * (double)K, sB);
-            // U2(j) on sA: rows [ke2, M) x columns [ke2, ncol)
-            u2_pending = false;
-            if (ke2 < M && ke2 < ncol) {
-                (void)hipStreamWaitEvent(sA, c->evP, 0);
-                const double mt = (double)(ncol - ke2), extra = (double)(M - ncol);
-                kt_begin(c, 1, sA);
-                launch_syrk_lower(c, sA, Pj + ke2, ld, W + (size_t)ke2 + (size_t)ke2 * ld, ld, M - ke2, ncol - ke2, K, c->d_ctr, c->ncu);
-                kt_end(c, 1, (mt * (mt + 1.0) + 2.0 * extra * mt) * (double)K, sA);
-                (void)hipEventRecord(c->evU, sA);
-                u2_pending = true;
-            }
-            // P(j + 1) on sB
-            kt_begin(c, 2, sB);
-            panel_rows(c, W, ld, d_info, Fpack_all, ke, ke2, NBO, 0, M, true, sB, fused);
-            {
-                const double w = (double)w1, m = (double)(M - ke);
-                kt_end(c, 2, w * w * (m - w) + w * w * w / 3.0, sB);
-            }
-            (void)hipEventRecord(c->evP, sB);
-        }
-        if (sA != caller) {
-            (void)hipEventRecord(c->evM, sA);
-            (void)hipStreamWaitEvent(caller, c->evM, 0);
-        }
-        (void)hipEventRecord(c->evU, sB);
-        (void)hipStreamWaitEvent(caller, c->evU, 0);
-    }
-#endif  // GPMI_PROBES
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gpmi_fail(GPMI_EHIP, "potrf launch failed: %s", hipGetErrorString(e));
     return 0;
@@ -1730,7 +1094,7 @@ static void trsm_right_rec(const gpmi_ctx *c, hipStream_t s, const double *L, si
     const int r0 = lower_out ? cm : 0;                           // rows of the right half that are wanted
     const double *A = X + (size_t)r0 + (size_t)c0 * ldx, *B = L + (size_t)cm + (size_t)c0 * ldl;
     double *C = X + (size_t)r0 + (size_t)cm * ldx;
-    if (upper_tri == 1 && (c->tune.gemm_variant == 3 || c->tune.gemm_variant == 0)) {
+    if (upper_tri == 1) {
         dim3 grid((c1 - cm + GT - 1) / GT, (mr + GT - 1) / GT);  // x: column tiles, y: row tiles (long K first)
         hipLaunchKernelGGL(k_gemm_nt<0>, grid, 256, 0, s, A, ldx, B, ldl, C, ldx, mr, c1 - cm, cm - c0, 0x100, 0,
                            FuseDiag{nullptr, nullptr, c0, 0, nullptr}, KSplit{});

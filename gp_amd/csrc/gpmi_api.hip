@@ -106,8 +106,7 @@ extern "C" int gpmi_kernel_timing(gpmi_ctx *c, int reset, double *out9);
 // to another queue's trailing update).  Neither HIP nor HSA tells which pipe a queue is on, so
 // it is measured: a long many-round kernel on stream a, a one-workgroup kernel on stream b and
 // the time until b's kernel is done -- ~15 us if the two queues dispatch concurrently, a time
-// slice or the whole long kernel if not.  Candidates are dedicated queues: the CU-mask API gives
-// every stream its own hardware queue instead of one shared out of the runtime's pool.
+// slice or the whole long kernel if not.
 namespace {
 __global__ __launch_bounds__(256) void k_cal_long(int *sink, int spin)
 {
@@ -148,21 +147,6 @@ static int streams_concurrent(gpmi_ctx *c, hipStream_t a, hipStream_t b, bool *c
     return 0;
 }
 
-#ifdef GPMI_PROBES
-static int full_mask_stream(gpmi_ctx *c, hipStream_t *out)
-{
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, c->device));
-    const int words = (prop.multiProcessorCount + 31) / 32;
-    std::vector<uint32_t> mask(words, 0xFFFFFFFFu);
-    if (prop.multiProcessorCount % 32) mask[words - 1] = (1u << (prop.multiProcessorCount % 32)) - 1u;
-    HIPCHK(hipExtStreamCreateWithCUMask(out, (uint32_t)words, mask.data()));
-    hipLaunchKernelGGL(k_cal_short, dim3(1), 64, 0, *out, c->d_info + 8);  // binds the hardware queue
-    HIPCHK(hipStreamSynchronize(*out));
-    return 0;
-}
-#endif
-
 // up to 4 dedicated streams that are pairwise concurrent (one per pipe)
 // want: concurrent streams the caller can use (lanes, at most 4).  The search is resumed when a later call wants
 // more than an earlier one found: which hardware queue a new stream lands on depends on the streams that exist at
@@ -177,17 +161,9 @@ static int calibrate_streams(gpmi_ctx *c, int want = 4)
     int nq = c->nq, rc;
     for (int i = 0; i < 10 && nq < want; ++i) {
         hipStream_t cand;
-#ifdef GPMI_PROBES
-        const char *kind = getenv("GPMI_CAL_KIND");  // experiment: 1 = dedicated (CU-mask API) queues
-        if (kind && atoi(kind) == 1) {
-            if ((rc = full_mask_stream(c, &cand))) return rc;
-        } else
-#endif
-        {
-            HIPCHK(hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
-            hipLaunchKernelGGL(k_cal_short, dim3(1), 64, 0, cand, c->d_info + 8);  // binds the hardware queue
-            HIPCHK(hipStreamSynchronize(cand));
-        }
+        HIPCHK(hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
+        hipLaunchKernelGGL(k_cal_short, dim3(1), 64, 0, cand, c->d_info + 8);  // binds the hardware queue
+        HIPCHK(hipStreamSynchronize(cand));
         bool ok = true;
         for (int k = 0; k < nq && ok; ++k)
             if ((rc = streams_concurrent(c, c->qstream[k], cand, &ok))) return rc;
@@ -196,17 +172,6 @@ static int calibrate_streams(gpmi_ctx *c, int want = 4)
     }
     c->nq = nq;
     if (getenv("GPMI_DEBUG")) fprintf(stderr, "[gpmi] stream calibration: %d concurrent dispatch streams\n", nq);
-    return 0;
-}
-
-int gpmi_lookahead_streams(gpmi_ctx *c)
-{
-    if (c->calibrate && c->nq == 0) {
-        int rc = calibrate_streams(c, 2);
-        if (rc) return rc;
-    }
-    if (c->nq >= 2) return 0;
-    if (!c->pstream) HIPCHK(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
     return 0;
 }
 
@@ -262,7 +227,6 @@ extern "C" int gpmi_create(gpmi_ctx **out, int device)
     c->pid = (int)getpid();
     gpmi_tuning_defaults(&c->tune);
     c->nb_outer = 0;  // auto
-    c->lookahead = 0; // (probe build: two-stream look-ahead over outer blocks, opt-in)
     c->calibrate = 1;
     c->ncu = prop.multiProcessorCount;
     // test hook: GPMI_FAIL_CREATE_AT=k makes the k-th resource acquisition below fail (leak tests of the unwind path)
@@ -272,9 +236,6 @@ extern "C" int gpmi_create(gpmi_ctx **out, int device)
 #define CREATE_STEP(expr) CREATE_CHK((++step == fail_at) ? hipErrorOutOfMemory : (expr))
     CREATE_STEP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    CREATE_STEP(hipEventCreateWithFlags(&c->evP, hipEventDisableTiming));
-    CREATE_STEP(hipEventCreateWithFlags(&c->evU, hipEventDisableTiming));
-    CREATE_STEP(hipEventCreateWithFlags(&c->evM, hipEventDisableTiming));
     CREATE_STEP(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
     CREATE_STEP(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
     CREATE_STEP(hipMalloc((void **)&c->Fpack, (size_t)GPMI_FPACK_SLOTS * GPMI_FPACK * sizeof(double)));
@@ -320,13 +281,9 @@ extern "C" int gpmi_destroy(gpmi_ctx *c)
             }
             delete k;
         }
-        hipEvent_t evs[] = {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->evM, c->evFork, c->evJoin, c->evP, c->evU};
+        hipEvent_t evs[] = {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->evFork, c->evJoin};
         for (hipEvent_t e : evs)
             if (e) (void)hipEventDestroy(e);
-        if (c->pstream) {
-            (void)hipStreamSynchronize(c->pstream);
-            (void)hipStreamDestroy(c->pstream);
-        }
         for (int q = 0; q < c->nq; ++q)
             if (c->qstream[q]) (void)hipStreamDestroy(c->qstream[q]);
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -399,12 +356,6 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         return 0;
     }
     if (!strcmp(name, "syrk_order")) {   // tile walk of multi-round trailing updates: 0 row-major, 2 XCD-partitioned bands
-#ifdef GPMI_PROBES
-        if (value == 1) {                // (probe build) the padded 8 x 8 super-tile grid of round 1
-            c->tune.syrk_order = 1;
-            return 0;
-        }
-#endif
         if (value != 0 && value != 2) return gpmi_fail(GPMI_EARG, "syrk_order must be 0 (row-major) or 2 (XCD bands)");
         c->tune.syrk_order = value;
         return 0;
@@ -490,34 +441,12 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         return 0;
     }
 #ifdef GPMI_PROBES
-    // switches of measured-and-rejected variants, kept as A/B material in the probe build only
-    if (!strcmp(name, "diag_waves")) {   // 5: the 5-wave / 3-barrier diagonal-block kernel of round 1
-        if (value != 4 && value != 5) return gpmi_fail(GPMI_EARG, "diag_waves must be 4 or 5");
-        c->tune.diag_waves = value;
-        return 0;
-    }
-    if (!strcmp(name, "lookahead")) {    // 1: two-stream look-ahead over outer blocks inside one factorisation
-        c->lookahead = value > 0;
-        return 0;
-    }
-    if (!strcmp(name, "lane_lookahead")) {
-        c->lane_lookahead = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "rect_auto")) {
-        c->tune.rect_auto = value;
-        return 0;
-    }
-    if (!strcmp(name, "gemm_variant")) {
-        c->tune.gemm_variant = value;
-        return 0;
-    }
     if (!strcmp(name, "debug_topology")) {  // prints which of the context's streams dispatch concurrently
-        hipStream_t st[4] = {c->stream, c->own_stream, c->pstream, c->nq > 1 ? c->qstream[1] : nullptr};
-        const char *nm[4] = {"stream", "own", "panel", "q1"};
-        for (int a = 0; a < 4; ++a) {
+        hipStream_t st[3] = {c->stream, c->own_stream, c->nq > 1 ? c->qstream[1] : nullptr};
+        const char *nm[3] = {"stream", "own", "q1"};
+        for (int a = 0; a < 3; ++a) {
             fprintf(stderr, "%8s:", nm[a]);
-            for (int b = 0; b < 4; ++b) {
+            for (int b = 0; b < 3; ++b) {
                 bool conc = false;
                 if (a != b && st[a] && st[b] && st[a] != st[b]) {
                     int rc = streams_concurrent(c, st[a], st[b], &conc);
@@ -1089,57 +1018,83 @@ extern "C" int gpmi_trsv_lower(gpmi_ctx *c, const double *L, int n, int ldl, con
 
 // ---- lanes: concurrent independent factorisations inside one GPU ---------------------------
 // Lane 0 is the context itself, lanes 1.. are internal contexts with their own workspaces.  Used
-// by the hyper-parameter grid and by the interpolation-table build (independent length-scales).
-static int lanes_prepare(gpmi_ctx *c, int lanes)
-{
-    for (int l = 1; l < lanes; ++l) {
-        if (!c->lane[l - 1]) {
-            int rc = gpmi_create(&c->lane[l - 1], c->device);
+// by the hyper-parameter grids, the interpolation-table build and the batched draws: independent
+// items, item g on lane g mod lanes.  One fan-out is prepare(), whatever the caller still enqueues
+// on its own stream, then run(); nothing synchronises with the host in between.
+struct LaneFan {
+    gpmi_ctx *const c;
+    int lanes = 1;
+    explicit LaneFan(gpmi_ctx *c_) : c(c_) {}
+    // the one place that knows where a lane's context lives
+    gpmi_ctx *ctx(int g) const { return g % lanes ? c->lane[g % lanes - 1] : c; }
+
+    // Lane count (grid_lanes, or auto: 4 -- one per calibrated dispatch stream -- or, for callers that ask for it, 3
+    // when that splits the items evenly and 4 does not), the lanes' contexts, then reserve(lc) for every lane BEFORE
+    // the fork: a growing buffer synchronises its stream.
+    template <class Reserve>
+    int prepare(int items, bool three_when_even, Reserve reserve)
+    {
+        lanes = c->grid_lanes > 0 ? c->grid_lanes : (three_when_even && items % 4 != 0 && items % 3 == 0 ? 3 : 4);
+        if (lanes > 8) lanes = 8;
+        if (lanes > items) lanes = items;
+        for (int l = 1; l < lanes; ++l) {
+            if (!c->lane[l - 1]) {
+                int rc = gpmi_create(&c->lane[l - 1], c->device);
+                if (rc) return rc;
+            }
+            gpmi_ctx *lc = c->lane[l - 1];
+            lc->tune = c->tune;
+            lc->nb_outer = c->nb_outer;
+            lc->calibrate = 0;  // a lane never probes for streams of its own
+        }
+        if (lanes > 1 && c->calibrate) {
+            int rc = calibrate_streams(c, lanes);
             if (rc) return rc;
         }
-        gpmi_ctx *lc = c->lane[l - 1];
-        lc->tune = c->tune;
-        lc->nb_outer = c->nb_outer;
-        lc->lookahead = c->lane_lookahead;  // default 0: concurrent lanes already fill the panel phases
-        lc->calibrate = 0;                  // a lane never probes for streams of its own
-    }
-    if (lanes > 1 && c->calibrate) {
-        int rc = calibrate_streams(c, lanes);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// lanes fork from / join into the caller's stream; with calibration every lane (lane 0 is this
-// context itself) runs on a stream of its own hardware pipe
-static void lanes_fork(gpmi_ctx *c, int lanes, hipStream_t caller)
-{
-    if (lanes <= 1) return;
-    c->lookahead = c->lane_lookahead;
-    const bool useq = c->calibrate && c->nq > 1;
-    (void)hipEventRecord(c->evFork, caller);
-    for (int l = 0; l < lanes; ++l) {
-        gpmi_ctx *lc = l ? c->lane[l - 1] : c;
-        lc->stream = (useq && l < c->nq) ? c->qstream[l] : (l ? lc->own_stream : caller);
-        lc->lanes_active = 1;
-        if (lc->stream != caller) (void)hipStreamWaitEvent(lc->stream, c->evFork, 0);
-    }
-}
-
-static void lanes_join(gpmi_ctx *c, int lanes, hipStream_t caller, int la_saved)
-{
-    if (lanes <= 1) return;
-    c->lookahead = la_saved;
-    for (int l = 0; l < lanes; ++l) {
-        gpmi_ctx *lc = l ? c->lane[l - 1] : c;
-        if (lc->stream != caller) {
-            (void)hipEventRecord(lc->evJoin, lc->stream);
-            (void)hipStreamWaitEvent(caller, lc->evJoin, 0);
+        for (int l = 0; l < lanes; ++l) {
+            int rc = reserve(ctx(l));
+            if (rc) return rc;
         }
-        lc->stream = l ? lc->own_stream : caller;
-        lc->lanes_active = 0;
+        return 0;
     }
-}
+    int prepare(int items, bool three_when_even)
+    {
+        return prepare(items, three_when_even, [](gpmi_ctx *) { return 0; });
+    }
+
+    // body(g, lane context) for g = 0 .. items - 1 between fork and join; stops at the first error and returns it.  The
+    // lanes fork from / join into the caller's stream on every path: a body cannot leave the entry point.  With
+    // calibration every lane (lane 0 is the context itself) runs on a stream of its own hardware pipe.
+    template <class Body>
+    int run(int items, Body body)
+    {
+        hipStream_t const caller = c->stream;
+        if (lanes > 1) {
+            const bool useq = c->calibrate && c->nq > 1;
+            (void)hipEventRecord(c->evFork, caller);
+            for (int l = 0; l < lanes; ++l) {
+                gpmi_ctx *lc = ctx(l);
+                lc->stream = (useq && l < c->nq) ? c->qstream[l] : (l ? lc->own_stream : caller);
+                lc->lanes_active = 1;
+                if (lc->stream != caller) (void)hipStreamWaitEvent(lc->stream, c->evFork, 0);
+            }
+        }
+        int rc = 0;
+        for (int g = 0; g < items && !rc; ++g) rc = body(g, ctx(g));
+        if (lanes > 1) {
+            for (int l = 0; l < lanes; ++l) {
+                gpmi_ctx *lc = ctx(l);
+                if (lc->stream != caller) {
+                    (void)hipEventRecord(lc->evJoin, lc->stream);
+                    (void)hipStreamWaitEvent(caller, lc->evJoin, 0);
+                }
+                lc->stream = l ? lc->own_stream : caller;
+                lc->lanes_active = 0;
+            }
+        }
+        return rc;
+    }
+};
 
 // ---- latent exact GP: f = chol(K) z --------------------------------------------------------
 extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
@@ -1308,21 +1263,15 @@ extern "C" int gpmi_logml_grid_dev(gpmi_ctx *c, const double *dX, int n, int ldx
     // another point's bulk update fills the chip.  Lanes fork from / join into the caller's stream.
     // auto: 4 lanes (one per calibrated dispatch stream), or 3 when that splits the grid evenly and 4 does not; a fifth
     // lane has no pipe of its own: G = 10 at N = 4096 / 8192 took 0.85 / 3.89 ms per point on 5 lanes, 0.71 / 3.58 on 4
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : (G % 4 == 0 ? 4 : (G % 3 == 0 ? 3 : 4));
-    if (lanes > 8) lanes = 8;
-    if (lanes > G) lanes = G;
-    int rc = lanes_prepare(c, lanes);
+    LaneFan fan(c);
+    int rc = fan.prepare(G, true);
     if (rc) return rc;
-    const int la_saved = c->lookahead;
-    hipStream_t const caller = c->stream;
-    lanes_fork(c, lanes, caller);
-    for (int g = 0; g < G && !rc; ++g) {
+    rc = fan.run(G, [&](int g, gpmi_ctx *lc) {
         SeParams p;
-        rc = fill_params(&p, D, alpha[g], &rho[g], 1);
-        gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
-        if (!rc) rc = logml_core(lc, dX, n, ldx, dy, p, sigma[g] * sigma[g] + jitter, d_out3 + 3 * (size_t)g, d_info + g);
-    }
-    lanes_join(c, lanes, caller, la_saved);
+        int rg = fill_params(&p, D, alpha[g], &rho[g], 1);
+        if (!rg) rg = logml_core(lc, dX, n, ldx, dy, p, sigma[g] * sigma[g] + jitter, d_out3 + 3 * (size_t)g, d_info + g);
+        return rg;
+    });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -1346,18 +1295,11 @@ extern "C" int gpmi_logml_grid_ard_dev(gpmi_ctx *c, const double *dX, int n, int
     if (small_logml(c, n, D, G)) {
         return small_grid(c, dX, n, ldx, D, dy, alpha, ell, D, sigma, G, jitter, d_out3, d_info);
     }
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : (G % 4 == 0 ? 4 : (G % 3 == 0 ? 3 : 4));
-    if (lanes > 8) lanes = 8;
-    if (lanes > G) lanes = G;
-    if ((rc = lanes_prepare(c, lanes))) return rc;
-    const int la_saved = c->lookahead;
-    hipStream_t const caller = c->stream;
-    lanes_fork(c, lanes, caller);
-    for (int g = 0; g < G && !rc; ++g) {
-        gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
-        rc = logml_core(lc, dX, n, ldx, dy, ps[g], sigma[g] * sigma[g] + jitter, d_out3 + 3 * (size_t)g, d_info + g);
-    }
-    lanes_join(c, lanes, caller, la_saved);
+    LaneFan fan(c);
+    if ((rc = fan.prepare(G, true))) return rc;
+    rc = fan.run(G, [&](int g, gpmi_ctx *lc) {
+        return logml_core(lc, dX, n, ldx, dy, ps[g], sigma[g] * sigma[g] + jitter, d_out3 + 3 * (size_t)g, d_info + g);
+    });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -1472,21 +1414,12 @@ extern "C" int gpmi_joint_logml_grid_dev(gpmi_ctx *c, const double *dt, int n, c
     if (n <= 0 || !dt || !dyy || !alpha || !l || !sigma || !d_out3 || !d_info) return gpmi_fail(GPMI_EARG, "bad argument");
     for (int g = 0; g < G; ++g)
         if (!(l[g] > 0.0)) return gpmi_fail(GPMI_EARG, "length-scale must be positive");
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : (G % 4 == 0 ? 4 : (G % 3 == 0 ? 3 : 4));
-    if (lanes > 8) lanes = 8;
-    if (lanes > G) lanes = G;
-    int rc = lanes_prepare(c, lanes);
+    LaneFan fan(c);
+    int rc = fan.prepare(G, true, [&](gpmi_ctx *lc) { return reserve_ws(lc, 2 * n + 1, 2 * n); });
     if (rc) return rc;
-    for (int k = 0; k < lanes; ++k)
-        if ((rc = reserve_ws(k ? c->lane[k - 1] : c, 2 * n + 1, 2 * n))) return rc;
-    const int la_saved = c->lookahead;
-    hipStream_t const caller = c->stream;
-    lanes_fork(c, lanes, caller);
-    for (int g = 0; g < G && !rc; ++g) {
-        gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
-        rc = joint_logml_core(lc, dt, n, dyy, alpha[g], l[g], sigma[g], jitter, d_out3 + 3 * (size_t)g, d_info + g);
-    }
-    lanes_join(c, lanes, caller, la_saved);
+    rc = fan.run(G, [&](int g, gpmi_ctx *lc) {
+        return joint_logml_core(lc, dt, n, dyy, alpha[g], l[g], sigma[g], jitter, d_out3 + 3 * (size_t)g, d_info + g);
+    });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -1688,32 +1621,22 @@ static int interp_factors(gpmi_ctx *c, const double *x, int n, const double *lp,
     // are independent factorisations: they run on the grid lanes, entry p on lane p mod lanes, every
     // lane in its own workspace and staging buffers, and nothing synchronises with the host until
     // all are enqueued.
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
-    if (lanes > 8) lanes = 8;
-    if (lanes > P) lanes = P;
-    if ((rc = lanes_prepare(c, lanes))) return rc;
-    // buffers every lane needs, sized BEFORE the fork (a growing buffer synchronises its stream)
-    for (int l = 0; l < lanes; ++l) {
-        gpmi_ctx *lc = l ? c->lane[l - 1] : c;
-        if ((rc = rbf_cov_chol_reserve(lc, n))) return rc;
-    }
-    const int la_saved = c->lookahead;
+    LaneFan fan(c);
+    if ((rc = fan.prepare(P, false, [&](gpmi_ctx *lc) { return rbf_cov_chol_reserve(lc, n); }))) return rc;
     hipStream_t const caller = c->stream;
     HIPCHK(hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, caller));
-    lanes_fork(c, lanes, caller);
-    for (int p = 0; p < P && !rc; ++p) {
-        gpmi_ctx *lc = (p % lanes == 0) ? c : c->lane[p % lanes - 1];
+    rc = fan.run(P, [&](int p, gpmi_ctx *lc) {
         double *Lc, *S;
         int ldd;
-        rc = rbf_cov_chol_core(lc, dx, n, lp[p], &Lc, &S, &ldd);
-        if (rc) break;
+        int rp = rbf_cov_chol_core(lc, dx, n, lp[p], &Lc, &S, &ldd);
+        if (rp) return rp;
         hipStream_t s = lc->stream;
         launch_copy_matrix(s, Lc, (size_t)ldd, Lt + (size_t)p * ld * n, ld, n, n, 0);
         launch_copy_matrix(s, S, (size_t)ldd, dLt + (size_t)p * ld * n, ld, n, n, 0);
         if (hipMemcpyAsync(dinfo + p, lc->d_info, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            rc = gpmi_fail(GPMI_EHIP, "info copy failed");
-    }
-    lanes_join(c, lanes, caller, la_saved);
+            return gpmi_fail(GPMI_EHIP, "info copy failed");
+        return 0;
+    });
     if (rc) return rc;
     std::vector<int> info(P, 0);
     HIPCHK(hipMemcpyAsync(info.data(), dinfo, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, caller));
@@ -3264,12 +3187,8 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
         }
         return grad_grid_down(c, dres, GPMI_SMALL_GRAD_RES, dinfo, G, D, alpha, rho, sigma, out3, grad, info);
     }
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
-    if (lanes > 8) lanes = 8;
-    if (lanes > G) lanes = G;
-    if ((rc = lanes_prepare(c, lanes))) return rc;
-    for (int k = 0; k < lanes; ++k)
-        if ((rc = logml_grad_reserve(k ? c->lane[k - 1] : c, n, D, G > 1))) return rc;
+    LaneFan fan(c);
+    if ((rc = fan.prepare(G, false, [&](gpmi_ctx *lc) { return logml_grad_reserve(lc, n, D, G > 1); }))) return rc;
     double *dX, *dy, *dres;
     if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
     // the root context's scratch also holds its packed panel factors (logml_grad_reserve): the results live behind them
@@ -3277,14 +3196,9 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
     if ((rc = scratch_buf(c, ((size_t)npan * GPMI_FPACK + (size_t)G * (GRAD_RES + 1) + 8) * sizeof(double), &dres))) return rc;
     dres += (size_t)npan * GPMI_FPACK;
     int *dinfo = (int *)(dres + (size_t)G * GRAD_RES);
-    const int la_saved = c->lookahead;
-    hipStream_t const caller = c->stream;
-    lanes_fork(c, lanes, caller);
-    for (int g = 0; g < G && !rc; ++g) {
-        gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
-        rc = logml_grad_core(lc, dX, n, n, dy, ps[g], sigma[g] * sigma[g] + jitter, dres + (size_t)g * GRAD_RES, dinfo + g, G > 1);
-    }
-    lanes_join(c, lanes, caller, la_saved);
+    rc = fan.run(G, [&](int g, gpmi_ctx *lc) {
+        return logml_grad_core(lc, dX, n, n, dy, ps[g], sigma[g] * sigma[g] + jitter, dres + (size_t)g * GRAD_RES, dinfo + g, G > 1);
+    });
     if (rc) return rc;
     return grad_grid_down(c, dres, GRAD_RES, dinfo, G, D, alpha, rho, sigma, out3, grad, info);
 }
@@ -3618,19 +3532,14 @@ static int logml_grad_grid_core(gpmi_ctx *c, const double *dX, int n, int ldx, i
     const bool small = D <= GPMI_MAXD && n <= (G >= 2 ? c->tune.small_ng : c->tune.small_ng1);
     const size_t np = 2 + (size_t)n_ell, stride = small ? GPMI_SMALL_GRAD_RES : GRAD_RES;
     const size_t head = small ? 0 : (size_t)((n + GPMI_NB - 1) / GPMI_NB) * GPMI_FPACK;
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
-    if (lanes > 8) lanes = 8;
-    if (lanes > G) lanes = G;
+    LaneFan fan(c);
     const int per = G < GPMI_SMALL_PTS ? G : GPMI_SMALL_PTS;
     static_assert(GPMI_SMALL_GRAD_DEV_PTS == GPMI_SMALL_PTS, "one workspace size for both one-workgroup gradient grids");
     if (small) {
         if ((rc = reserve_ws_small(c, n, 2 * per))) return rc;
         if ((rc = reserve_small_par(c, G))) return rc;
-    } else {
-        if ((rc = lanes_prepare(c, lanes))) return rc;
-        for (int k = 0; k < lanes; ++k)
-            if ((rc = logml_grad_reserve(k ? c->lane[k - 1] : c, n, D, G > 1))) return rc;
-    }
+    } else if ((rc = fan.prepare(G, false, [&](gpmi_ctx *lc) { return logml_grad_reserve(lc, n, D, G > 1); })))
+        return rc;
     double *base;
     if ((rc = scratch_buf(c, (head + (size_t)G * (stride + 2 * np + 3 + 1) + 8) * sizeof(double), &base))) return rc;
     double *dres = base + head, *dpar = dres + (size_t)G * stride;
@@ -3650,14 +3559,9 @@ static int logml_grad_grid_core(gpmi_ctx *c, const double *dX, int n, int ldx, i
         launch_logml_grad_batch_dev(c->stream, dX, n, ldx, D, dy, alpha, ell, sigma, G, jitter, c->d_spar, c->W, per, dres, d_info,
                                     c->d_sinfo);
     } else {
-        const int la_saved = c->lookahead;
-        hipStream_t const caller = c->stream;
-        lanes_fork(c, lanes, caller);
-        for (int g = 0; g < G && !rc; ++g) {
-            gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
-            rc = logml_grad_core(lc, dX, n, ldx, dy, ps[g], sigma[g] * sigma[g] + jitter, dres + (size_t)g * stride, d_info + g, G > 1);
-        }
-        lanes_join(c, lanes, caller, la_saved);
+        rc = fan.run(G, [&](int g, gpmi_ctx *lc) {
+            return logml_grad_core(lc, dX, n, ldx, dy, ps[g], sigma[g] * sigma[g] + jitter, dres + (size_t)g * stride, d_info + g, G > 1);
+        });
         if (rc) return rc;
     }
     // the finishing kernel's parameters, in stream order
@@ -3840,27 +3744,18 @@ extern "C" int gpmi_joint_logml_grad_grid(gpmi_ctx *c, const double *t, int n, c
     int rc;
     for (int g = 0; g < G; ++g)
         if ((rc = joint_grad_check(n, alpha[g], l[g]))) return rc;
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
-    if (lanes > 8) lanes = 8;
-    if (lanes > G) lanes = G;
-    if ((rc = lanes_prepare(c, lanes))) return rc;
-    for (int k = 0; k < lanes; ++k)
-        if ((rc = joint_logml_grad_reserve(k ? c->lane[k - 1] : c, n, G > 1))) return rc;
+    LaneFan fan(c);
+    if ((rc = fan.prepare(G, false, [&](gpmi_ctx *lc) { return joint_logml_grad_reserve(lc, n, G > 1); }))) return rc;
     double *dt, *dyy, *dres;
     if ((rc = upload_joint(c, t, n, yy, &dt, &dyy))) return rc;
     const int npan = (2 * n + GPMI_NB - 1) / GPMI_NB;
     if ((rc = scratch_buf(c, ((size_t)npan * GPMI_FPACK + (size_t)G * 7 + 8) * sizeof(double), &dres))) return rc;
     dres += (size_t)npan * GPMI_FPACK;
     int *dinfo = (int *)(dres + (size_t)G * 6);
-    const int la_saved = c->lookahead;
-    hipStream_t const caller = c->stream;
-    lanes_fork(c, lanes, caller);
-    for (int g = 0; g < G && !rc; ++g) {
-        gpmi_ctx *lc = (g % lanes == 0) ? c : c->lane[g % lanes - 1];
+    rc = fan.run(G, [&](int g, gpmi_ctx *lc) {
         double *r = dres + (size_t)g * 6;
-        rc = joint_logml_grad_core(lc, dt, n, dyy, alpha[g], l[g], sigma[g], jitter, r, r + 3, dinfo + g, G > 1);
-    }
-    lanes_join(c, lanes, caller, la_saved);
+        return joint_logml_grad_core(lc, dt, n, dyy, alpha[g], l[g], sigma[g], jitter, r, r + 3, dinfo + g, G > 1);
+    });
     if (rc) return rc;
     std::vector<double> hr((size_t)G * 6);
     HIPCHK(hipMemcpyAsync(hr.data(), dres, hr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -4176,14 +4071,8 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
         if (!(params[3 * b] > 0.0)) return gpmi_fail(GPMI_EARG, "length-scale must be positive");
     int rc;
     const bool small = small_sample_derivs(c, n, m, B);
-    int lanes = c->grid_lanes > 0 ? c->grid_lanes : 4;
-    if (lanes > 8) lanes = 8;
-    if (lanes > B) lanes = B;
-    if (!small) {
-        if ((rc = lanes_prepare(c, lanes))) return rc;
-        for (int l = 0; l < lanes; ++l)
-            if ((rc = sample_derivs_reserve(l ? c->lane[l - 1] : c, n, m))) return rc;
-    }
+    LaneFan fan(c);
+    if (!small && (rc = fan.prepare(B, false, [&](gpmi_ctx *lc) { return sample_derivs_reserve(lc, n, m); }))) return rc;
     StageCall sc(c);
     const size_t t_ = sc.in(t, n, 1, n), ts_ = sc.in(ts, m, 1, m), Y_ = sc.in(Y, n, B, ldy), Z_ = sc.in(Z, m, B, ldz),
                  D_ = sc.out(draws, m, B, ldd), M_ = sc.out(mus, m, B, ldmu), st_ = sc.mat((B + 1) / 2);   // one status word per draw
@@ -4194,15 +4083,11 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
     if (small) {
         if ((rc = sample_derivs_small(c, dt, n, dts, m, dY, params, B, jitter, dZ, dD, dM, dst))) return rc;
     } else {
-        const int la_saved = c->lookahead;
-        lanes_fork(c, lanes, caller);
-        for (int b = 0; b < B && !rc; ++b) {
-            gpmi_ctx *lc = (b % lanes == 0) ? c : c->lane[b % lanes - 1];
+        rc = fan.run(B, [&](int b, gpmi_ctx *lc) {
             const double l = params[3 * b], a = params[3 * b + 1], sy = params[3 * b + 2];
-            rc = sample_derivs_core(lc, dt, n, dts, m, dY + (size_t)b * n, a, l, sy * sy, jitter, dZ + (size_t)b * m, dD + (size_t)b * m,
-                                    dM + (size_t)b * m, dst + b);
-        }
-        lanes_join(c, lanes, caller, la_saved);
+            return sample_derivs_core(lc, dt, n, dts, m, dY + (size_t)b * n, a, l, sy * sy, jitter, dZ + (size_t)b * m, dD + (size_t)b * m,
+                                      dM + (size_t)b * m, dst + b);
+        });
         if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(info, dst, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, caller));
@@ -4966,7 +4851,6 @@ static int debug_sync_all(gpmi_ctx *c)
 {
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->own_stream && c->own_stream != c->stream) HIPCHK(hipStreamSynchronize(c->own_stream));
-    if (c->pstream) HIPCHK(hipStreamSynchronize(c->pstream));
     for (int q = 0; q < c->nq; ++q)
         if (c->qstream[q]) HIPCHK(hipStreamSynchronize(c->qstream[q]));
     for (int l = 0; l < 7; ++l)

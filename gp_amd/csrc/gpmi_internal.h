@@ -48,16 +48,14 @@ __host__ __device__ inline void gpmi_grad_from_sums(const double *hs, int D, dou
 // Algorithm switches of one context (gpmi_set_option).  Per context, never process-global: two
 // contexts or two host threads do not change each other's algorithm; grid lanes copy their root's.
 struct gpmi_tuning {
-    int syrk_order;       // tile walk of multi-round trailing updates: 0 row-major, 2 XCD-partitioned bands (1: probe build, padded super-tiles)
+    int syrk_order;       // tile walk of multi-round trailing updates: 0 row-major, 2 XCD-partitioned bands
     int stagger;          // (mode << 16) | number of s_sleep(127) (~3.5 us each) for the late workgroup of a CU pair
     int fuse_diag;        // default 15; bit 0: in-block GEMMs, bit 1: trailing SYRK (multi-round), bit 2: sub-tiled diagonal tile, bit 3: single-round SYRK (sub-tiled)
-    int diag_waves;       // (probe build only) 4: k_potrf_diag4 (default), 5: k_potrf_diag
     int nb_adapt;         // outer-block width re-chosen per block from the order of the matrix still to update
     int nb_thr[3];        // ... >= nb_thr[0]: 1024 columns, >= nb_thr[1]: 512, >= nb_thr[2]: 256, below: 128
     int ksplit, ksplit_max;
     int block_recursive;
     int se_nt;            // non-temporal stores in k_se_cov<>
-    int gemm_variant, rect_auto;  // A/B kernels: honoured by the probe build (-DGPMI_PROBES) only
     int small_n;          // grids of marginal likelihoods at n <= small_n (and D <= GPMI_MAXD): one workgroup per point, one launch (0: off)
     int small_n1;         // ... a single evaluation (or a grid of fewer than 6 points) up to this n: beyond it the multi-CU launch chain is faster
     int small_m;          // partial factorisation of <= small_m rows: one workgroup, one launch (0: off)
@@ -105,10 +103,6 @@ struct gpmi_ctx {
     double *stage[4];
     size_t stage_bytes[4];
     int nb_outer;            // outer panel width (multiple of GPMI_NB)
-    int lookahead;           // (probe build only) two-stream look-ahead over outer blocks: 0 off (default), 1 on
-    hipStream_t pstream;     // panel stream of the look-ahead when no calibrated pair exists
-    hipEvent_t evM;
-    hipEvent_t evP, evU;     // panel done / next-panel columns updated
     int timing;
     hipEvent_t ev[4];
     double last_ms[3];
@@ -119,7 +113,6 @@ struct gpmi_ctx {
     // grid lanes: extra internal contexts (own workspace + streams) so that independent grid
     // points overlap -- one point's panel phase and SYRK tails run under another's bulk update
     int grid_lanes;          // 0 = auto
-    int lane_lookahead;      // panel look-ahead inside each lane of a multi-lane grid (default off)
     // Cholesky-factor interpolation table (gpmi_interp_*): P stacked n x itp_ld matrices each
     double *itp_L, *itp_dL, *itp_part;
     double *itp_lp;          // host copy of the P length-scales
@@ -150,7 +143,6 @@ struct gpmi_ctx {
 // event-pair recorder; begin/end bracket one launch on the context's stream
 void kt_begin(gpmi_ctx *c, int cat, hipStream_t s = nullptr);
 void kt_end(gpmi_ctx *c, int cat, double work, hipStream_t s = nullptr, int flag = 0);
-int gpmi_lookahead_streams(gpmi_ctx *c);  // two concurrently dispatching streams for the look-ahead (calibrated, or a panel stream)
 
 // ---- error plumbing -------------------------------------------------------
 int gpmi_fail(int code, const char *fmt, ...);

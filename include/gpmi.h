@@ -96,9 +96,9 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_cen" (gpmi_centered_gp_lp_grad[_dev] by one
  * workgroup up to n <= small_cen <= 256 (default 192: the measured crossover), D <= 8, k <= 8; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
  * n + m + 1 <= small_sd rows for at least small_sdb ((n + m + 1) / 400)^2 draws), "small_n2", "small_g2" (grids of at least small_g2 (n / 1024)^2 + 2 points run one workgroup per point up
- * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing"; unknown names return GPMI_EARG.  Switches of variants that
- * were measured and rejected ("lookahead", "syrk_order", "diag_waves", "gemm_variant", ...) exist in the probe
- * build only. */
+ * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing"; unknown names return GPMI_EARG.  The switches of variants
+ * that were measured and rejected ("lookahead", "lane_lookahead", "diag_waves", "gemm_variant", "rect_auto", "syrk_order" = 1)
+ * were removed with the variants (DESIGN.md sections 4 and 5 keep the measurements): both builds reject them. */
 GPMI_API int gpmi_set_option(gpmi_ctx *ctx, const char *name, int value);
 
 /* ---- covariance builders ---------------------------------------------- */
@@ -676,8 +676,8 @@ GPMI_API int gpmi_debug_counters(gpmi_ctx *ctx, int *nonzero);
 
 /* ---- probes: tools/ only ------------------------------------------------
  * Built into libgpmi_probes.so (-DGPMI_PROBES: `python -m gp_amd._build --probes`), never into the
- * shipped libgpmi.so: micro-benchmarks, the A/B kernel variants and their option names
- * (gemm_variant, rect_auto, debug_topology). */
+ * shipped libgpmi.so: micro-benchmarks and instruments of the product's kernels, and the
+ * debug_topology option. */
 #ifdef GPMI_PROBES
 /* Stand-alone trailing-update (SYRK, lower) launch on synthetic data, C(m x m) -= P P^T with
  * P m x k: average ms per launch over `reps` back-to-back launches (HIP events). */

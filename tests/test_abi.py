@@ -51,7 +51,7 @@ def test_probe_build_is_a_separate_library():
     assert sorted(exported) == sorted(_header_functions() + _header_functions(probes=True))
     assert sorted(_lib.PROBE_SYMBOLS) == _header_functions(probes=True)
     code = open(lib, "rb").read()
-    assert b"k_gemm9" in code and b"k_gemm9" not in open(_build.LIB, "rb").read()
+    assert b"k_probe_peak" in code and b"k_probe_peak" not in open(_build.LIB, "rb").read()
 
 
 def test_signatures_are_plain_c():

@@ -172,6 +172,29 @@ def test_grid_lanes_match_single_evaluations(ctx, orc):
             assert out[g, 0] == ctx.logml(X, y, 1.0, [rho[g]], sig[g])[0]  # bit-identical
 
 
+def test_error_inside_the_lane_fan_out_leaves_the_context_usable(ctx, orc):
+    """A host-side argument check that fails AFTER the lanes have forked (the third point's length-scale, found when
+    its parameters are filled in) must still join the lanes: the call reports the argument error, and the same valid
+    grid afterwards gives the bits it gave before, with every device counter back at zero."""
+    import gp_amd
+    X, y = orc.synth(300, 2)   # above the one-workgroup limits for a 4-point grid: the blocked path on the lanes
+    rho = np.array([0.2, 0.4, 0.6, 0.8]); sig = np.array([0.1, 0.2, 0.3, 0.4])
+    bad = rho.copy(); bad[2] = -1.0
+    ctx.set_option("grid_lanes", 4)
+    try:
+        first, info = ctx.logml_grid(X, y, 1.0, rho, sig)
+        assert np.all(info == 0)
+        with pytest.raises(gp_amd.GpmiError) as e:
+            ctx.logml_grid(X, y, 1.0, bad, sig)
+        assert e.value.code == -1   # GPMI_EARG
+        again, info = ctx.logml_grid(X, y, 1.0, rho, sig)
+        assert np.all(info == 0)
+        assert np.array_equal(again, first)   # bit-identical
+        assert ctx.debug_counters() == 0
+    finally:
+        ctx.set_option("grid_lanes", 0)
+
+
 @pytest.mark.parametrize("n,nbo", [(2500, 1024), (1333, 512), (1153, 0)])
 def test_fused_diagonal_modes_agree(ctx, orc, n, nbo):
     """The fused look-ahead variants (diagonal block factored inside the update that completes it;
@@ -224,7 +247,7 @@ def test_far_and_infinite_points_have_zero_covariance(ctx):
 
 
 def test_create_unwinds_on_every_failing_step_without_leaking(ctx):
-    """gpmi_create acquires a stream, five events, six device buffers and four timing events; when step k fails
+    """gpmi_create acquires a stream, two events, six device buffers and four timing events; when step k fails
     (GPMI_FAIL_CREATE_AT = k: the test hook makes the k-th acquisition report an allocation failure) everything
     acquired before it is released again: the free device memory after 20 rounds of failing creates at every step is
     what it was before, and a normal create still works.  KTimer events of a context are released by gpmi_destroy."""
@@ -235,7 +258,7 @@ def test_create_unwinds_on_every_failing_step_without_leaking(ctx):
     free0 = torch.cuda.mem_get_info(0)[0]
     try:
         for _ in range(20):
-            for k in range(1, 18):
+            for k in range(1, 15):  # every step of gpmi_create: the last one is the 14th
                 os.environ["GPMI_FAIL_CREATE_AT"] = str(k)
                 with pytest.raises(gp_amd.GpmiError) as e:
                     gp_amd.Context(0)

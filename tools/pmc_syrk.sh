@@ -1,8 +1,9 @@
 #!/bin/bash
 # PMC passes over the stand-alone SYRK probe (one counter group per run, as the guide asks).
-# usage: tools/pmc_syrk.sh <tag> <m> <k> <variant> <order>
+# usage: tools/pmc_syrk.sh <tag> <m> <k> <order>
 set -u
-TAG=$1; M=$2; K=$3; GV=$4; ORD=$5
+TAG=$1; M=$2; K=$3; ORD=$4
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
@@ -11,6 +12,6 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY S
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM_RD SQ_WAVES" \
            "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -- python3 $GRAFT_REPO_ROOT/tools/syrk_bench.py $M $K $GV 2 $ORD > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -3 $OUT/p$i.log; exit 1; }
+  timeout -k 10 200 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -- python3 $ROOT/tools/syrk_bench.py $M $K 2 $ORD > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -3 $OUT/p$i.log; exit 1; }
 done
-python3 $GRAFT_REPO_ROOT/tools/pmc_summary.py $OUT
+python3 $ROOT/tools/pmc_summary.py $OUT

@@ -9,7 +9,7 @@ print(rows[0].keys())
 for r in rows[lo:lo + n]:
     s = (int(r["Start_Timestamp"]) - t0) / 1e3; e = (int(r["End_Timestamp"]) - t0) / 1e3
     nm = r["Kernel_Name"]
-    for k in ("k_gemm_nt", "k_gemm8", "k_gemm9", "k_potrf_diag", "k_trsm_panel", "k_se_cov", "k_logml", "k_set_row"):
+    for k in ("k_gemm_nt", "k_potrf_diag", "k_trsm_panel", "k_se_cov", "k_logml", "k_set_row"):
         if k in nm:
             nm = k + nm.split(k)[1][:8]
             break
