@@ -5,6 +5,7 @@
 // relocatable device code), and in the probe build each has its own g_body stamp array.
 #pragma once
 #include "gpmi_internal.h"
+#include "syrk_walk.h"
 #include <math.h>
 #include <type_traits>
 
@@ -380,7 +381,7 @@ __device__ __forceinline__ void trsm_panel_body(const double *__restrict__ s_F, 
 // 1-KiB global_load_lds write; the 128-B row pad puts k and k+1 on opposite
 // halves of the 64 banks so the ds_read_b64 fragment reads are conflict-free.
 // ---------------------------------------------------------------------------
-constexpr int GT = 128, GK = 16, GP = 144;
+constexpr int GP = 144;  // GT = 128 and GK = 16 are syrk_walk.h's
 // Pair-row layout (PAIR, the blocked update kernels): a lane owns TWO ADJACENT operand rows per pair of MFMA tiles -- inside
 // the wave's 64 rows tile t, lane row lr is row (t >> 1) * 32 + 2 * lr + (t & 1) instead of t * 16 + lr -- so that the
 // fragments of tiles t, t + 1 (t even) are 16 contiguous bytes of a k-row (one ds_read_b128) and acc[tn][tm][i],

@@ -22,7 +22,8 @@
 // The device functions behind these kernels (potrf_diag4_body, trsm_panel_body, gemm_tile, gemm_quad64) live in
 // chol_device.h: the one-workgroup kernels of small_kernels.hip inline them too.  This file keeps the blocked kernels,
 // the triangular helpers (k_trsv_wave, k_trmv_*, k_logml_partial / finalize, k_get_row, k_pack_factors, ...), the
-// probe build's instruments, gpmi_tuning_defaults and the panel scheduler.
+// probe build's instruments, gpmi_tuning_defaults and the panel scheduler.  The tile walks of the SYRK mode (syrk_tile,
+// syrk_tile_bands) and the launch plan of the trailing update (syrk_plan) are host-and-device integer code in syrk_walk.h.
 // Reference: Stan cholesky_decompose (models/fit_hyperparameters.stan:25),
 // multi_normal_cholesky (:31), L*z (models/exact_gp.stan:25).
 #include "chol_device.h"
@@ -57,65 +58,6 @@ __global__ __launch_bounds__(256) void k_trsm_panel(double *__restrict__ Acol, s
         trsm_panel_body<false>(s_F, Acol, lda, r, r < M, nb_act);
 }
 
-// SYRK tile order 0: block b is tile b of the row-major walk of the lower triangle.
-// TN < T: the lower TRAPEZOID of a T x TN tile grid (a trailing matrix with more rows than columns,
-// e.g. the augmented row): the TN x TN triangle first, then the rows below it.
-__device__ __forceinline__ bool syrk_tile(int b, int T, int TN, int order, int &ti, int &tj)
-{
-    if (order == 0) {  // plain row-major walk of the lower triangle / trapezoid
-        const int tri = TN * (TN + 1) / 2;
-        if (b >= tri) {
-            const int q = b - tri;
-            ti = TN + q / TN;
-            tj = q % TN;
-            return ti < T;
-        }
-        int i = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-        while ((i + 1) * (i + 2) / 2 <= b) ++i;
-        while (i * (i + 1) / 2 > b) --i;
-        ti = i;
-        tj = b - i * (i + 1) / 2;
-        return ti < T;
-    }
-    return false;  // walk 2 has its own enumeration (syrk_tile_bands); no other walk exists
-}
-__host__ inline int syrk_grid(int T, int TN) { return TN * (TN + 1) / 2 + (T - TN) * TN; }  // tiles of the triangle / trapezoid
-
-// XCD-partitioned band walk (order 2) of the lower triangle / trapezoid, WITHOUT a padded grid: the valid tiles are
-// enumerated band by band (8 tile rows), inside a band column by column -- 64 consecutive tiles are an 8 x 8 patch --
-// and workgroup b takes canonical tile (b % 8) S + b / 8, S = ceil(ntiles / 8): the workgroups the dispatcher deals to
-// one XCD (observed: b % 8; speed only, any placement is correct) walk ONE contiguous eighth of that order.  The 64
-// tiles resident on an XCD at a time then share 8 row blocks (for a whole band) and 8 column blocks of the panel
-// through that XCD's L2 instead of ~5 + 15 that change every round.  Every XCD gets the same number of tiles, so the
-// launch ends as evenly as the row-major walk; the last partial round of EACH XCD is what the tail split cuts into
-// quadrants, and a thin last tile row (the augmented row) is multiplied as quadrants by its own workgroup.
-__device__ __forceinline__ void syrk_tile_bands(int c, int T, int TN, int &ti, int &tj)
-{
-    for (int r0 = 0;; r0 += 8) {
-        const int R = (T - r0 < 8) ? T - r0 : 8;
-        const int cf = r0 < TN ? r0 : TN;                          // columns left of the band's diagonal block: R tiles each
-        const int dmax = (TN - r0 < R) ? (TN - r0 > 0 ? TN - r0 : 0) : R;  // columns r0 + d of the diagonal block: rows d .. R - 1
-        const int cnt = R * cf + dmax * R - dmax * (dmax - 1) / 2;
-        if (c < cnt || R <= 0) {
-            if (c < R * cf) {
-                tj = c / R;
-                ti = r0 + c - tj * R;
-                return;
-            }
-            c -= R * cf;
-            int d = 0;
-            while (d < dmax - 1 && c >= R - d) {
-                c -= R - d;
-                ++d;
-            }
-            tj = r0 + d;
-            ti = r0 + d + c;
-            return;
-        }
-        c -= cnt;
-    }
-}
-
 // Two workgroups share a CU and its matrix pipes.  All tiles cost the same, so workgroups that
 // start together stay in lock-step: both reach their memory-bound epilogue at the same time
 // and the pipes idle.  Delaying the second-dispatched workgroup of each CU once, by about one
@@ -144,7 +86,6 @@ __device__ __forceinline__ void stagger_start(double (&smem)[2][2][GK][GP], int 
 // own tile is stored, while the other workgroups of the launch are still updating.  The
 // diagonal-block latency chain (27 us per panel) then runs inside the update instead of after
 // it, needs no launch and no free CU of its own, and the panel solve follows directly.
-constexpr int SUBWG = 9;  // workgroups (x 4 waves = 36 sub-tiles of 16 x 16) of the sub-tiled diagonal tile of a fused launch
 struct FuseDiag {
     double *Fp;   // packed-factor slot of that panel; nullptr: no fusion
     int *info;
@@ -210,16 +151,6 @@ __device__ __forceinline__ void gemm_sub16(const double *__restrict__ A, size_t 
         else *q = v;
     }
 }
-
-// Tail split of a SYRK launch: the R < slots tiles of the last, partial round would hold R
-// workgroup slots for a whole tile time while the rest of the chip idles.  Each of them is cut
-// into its four 64 x 64 quadrants (blocks bfull + 4 t + q), computed by gemm_quad64: independent
-// outputs, no exchange between workgroups, the same sums in the same order as timing-independent
-// code must have.
-struct KSplit {
-    int bfull;   // blocks below this index are whole tiles
-    int S;       // 4: quadrants; <= 1: no split
-};
 
 #ifdef GPMI_PROBES
 // shader-clock probe: per workgroup of the SYRK kernel, elapsed shader cycles (s_memtime) and elapsed
@@ -756,6 +687,7 @@ void gpmi_tuning_defaults(gpmi_tuning *t)
     t->ksplit = 1;
     t->ksplit_max = 100;
     t->block_recursive = 1;
+    t->debug_ncu = 0;     // test hook: the trailing-update planner sees the device's own CU count
     t->se_nt = 1;
     t->small_n = 256;
     t->small_n1 = 128;
@@ -831,100 +763,42 @@ static bool launch_gemm_nt_fused(const gpmi_ctx *c, hipStream_t s, const double 
 //                  blocks of a large matrix are a small matrix.  Pays since single-round trailing updates carry the next
 //                  diagonal block (fuse_diag bit 3): N = 8192 5.63 -> 5.35 ms one at a time, 3.54 -> 3.38 on lanes;
 //                  N = 4096 1.54 -> 1.47; N = 16384 28.0 -> 27.4 / 23.3 -> 23.1 (thresholds swept in steps of 1024)
-// tune.ksplit      quadrant split of the tail-round tiles of a SYRK launch (see KSplit) ...
-// tune.ksplit_max  ... when at most this many tiles are left for the last round.  Whole tiles of a round this thin run
-// alone on their CUs (~115 us at K = 1024 instead of ~250 us shared); four quadrant workgroups take
-// ~75 us as long as they, too, have CUs of their own (4 R <= ~400).  Measured per launch (K = 1024):
-// R = 16..92: -0.04 .. -0.065 ms; R = 136..340: +0.03 .. +0.06 ms.
+// the CU count the trailing-update planner sees: the device's, or the "debug_ncu" test hook's
+static int plan_ncu(const gpmi_ctx *c) { return c->tune.debug_ncu > 0 ? c->tune.debug_ncu : c->ncu; }
 
-// returns true when fd was given and the launch factors the diagonal block at C's origin
-static bool launch_syrk_lower(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int M,
-                              int N, int K, int *ctr, int ncu, int tri = 0, const FuseDiag *fd = nullptr)
+// C(lower) -= P P^T by the plan of syrk_plan (syrk_walk.h: tile walk, tail split, fused diagonal block); returns the plan --
+// .fuse: fd was given and the launch factors the diagonal block at C's origin
+static SyrkPlan launch_syrk_lower(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int M,
+                                  int N, int K, int ncu, int tri = 0, const FuseDiag *fd = nullptr)
 {
-    if (tri && M > 0 && N > 0 && K > 0) {  // upper-triangular panel: plain kernel, row-major tiles, zero K-range skipped
-        const int T = (M + GT - 1) / GT;
-        hipLaunchKernelGGL(k_gemm_nt<1>, dim3(syrk_grid(T, T)), 256, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, 0x100, 0,
-                           FuseDiag{}, KSplit{});
-        return false;
-    }
-    if (M <= 0 || N <= 0 || K <= 0) return false;
-    const int T = (M + GT - 1) / GT;
-    // N < M: lower trapezoid
-    const int TNf = (N + GT - 1) / GT, TN = TNf < T ? TNf : T;
-    const int slots = 2 * (ncu > 0 ? ncu : 256);
-    // tile walk: 0 row-major; 2 XCD-partitioned bands (launches of more than one round of tiles: that is where the
-    // operand re-reads that miss the XCD L2s come from).
-    // Walk 2 is the default for an evaluation that has the chip to itself (N = 16384: L2 hit rate 53 -> 79 %, L2-miss
-    // traffic 1.27 -> 0.65 GB per launch, 27.31 -> 27.07 ms); under the grid lanes, where four launches share every
-    // XCD, its static per-XCD partition loses 1.6 % (23.09 -> 23.45 ms per point) and the row-major walk stays.
-    const int syrk_order = (c->tune.syrk_order == 2 && !c->lanes_active && syrk_grid(T, TN) > slots) ? 2 : 0;
-    const int ntiles = syrk_grid(T, TN);
-    const int stg = ntiles >= 1024 ? c->tune.stagger : 0;  // only when every CU holds two workgroups for many rounds
-    // only in launches of more than one round of tiles, where workgroup 0's extra 27 us do not
-    // lengthen the kernel
-    bool fuse = fd && fd->Fp && (c->tune.fuse_diag & 2) && ntiles > slots;  // tile (0, 0) is block 0 in walks 0 and 2
-    // Single-round launches: the next diagonal block rides along as well, sub-tiled like in the in-block products
-    // (fused_subtiles_and_diag) -- its 36 sub-tiles and the block's factorisation (~6 + 21 us) run beside the other
-    // tiles instead of in a kernel of their own behind the launch (tune.fuse_diag bit 3).
-    int ord = syrk_order;
-    FuseDiag fdl = fuse ? *fd : FuseDiag{};
-    if (!fuse && fd && fd->Fp && (c->tune.fuse_diag & 8) && syrk_order == 0 && M >= GT && N >= GT && K % 64 == 0 && c->d_ctr) {
-        fuse = true;
-        ord |= 0x200;
-        fdl = *fd;
-        fdl.ctr = c->d_ctr + 8;
-    }
-    KSplit ks{};
-    int grid = ntiles;
-    if (syrk_order == 2) {
-        // every XCD walks S tiles on its slots / 8 workgroup slots: its last partial round, when thin, runs as quadrants
-        // (quadrant 0 by the tile's own workgroup, 1 .. 3 by workgroups behind the grid)
-        const int S = (ntiles + 7) / 8, per = slots / 8;
-        const int S_full = (S / per) * per, Rx = S - S_full;
-        grid = 8 * S;
-        if (c->tune.ksplit && K % GK == 0 && Rx > 0 && 8 * Rx <= c->tune.ksplit_max) {
-            ks = KSplit{S_full, 4};
-            grid += 3 * 8 * Rx;
-        }
-    } else
-    if (c->tune.ksplit && syrk_order == 0 && K % GK == 0) {
-        int first = ntiles;  // first tile computed as quadrants
-        const int bfull = (ntiles / slots) * slots, R = ntiles - bfull;
-        if (R > 0 && R <= c->tune.ksplit_max) first = bfull;
-        // A last tile row with few valid rows -- the augmented row y^T of the marginal likelihood makes
-        // every trailing update end in a row of T tiles with ONE valid row -- costs a whole tile time
-        // per tile (2.4 % of all tiles at N = 16384); as quadrants only the MFMA tiles that hold
-        // valid rows are multiplied (1/8 of the work).
-        const int vlast = M - (T - 1) * GT;
-        if (T > 1 && vlast <= 64 && ntiles - TN < first) first = ntiles - TN;  // the last tile row has TN tiles
-        if ((ord & 0x200) && first < 1) first = 1;  // tile 0 belongs to the sub-tile blocks
-        if (first < ntiles) {
-            ks = KSplit{first, 4};
-            grid = first + 4 * (ntiles - first);
-        }
-    }
-    if (ord & 0x200) grid += SUBWG - 1;
-    hipLaunchKernelGGL(k_gemm_nt<1>, dim3(grid), 256, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, ord, stg, fdl, ks);
-    return fuse;
+    // the sub-tiled single-round fusion (bit 3) needs the context's counter
+    const SyrkTune tune{c->tune.syrk_order, c->tune.stagger, c->d_ctr ? c->tune.fuse_diag : (c->tune.fuse_diag & ~8), c->tune.ksplit,
+                        c->tune.ksplit_max};
+    const SyrkPlan p = syrk_plan(M, N, K, syrk_slots(ncu), tune, c->lanes_active, fd && fd->Fp, tri);
+    if (!p.launch) return p;
+    FuseDiag fdl = p.fuse ? *fd : FuseDiag{};
+    if (p.order & 0x200) fdl.ctr = c->d_ctr + 8;
+    hipLaunchKernelGGL(k_gemm_nt<1>, dim3(p.grid), 256, 0, s, P, ldp, P, ldp, C, ldc, M, N, K, p.order, p.stagger, fdl, p.ks);
+    return p;
 }
 
 #ifdef GPMI_PROBES
 void launch_syrk_probe(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int m, int k)
 {
-    launch_syrk_lower(c, s, P, ldp, C, ldc, m, m, k, c->d_ctr, c->ncu);
+    launch_syrk_lower(c, s, P, ldp, C, ldc, m, m, k, plan_ncu(c));
 }
 #endif
 
 // C(lower) -= U U^T for an upper-triangular n x n U
 void launch_syrk_uut(const gpmi_ctx *c, hipStream_t s, const double *U, size_t ldu, double *C, size_t ldc, int n)
 {
-    launch_syrk_lower(c, s, U, ldu, C, ldc, n, n, n, nullptr, 0, 1);
+    launch_syrk_lower(c, s, U, ldu, C, ldc, n, n, n, 0, 1);
 }
 
 // C(lower) -= P P^T for a full n x n P: the trailing update's launch (tile walk, tail split) with nothing fused
 void launch_syrk_ppt(const gpmi_ctx *c, hipStream_t s, const double *P, size_t ldp, double *C, size_t ldc, int n)
 {
-    launch_syrk_lower(c, s, P, ldp, C, ldc, n, n, n, c->d_ctr, c->ncu);
+    launch_syrk_lower(c, s, P, ldp, C, ldc, n, n, n, plan_ncu(c));
 }
 
 // tune.block_recursive  1: in-block updates by recursive halving; 0: 128 / 256 / rest-of-block levels
@@ -1055,14 +929,12 @@ int launch_potrf_partial(gpmi_ctx *c, double *W, size_t ld, int M, int ncol, int
         if (ke < nfac)
             fd = FuseDiag{fpack_slot(c, Fpack_all, ke, ke), d_info, ke, (nfac - ke < GPMI_NB) ? nfac - ke : GPMI_NB, nullptr};
         kt_begin(c, 1, s);
-        diag_done = launch_syrk_lower(c, s, W + (size_t)ke + (size_t)ko * ld, ld, W + (size_t)ke + (size_t)ke * ld, ld,
-                                      M - ke, ncol - ke, ke - ko, c->d_ctr, c->ncu, 0, &fd);
-        // algorithmic flops: lower triangle (incl. diagonal) of the square part + extra rows
-        {   // flag: more than one round of tiles (throughput-bound launch)
-            const int T = (M - ke + GT - 1) / GT, TNf = (ncol - ke + GT - 1) / GT, TN = TNf < T ? TNf : T;
-            kt_end(c, 1, (mt * (mt + 1.0) + 2.0 * extra * mt) * (double)(ke - ko), s,
-                   syrk_grid(T, TN) > 2 * (c->ncu > 0 ? c->ncu : 256));
-        }
+        const SyrkPlan plan = launch_syrk_lower(c, s, W + (size_t)ke + (size_t)ko * ld, ld, W + (size_t)ke + (size_t)ke * ld, ld, M - ke,
+                                                ncol - ke, ke - ko, plan_ncu(c), 0, &fd);
+        diag_done = plan.fuse;
+        // algorithmic flops: lower triangle (incl. diagonal) of the square part + extra rows; flag: more than one round of
+        // tiles (throughput-bound launch)
+        kt_end(c, 1, (mt * (mt + 1.0) + 2.0 * extra * mt) * (double)(ke - ko), s, plan.multi_round);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gpmi_fail(GPMI_EHIP, "potrf launch failed: %s", hipGetErrorString(e));

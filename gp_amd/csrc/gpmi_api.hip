@@ -346,6 +346,12 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
         c->tune.block_recursive = value != 0;
         return 0;
     }
+    if (!strcmp(name, "debug_ncu")) {  // test hook: the CU count the trailing-update planner sees (0: the device's own)
+        if (value != 0 && (value < 4 || value > c->ncu))
+            return gpmi_fail(GPMI_EARG, "debug_ncu must be 0 (the device's count) or 4 .. %d", c->ncu);
+        c->tune.debug_ncu = value;
+        return 0;
+    }
     if (!strcmp(name, "nb_adapt")) {
         c->tune.nb_adapt = value != 0;
         return 0;

@@ -55,6 +55,7 @@ struct gpmi_tuning {
     int nb_thr[3];        // ... >= nb_thr[0]: 1024 columns, >= nb_thr[1]: 512, >= nb_thr[2]: 256, below: 128
     int ksplit, ksplit_max;
     int block_recursive;
+    int debug_ncu;        // test hook: CU count the trailing-update planner sees instead of the device's (0: the device's); no kernel changes
     int se_nt;            // non-temporal stores in k_se_cov<>
     int small_n;          // grids of marginal likelihoods at n <= small_n (and D <= GPMI_MAXD): one workgroup per point, one launch (0: off)
     int small_n1;         // ... a single evaluation (or a grid of fewer than 6 points) up to this n: beyond it the multi-CU launch chain is faster

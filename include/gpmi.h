@@ -96,7 +96,9 @@ GPMI_API int gpmi_reserve(gpmi_ctx *ctx, int n_max);
  * one workgroup up to n <= small_vjp <= 256; 0 sends every size to the blocked chain), "small_cen" (gpmi_centered_gp_lp_grad[_dev] by one
  * workgroup up to n <= small_cen <= 256 (default 192: the measured crossover), D <= 8, k <= 8; 0 sends every size to the blocked chain), "small_sd", "small_sdb" (gpmi_sample_derivs[_batch]: one workgroup per draw up to
  * n + m + 1 <= small_sd rows for at least small_sdb ((n + m + 1) / 400)^2 draws), "small_n2", "small_g2" (grids of at least small_g2 (n / 1024)^2 + 2 points run one workgroup per point up
- * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing"; unknown names return GPMI_EARG.  The switches of variants
+ * to n <= small_n2 <= 1024), "calibrate", "timing", "kernel_timing", "debug_ncu" (test hook like gpmi_debug_fill: the compute-unit
+ * count the planner of the trailing update sees -- 0: the device's own, 4 .. the device's count: that many; any other value
+ * returns GPMI_EARG and changes nothing; no kernel and no default changes, grid lanes copy it); unknown names return GPMI_EARG.  The switches of variants
  * that were measured and rejected ("lookahead", "lane_lookahead", "diag_waves", "gemm_variant", "rect_auto", "syrk_order" = 1)
  * were removed with the variants (DESIGN.md sections 4 and 5 keep the measurements): both builds reject them. */
 GPMI_API int gpmi_set_option(gpmi_ctx *ctx, const char *name, int value);

@@ -16,15 +16,32 @@ import pytest
 import logml_grad_reference as lg
 import loo_reference as lr
 import predict_reference as pr
-from test_gpu_logml_grad_parity import GRID_A, GRID_R, GRID_S, BAD, aug, chains, one_wg, routes  # noqa: F401  (fixtures: the contexts)
+from test_gpu_logml_grad_parity import GRID_A, GRID_R, GRID_S, BAD, aug, chains  # noqa: F401  (fixtures: the contexts)
 
 pytestmark = pytest.mark.gpu
 
 EARG = -1
 PAD = 1e3   # rows n .. ldx of X when ldx > n: never read into a result
-ROUTES = ("aug", "chains")
-PARITY = [(r, c) for r in ROUTES for c in lr.CASES]
+# "chains_ncu8": the three chains with the trailing-update planner made to see 8 compute units ("debug_ncu"), so that the
+# symmetric product -M M^T of the gradient (launch_syrk_ppt, the trailing update's launch) and the updates of the factorisation
+# take their multi-round paths at NCU8_CASE, n = 705 (21 tiles on 16 workgroup slots); the catalogue itself stops at n = 385
+ROUTES = ("aug", "chains", "chains_ncu8")
+NCU8_CASE = (705, 2, False, 0.15, "")
+PARITY = [(r, c) for r in ROUTES for c in lr.CASES] + [("chains_ncu8", NCU8_CASE)]
 KEYS = ("out3", "loo", "mu", "var", "lpd", "grad")
+
+
+@pytest.fixture(scope="module")
+def chains_ncu8():
+    from test_gpu_logml_grad_parity import ROUTES as GRAD_ROUTES, _context
+    c = _context(dict(GRAD_ROUTES["chains"], debug_ncu=8))
+    yield c
+    c.close()
+
+
+@pytest.fixture
+def routes(aug, chains, chains_ncu8):  # noqa: F811  (this file's routes: the two chain routes and the debug_ncu one)
+    return {"aug": aug, "chains": chains, "chains_ncu8": chains_ncu8}
 
 
 def _check(tag, got, ref, cond, scale=1.0):
@@ -142,7 +159,8 @@ def test_points_equal_gp_predict_without_the_point(routes, route, case, idx):
 
 
 # ---- 3. bits ------------------------------------------------------------------------------------------------------------
-BITS_CASES = {"aug": (129, 33, True, 0.0, ""), "chains": (129, 8, True, 1e-3, "")}
+BITS_CASES = {"aug": (129, 33, True, 0.0, ""), "chains": (129, 8, True, 1e-3, ""), "chains_ncu8": (129, 8, True, 1e-3, "")}
+WORKSPACE_CASES = dict(BITS_CASES, chains_ncu8=NCU8_CASE)   # ... where its launches are multi-round
 
 
 @pytest.mark.parametrize("route", ROUTES)
@@ -168,9 +186,10 @@ def test_repeated_calls_forms_and_null_outputs_give_identical_bits(routes, route
 
 @pytest.mark.parametrize("route", ROUTES)
 def test_results_do_not_depend_on_what_the_workspace_held(routes, route):
-    """n = 129 on both routes: after every double of the context's scratch was a NaN (0xFF) and 1.38e306 (0x7F)."""
+    """n = 129 on both routes, n = 705 on the debug_ncu one: after every double of the context's scratch was a NaN (0xFF) and
+    1.38e306 (0x7F)."""
     c = routes[route]
-    X, y, a, ell, s, jit = lg.case_inputs(*BITS_CASES[route])
+    X, y, a, ell, s, jit = lg.case_inputs(*WORKSPACE_CASES[route])
     r0 = c.logml_loo(X, y, a, ell, s, jit)
     assert c.debug_counters() == 0
     for byte in (0xFF, 0x7F):
