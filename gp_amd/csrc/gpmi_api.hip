@@ -486,6 +486,20 @@ extern "C" int gpmi_set_option(gpmi_ctx *c, const char *name, int value)
     return gpmi_fail(GPMI_EARG, "unknown option '%s'", name);
 }
 
+// Grow a device buffer (*buf of *bytes bytes) to at least `need` bytes; `what` names it in the message.  The stream is drained
+// before the old block is freed, and pointer and size read as empty until the new block exists.
+static int grow_dev(gpmi_ctx *c, double **buf, size_t *bytes, size_t need, const char *what)
+{
+    if (need <= *bytes) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (*buf) HIPCHK(hipFree(*buf));
+    *buf = nullptr;
+    *bytes = 0;
+    if (hipMalloc((void **)buf, need) != hipSuccess) return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes %s", need, what);
+    *bytes = need;
+    return 0;
+}
+
 // workspace for an (rows x cols) lower-stored matrix; ld padded so that columns do not
 // alias HBM channels and 16-column slack exists past the end for tile over-reads
 static int reserve_ws(gpmi_ctx *c, int rows, int cols)
@@ -499,15 +513,7 @@ static int reserve_ws(gpmi_ctx *c, int rows, int cols)
     if (const char *e = getenv("GPMI_LD_PAD")) ld += atoi(e);
 #endif
     const size_t need = ((size_t)ld * (size_t)(cols + 1) + 4096) * sizeof(double);
-    if (need > c->W_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->W) HIPCHK(hipFree(c->W));
-        c->W = nullptr;
-        c->W_bytes = 0;
-        if (hipMalloc((void **)&c->W, need) != hipSuccess)
-            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of workspace", need);
-        c->W_bytes = need;
-    }
+    if (int rc = grow_dev(c, &c->W, &c->W_bytes, need, "of workspace")) return rc;
     c->ld = ld;
     c->ncols = cols;
     return 0;
@@ -519,15 +525,7 @@ static int reserve_ws_small(gpmi_ctx *c, int n, int count)
     size_t ld, stride;
     small_ws_layout(n, &ld, &stride);
     const size_t need = (stride * (size_t)count + 4096) * sizeof(double);
-    if (need > c->W_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->W) HIPCHK(hipFree(c->W));
-        c->W = nullptr;
-        c->W_bytes = 0;
-        if (hipMalloc((void **)&c->W, need) != hipSuccess)
-            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of workspace", need);
-        c->W_bytes = need;
-    }
+    if (int rc = grow_dev(c, &c->W, &c->W_bytes, need, "of workspace")) return rc;
     c->ld = (int)ld;
     c->ncols = n;
     return 0;
@@ -553,30 +551,14 @@ extern "C" int gpmi_reserve(gpmi_ctx *c, int n_max)
 static int stage_buf(gpmi_ctx *c, int slot, size_t bytes, double **out)
 {
     bytes += 4096 * sizeof(double);  // slack for tile over-reads
-    if (bytes > c->stage_bytes[slot]) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->stage[slot]) HIPCHK(hipFree(c->stage[slot]));
-        c->stage[slot] = nullptr;
-        c->stage_bytes[slot] = 0;
-        if (hipMalloc((void **)&c->stage[slot], bytes) != hipSuccess)
-            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of staging", bytes);
-        c->stage_bytes[slot] = bytes;
-    }
+    if (int rc = grow_dev(c, &c->stage[slot], &c->stage_bytes[slot], bytes, "of staging")) return rc;
     *out = c->stage[slot];
     return 0;
 }
 
 static int scratch_buf(gpmi_ctx *c, size_t bytes, double **out)
 {
-    if (bytes > c->scratch_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->scratch) HIPCHK(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        if (hipMalloc((void **)&c->scratch, bytes) != hipSuccess)
-            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes of scratch", bytes);
-        c->scratch_bytes = bytes;
-    }
+    if (int rc = grow_dev(c, &c->scratch, &c->scratch_bytes, bytes, "of scratch")) return rc;
     *out = c->scratch;
     return 0;
 }
@@ -632,39 +614,33 @@ static int upload_xy(gpmi_ctx *c, const double *X, int n, int ldx, int D, const 
 // An entry point that takes host pointers travels one of two ways, and both lay their matrices out the same way: packed
 // (leading dimension = rows) one behind the other in ONE buffer, behind a head of GPMI_HB_HEAD doubles.  The head: word 0
 // holds the info word (an int), word 7 the completion flag (an int) of a one-launch call, the rest is spare.  Kernels take
-// every address as a pointer of its own, so this layout is the host's alone.  A caller names its slots -- in(): copied in
+// every address as a pointer of its own, so this layout is the host's alone.  A caller names its slots ONCE -- in(): copied in
 // from (src, rows, cols, ld) by begin(); out(): copied out to (dst, rows, cols, ld) by finish(), a null pointer keeps the slot
-// and copies nothing; mat(): a slot the caller reads itself -- and launches on dev() pointers between begin() and finish().
+// and copies nothing; mat(): a slot the caller reads itself -- picks the transport with begin(), hands dev() pointers, info()
+// and link() to its family's core, which owns the route (one workgroup or the chain) and makes every launch, and finish()es.
+//
+// HOST_PINNED (the one-workgroup routes): begin() packs the inputs (by the CPU) into the pinned, device-mapped buffer that the
+// kernel reads directly, reserves `scratch_doubles` of device scratch (c->scratch) for the kernel's copy of host-mapped inputs
+// and arms the completion flag; the kernel writes its results and info() straight into the buffer and publishes
+// (link()->flag, link()->seq) last; finish() waits for it and unpacks the outputs: no copy call in either direction.  A caller
+// whose kernels publish no flag (several launches) never takes link(), and finish() waits on the stream instead.
+// HOST_STAGED (the chains): the same layout in staging buffer 0 of the device: begin() copies the inputs up, finish() the
+// outputs and the info word down, with one synchronisation at the end.
+//
+// Who owns which device buffer.  stage[0] is the staged transport's: no core touches it.  The chains take stage[2] and stage[3]
+// (exact_gp_vjp_core stage[1] and stage[2]), c->scratch for their packed panel factors, c->d_fin and c->d_out; c->scratch is
+// therefore the pinned transport's scratch on the one-workgroup routes only, where no core uses it.  The grid and lane callers
+// name no slots: upload_xy / upload_joint put their data, shared by every lane, into stage[0] and stage[1] of the root context.
 #define GPMI_HB_HEAD 8
-struct HbCall {
-    struct Slot {
-        size_t off;
-        const double *src;
-        double *dst;
-        int rows, cols, ld;
-    };
-    gpmi_ctx *c;
-    size_t used = GPMI_HB_HEAD;   // doubles handed out so far
-    Slot slot[12];                // (the widest caller names 8)
-    int nslot = 0;
-    explicit HbCall(gpmi_ctx *ctx) : c(ctx) {}
-    size_t mat(size_t rows, size_t cols = 1)   // offset of a packed rows x cols slot; every slot starts a 64-byte line
-    {
-        const size_t o = used;
-        used = (used + rows * cols + 7) & ~(size_t)7;
-        return o;
-    }
-    size_t in(const double *src, int rows, int cols, int ld)
-    {
-        slot[nslot] = Slot{mat(rows, cols), src, nullptr, rows, cols, ld};
-        return slot[nslot++].off;
-    }
-    size_t out(double *dst, int rows, int cols, int ld)
-    {
-        slot[nslot] = Slot{mat(rows, cols), nullptr, dst, rows, cols, ld};
-        return slot[nslot++].off;
-    }
+enum HostTransport { HOST_PINNED, HOST_STAGED };
+// what a one-launch kernel needs from the pinned transport; a core is handed a null pointer by device callers and by the
+// staged transport
+struct HostLink {
+    double *scratch;   // device scratch for the kernel's copy of host-mapped inputs
+    int *flag;         // host-mapped completion flag, set to seq by the kernel's last store
+    int seq;
 };
+static HostLink link_or_none(const HostLink *l) { return l ? *l : HostLink{nullptr, nullptr, 0}; }
 
 // pinned, device-mapped host buffer of the one-launch host-buffer calls (inputs in, results out, no copy call)
 static int pin_reserve(gpmi_ctx *c, size_t need)
@@ -695,32 +671,74 @@ static int pin_wait(gpmi_ctx *c, const int *flag, int seq)
     return gpmi_fail(GPMI_EHIP, "the kernel of a one-launch call did not publish its completion flag");
 }
 
-// The one-launch call: begin() packs the inputs (by the CPU) into the pinned, device-mapped buffer that the kernel reads
-// directly, reserves the caller's device scratch (stage) and `ws_count` one-workgroup workspace slices of order ws_n, and arms
-// the completion flag; the kernel writes its results and info() straight into the buffer and publishes (flag(), seq) last;
-// finish() waits for it, unpacks the outputs and returns the info word: no copy call in either direction.  Callers whose
-// kernels publish no flag (several launches) pack(), wait on the stream and unpack().
-struct PinCall : HbCall {
-    using HbCall::HbCall;
-    int seq = 0;
-    double *stage = nullptr;
-    double *host(size_t o) const { return c->h_pin + o; }
-    double *dev(size_t o) const { return c->h_pin_dev + o; }
-    int *info() const { return (int *)c->h_pin_dev; }
-    int *flag() const { return (int *)(c->h_pin_dev + 7); }
-    int host_info() const { return *(const int *)c->h_pin; }
-    int pack()
+struct HostCall {
+    struct Slot {
+        size_t off;
+        const double *src;
+        double *dst;
+        int rows, cols, ld;
+    };
+    gpmi_ctx *c;
+    size_t used = GPMI_HB_HEAD;   // doubles handed out so far
+    Slot slot[12];                // (the widest caller names 8)
+    int nslot = 0;
+    HostTransport via = HOST_STAGED;
+    double *d = nullptr;          // the buffer's device address
+    HostLink lk{nullptr, nullptr, 0};
+    bool flagged = false;         // link() was taken: the kernel publishes the completion flag
+    explicit HostCall(gpmi_ctx *ctx) : c(ctx) {}
+    size_t mat(size_t rows, size_t cols = 1)   // offset of a packed rows x cols slot; every slot starts a 64-byte line
     {
-        int rc = pin_reserve(c, used * sizeof(double));
-        if (rc) return rc;
-        for (int q = 0; q < nslot; ++q) {
-            const Slot &t = slot[q];
-            if (!t.src) continue;
-            for (int j = 0; j < t.cols; ++j) memcpy(host(t.off) + (size_t)j * t.rows, t.src + (size_t)j * t.ld, (size_t)t.rows * sizeof(double));
+        const size_t o = used;
+        used = (used + rows * cols + 7) & ~(size_t)7;
+        return o;
+    }
+    size_t in(const double *src, int rows, int cols, int ld)
+    {
+        slot[nslot] = Slot{mat(rows, cols), src, nullptr, rows, cols, ld};
+        return slot[nslot++].off;
+    }
+    size_t out(double *dst, int rows, int cols, int ld)
+    {
+        slot[nslot] = Slot{mat(rows, cols), nullptr, dst, rows, cols, ld};
+        return slot[nslot++].off;
+    }
+    double *dev(size_t o) const { return d + o; }
+    double *host(size_t o) const { return c->h_pin + o; }   // pinned transport (and tri_host's read-back)
+    int *info() const { return (int *)d; }
+    double *scratch() const { return lk.scratch; }   // (for a pinned caller whose kernels publish no flag: see link())
+    const HostLink *link()
+    {
+        if (via != HOST_PINNED) return nullptr;
+        flagged = true;
+        return &lk;
+    }
+    int begin(HostTransport t, size_t scratch_doubles = 0)
+    {
+        int rc;
+        via = t;
+        if (via == HOST_STAGED) {
+            if ((rc = stage_buf(c, 0, used * sizeof(double), &d))) return rc;
+            for (int q = 0; q < nslot; ++q)
+                if (slot[q].src && (rc = h2d_matrix(c, slot[q].src, slot[q].rows, slot[q].cols, slot[q].ld, d + slot[q].off))) return rc;
+            return 0;
         }
+        if ((rc = pin_reserve(c, used * sizeof(double)))) return rc;
+        d = c->h_pin_dev;
+        for (int q = 0; q < nslot; ++q) {
+            const Slot &u = slot[q];
+            if (!u.src) continue;
+            for (int j = 0; j < u.cols; ++j) memcpy(host(u.off) + (size_t)j * u.rows, u.src + (size_t)j * u.ld, (size_t)u.rows * sizeof(double));
+        }
+        if ((rc = scratch_buf(c, scratch_doubles * sizeof(double), &lk.scratch))) return rc;
+        // the flag is cleared first: pin_reserve hands out fresh memory when the buffer grows, and a stale word must never
+        // read as done
+        __atomic_store_n((int *)(c->h_pin + 7), 0, __ATOMIC_RELEASE);
+        lk.flag = (int *)(c->h_pin_dev + 7);
+        lk.seq = ++c->pin_seq;
         return 0;
     }
-    void unpack() const
+    void unpack() const   // the out() slots from the pinned buffer to the caller's matrices, by the CPU
     {
         for (int q = 0; q < nslot; ++q) {
             const Slot &t = slot[q];
@@ -728,62 +746,23 @@ struct PinCall : HbCall {
             for (int j = 0; j < t.cols; ++j) memcpy(t.dst + (size_t)j * t.ld, host(t.off) + (size_t)j * t.rows, (size_t)t.rows * sizeof(double));
         }
     }
-    int begin(size_t stage_doubles, int ws_n, int ws_count)
+    // the results are the caller's when this returns: the info word (with_info == false: nobody wrote one, 0), or an error
+    int finish(bool with_info = true) const
     {
-        int rc;
-        if ((rc = pack())) return rc;
-        if ((rc = scratch_buf(c, stage_doubles * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, ws_n, ws_count))) return rc;
-        // the flag is cleared first: pin_reserve hands out fresh memory when the buffer grows, and a stale word must never
-        // read as done
-        __atomic_store_n((int *)(c->h_pin + 7), 0, __ATOMIC_RELEASE);
-        seq = ++c->pin_seq;
-        return 0;
-    }
-    int wait() const
-    {
+        int rc, word = 0;
+        if (via == HOST_STAGED) {
+            for (int q = 0; q < nslot; ++q)
+                if (slot[q].dst && (rc = d2h_matrix(c, d + slot[q].off, (size_t)slot[q].rows, slot[q].rows, slot[q].cols, slot[q].dst, slot[q].ld)))
+                    return rc;
+            if (with_info) HIPCHK(hipMemcpyAsync(&word, info(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return word;
+        }
         HIPCHK(hipGetLastError());
-        return pin_wait(c, (const int *)(c->h_pin + 7), seq);
-    }
-    int finish() const
-    {
-        int rc = wait();
-        if (rc) return rc;
+        if (!flagged) HIPCHK(hipStreamSynchronize(c->stream));
+        else if ((rc = pin_wait(c, (const int *)(c->h_pin + 7), lk.seq))) return rc;
         unpack();
-        return host_info();
-    }
-};
-
-// The staged call: the same layout in a staging buffer of the device (slot 0 unless the core it runs needs that one): begin()
-// copies the inputs up, finish() the outputs and the info word at d_info (nullable: none) down, with one synchronisation at
-// the end.
-static int staged_finish(gpmi_ctx *c, const int *d_info)
-{
-    int info = 0;
-    if (d_info) HIPCHK(hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return info;
-}
-struct StageCall : HbCall {
-    using HbCall::HbCall;
-    double *d = nullptr;
-    double *dev(size_t o) const { return d + o; }
-    int *info() const { return (int *)d; }
-    int begin(int stage_slot = 0)
-    {
-        int rc;
-        if ((rc = stage_buf(c, stage_slot, used * sizeof(double), &d))) return rc;
-        for (int q = 0; q < nslot; ++q)
-            if (slot[q].src && (rc = h2d_matrix(c, slot[q].src, slot[q].rows, slot[q].cols, slot[q].ld, d + slot[q].off))) return rc;
-        return 0;
-    }
-    int finish(const int *d_info) const
-    {
-        int rc;
-        for (int q = 0; q < nslot; ++q)
-            if (slot[q].dst && (rc = d2h_matrix(c, d + slot[q].off, (size_t)slot[q].rows, slot[q].rows, slot[q].cols, slot[q].dst, slot[q].ld)))
-                return rc;
-        return staged_finish(c, d_info);
+        return with_info ? *(const int *)c->h_pin : 0;
     }
 };
 
@@ -1103,6 +1082,33 @@ struct LaneFan {
 };
 
 // ---- latent exact GP: f = chol(K) z --------------------------------------------------------
+static bool small_exact_f(int n, int D) { return n <= 256 && D <= GPMI_MAXD; }
+
+// device (one workgroup: or host-mapped) X (ldx), z; f and *d_info written; enqueues on c->stream
+static int exact_gp_f_run(gpmi_ctx *c, const double *dX, int n, int ldx, const SeParams &p, double jitter, const double *dz, double *df,
+                          int *d_info, const HostLink *hl)
+{
+    int rc;
+    hipStream_t s = c->stream;
+    if (small_exact_f(n, p.D)) {   // one launch of one workgroup
+        if ((rc = reserve_ws_small(c, n, 1))) return rc;
+        const HostLink t = link_or_none(hl);
+        launch_exact_gp_small(s, dX, n, ldx, dz, p, jitter, c->W, df, d_info, c->d_info, t.scratch, t.flag, t.seq);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    if ((rc = reserve_ws(c, n, n))) return rc;
+    const size_t ld = (size_t)c->ld;
+    double *part;
+    if ((rc = stage_buf(c, 3, (size_t)trmv_lower_chunks(n) * n * sizeof(double), &part))) return rc;
+    HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int), s));
+    launch_se_cov(c, s, dX, n, ldx, nullptr, n, ldx, p, jitter, 1, c->W, ld);
+    if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, d_info, nullptr))) return rc;
+    launch_trmv_lower(s, c->W, ld, n, dz, df, part);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
                                double jitter, const double *z, double *f)
 {
@@ -1111,30 +1117,12 @@ extern "C" int gpmi_exact_gp_f(gpmi_ctx *c, const double *X, int n, int ldx, int
     SeParams p;
     int rc;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    hipStream_t s = c->stream;
-    if (n <= 256 && D <= GPMI_MAXD) {
-        // one launch of one workgroup; X, z in and f, info out through the pinned, device-mapped buffer
-        PinCall pc(c);
-        const size_t f_ = pc.out(f, n, 1, n), X_ = pc.in(X, n, D, ldx), z_ = pc.in(z, n, 1, n);
-        if ((rc = pc.begin((size_t)n * (D + 1), n, 1))) return rc;
-        launch_exact_gp_small(s, pc.dev(X_), n, n, pc.dev(z_), p, jitter, c->W, pc.dev(f_), pc.info(), c->d_info, pc.stage, pc.flag(),
-                              pc.seq);
-        return pc.finish();
-    }
-    double *dX, *dz;
-    if ((rc = upload_xy(c, X, n, ldx, D, z, &dX, &dz))) return rc;
-    if ((rc = reserve_ws(c, n, n))) return rc;
-    const size_t ld = (size_t)c->ld;
-    double *part;
-    if ((rc = stage_buf(c, 3, ((size_t)trmv_lower_chunks(n) + 1) * n * sizeof(double), &part))) return rc;
-    double *df = part + (size_t)trmv_lower_chunks(n) * n;
-    HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
-    launch_se_cov(c, s, dX, n, n, nullptr, n, n, p, jitter, 1, c->W, ld);
-    if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, c->d_info, nullptr))) return rc;
-    launch_trmv_lower(s, c->W, ld, n, dz, df, part);
-    if ((rc = d2h_matrix(c, df, (size_t)n, n, 1, f, n))) return rc;
-    const int info = staged_finish(c, c->d_info);
-    if (info)
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), z_ = hc.in(z, n, 1, n), f_ = hc.out(f, n, 1, n);
+    if ((rc = hc.begin(small_exact_f(n, D) ? HOST_PINNED : HOST_STAGED, (size_t)n * (D + 1)))) return rc;
+    if ((rc = exact_gp_f_run(c, hc.dev(X_), n, n, p, jitter, hc.dev(z_), hc.dev(f_), hc.info(), hc.link()))) return rc;
+    const int info = hc.finish();
+    if (info && !small_exact_f(n, D))   // the chain went on to multiply by a broken factor
         for (int i = 0; i < n; ++i) f[i] = NAN;
     return info;
 }
@@ -1204,16 +1192,18 @@ static int small_grid(gpmi_ctx *c, const double *dX, int n, int ldx, int D, cons
     return 0;
 }
 
+// hl: the pinned transport of a host caller on the one-workgroup route (X, y, d_out3, d_info host-mapped), else null
 static int logml_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p,
-                      double diag_add, double *d_out3, int *d_info)
+                      double diag_add, double *d_out3, int *d_info, const HostLink *hl = nullptr)
 {
     int rc;
     const int M = n + 1;
     if (small_logml(c, n, p.D)) {  // build, factorisation, solve and log-det in ONE launch of one workgroup
         if ((rc = reserve_ws_small(c, n, 1))) return rc;
+        const HostLink t = link_or_none(hl);
         tic(c, 0);
         tic(c, 1);
-        launch_logml_small(c->stream, dX, n, ldx, dy, p, diag_add, c->W, (size_t)c->ld, d_out3, d_info, c->d_info, nullptr);
+        launch_logml_small(c->stream, dX, n, ldx, dy, p, diag_add, c->W, (size_t)c->ld, d_out3, d_info, c->d_info, t.scratch, t.flag, t.seq);
         tic(c, 2);
         tic(c, 3);
         HIPCHK(hipGetLastError());
@@ -1316,27 +1306,19 @@ extern "C" int gpmi_logml(gpmi_ctx *c, const double *X, int n, int ldx, int D, c
 {
     ENTER(c);
     if (n <= 0 || !X || !y || !out3 || ldx < n || D < 1) return gpmi_fail(GPMI_EARG, "bad argument");
-    double *dX, *dy;
+    SeParams p;
     int rc;
-    if (small_logml(c, n, D)) {
-        // Small n, host buffers: X, y are copied (by the CPU) into a pinned, device-mapped buffer that the kernel
-        // reads directly, and the kernel writes (logml, sum log L_ii, z'z, info) straight into it: ONE launch and one
-        // stream synchronisation, no copy call in either direction (the four of the general path cost ~55 us,
-        // more than the kernel itself)
-        SeParams p;
-        if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-        PinCall pc(c);
-        const size_t out_ = pc.out(out3, 3, 1, 3), X_ = pc.in(X, n, D, ldx), y_ = pc.in(y, n, 1, n);
-        if ((rc = pc.begin((size_t)n * (D + 1), n, 1))) return rc;
-        launch_logml_small(c->stream, pc.dev(X_), n, n, pc.dev(y_), p, sigma * sigma + jitter, c->W, (size_t)c->ld, pc.dev(out_),
-                           pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = gpmi_logml_dev(c, dX, n, n, D, dy, alpha, ell, n_ell, sigma, jitter, c->d_out, c->d_info + 1))) return rc;
-    if ((rc = d2h_matrix(c, c->d_out, 3, 3, 1, out3, 3))) return rc;
-    const int info = staged_finish(c, c->d_info + 1);
-    if (c->timing) {
+    if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
+    // Small n: X, y are copied (by the CPU) into a pinned, device-mapped buffer that the kernel reads directly, and the kernel
+    // writes (logml, sum log L_ii, z'z, info) straight into it: ONE launch and no copy call in either direction (the four of
+    // the general path cost ~55 us, more than the kernel itself)
+    const bool small = small_logml(c, n, D);
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n), out_ = hc.out(out3, 3, 1, 3);
+    if ((rc = hc.begin(small ? HOST_PINNED : HOST_STAGED, (size_t)n * (D + 1)))) return rc;
+    if ((rc = logml_core(c, hc.dev(X_), n, n, hc.dev(y_), p, sigma * sigma + jitter, hc.dev(out_), hc.info(), hc.link()))) return rc;
+    const int info = hc.finish();
+    if (c->timing && !small) {   // (the one-launch route drains no stream: its events may still be pending)
         float ms;
         for (int i = 0; i < 3; ++i) {
             c->last_ms[i] = (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) == hipSuccess) ? ms : 0.0;
@@ -1435,16 +1417,13 @@ extern "C" int gpmi_joint_logml(gpmi_ctx *c, const double *t, int n, const doubl
                                 double l, double sigma, double jitter, double *out3)
 {
     ENTER(c);
-    if (n <= 0 || !t || !yy || !out3) return gpmi_fail(GPMI_EARG, "bad argument");
-    double *dt, *dyy;
+    if (n <= 0 || !t || !yy || !out3 || !(l > 0.0)) return gpmi_fail(GPMI_EARG, "bad argument");
     int rc;
-    if ((rc = stage_buf(c, 0, (size_t)n * sizeof(double), &dt))) return rc;
-    if ((rc = stage_buf(c, 1, (size_t)2 * n * sizeof(double), &dyy))) return rc;
-    HIPCHK(hipMemcpyAsync(dt, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dyy, yy, (size_t)2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if ((rc = gpmi_joint_logml_dev(c, dt, n, dyy, alpha, l, sigma, jitter, c->d_out, c->d_info + 1))) return rc;
-    if ((rc = d2h_matrix(c, c->d_out, 3, 3, 1, out3, 3))) return rc;
-    return staged_finish(c, c->d_info + 1);
+    HostCall hc(c);
+    const size_t t_ = hc.in(t, n, 1, n), yy_ = hc.in(yy, 2 * n, 1, 2 * n), out_ = hc.out(out3, 3, 1, 3);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    if ((rc = joint_logml_core(c, hc.dev(t_), n, hc.dev(yy_), alpha, l, sigma, jitter, hc.dev(out_), hc.info()))) return rc;
+    return hc.finish();
 }
 
 // ---- rbf_cov_chol (covariance.cpp:9-47) ---------------------------------------
@@ -1480,8 +1459,8 @@ static int rbf_cov_chol_reserve(gpmi_ctx *c, int n)
 }
 
 // device core: x resident in dx; on return (stream order) Lc holds L (zero upper) and S holds dL/dl,
-// both n x n with leading dimension ldd in the context's staging buffers 3 and 1
-static int rbf_cov_chol_core(gpmi_ctx *c, const double *dx, int n, double l, double **Lc_out, double **S_out, int *ldd_out)
+// both n x n with leading dimension ldd in the context's staging buffers 3 and 1, *d_info the factorisation's status
+static int rbf_cov_chol_core(gpmi_ctx *c, const double *dx, int n, double l, double **Lc_out, double **S_out, int *ldd_out, int *d_info)
 {
     int rc;
     if ((rc = reserve_ws(c, n, n))) return rc;
@@ -1495,13 +1474,13 @@ static int rbf_cov_chol_core(gpmi_ctx *c, const double *dx, int n, double l, dou
     if ((rc = stage_buf(c, 3, msz, &Lc))) return rc;
     if ((rc = scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &Fall))) return rc;
     hipStream_t s = c->stream;
-    HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
+    HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int), s));
     // Sigma (+1e-10 jitter, covariance.cpp:23-25) -> L
     SeParams p;
     double ell = l;
     if ((rc = fill_params(&p, 1, 1.0, &ell, 1))) return rc;
     launch_se_cov(c, s, dx, n, n, nullptr, n, n, p, 1e-10, 1, c->W, ld);
-    if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, c->d_info, Fall))) return rc;
+    if ((rc = launch_potrf_partial(c, c->W, ld, n, n, n, d_info, Fall))) return rc;
     launch_copy_matrix(s, c->W, ld, Lc, (size_t)ldd, n, n, 1);
     // tangent: Ldot = L Phi(L^-1 Sdot L^-T), Phi = lower triangle with halved diagonal
     hipLaunchKernelGGL(k_rbf_dsigma, dim3((n + 63) / 64, (n + 15) / 16), 256, 0, s, dx, n, l, S, (size_t)ldd);
@@ -1522,36 +1501,43 @@ static int rbf_cov_chol_core(gpmi_ctx *c, const double *dx, int n, double l, dou
     return 0;
 }
 
+// P factors and tangents of x by one workgroup each in ONE launch (n <= GPMI_NB; the single call and the table build): entry p
+// to Lout / dLout + p ostride (ldo) and info_out[p]; d_work: one device int per entry; x, the outputs and info_out may be
+// host-mapped (scratch != null: n doubles of device scratch)
+static int rbf_cov_chol_wg(gpmi_ctx *c, const double *dx, int n, const double *ls, int P, double *Lout, double *dLout, size_t ostride,
+                           size_t ldo, int *info_out, int *d_work, double *scratch)
+{
+    int rc;
+    if ((rc = reserve_ws_small(c, n, 3 * P))) return rc;
+    launch_rbf_cov_chol_small(c->stream, dx, n, ls, P, c->W, Lout, dLout, ostride, ldo, info_out, d_work, scratch);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int gpmi_rbf_cov_chol(gpmi_ctx *c, const double *x, int n, double l, double *L, int ldl,
                                  double *dLdl, int lddl)
 {
     ENTER(c);
     if (n <= 0 || !x || !L || !dLdl || ldl < n || lddl < n || !(l > 0.0)) return gpmi_fail(GPMI_EARG, "bad argument");
-    int rc, ldd;
-    double *dx, *Lc, *S;
-    hipStream_t s = c->stream;
-    if (n <= 64) {
-        // small n: ONE launch of one workgroup; x in, L / dL/dl / info out through the pinned, device-mapped buffer
-        // (tools/interp_small_bench.py: n = 50 144 -> 84 us; at n = 100 one workgroup takes 170 us against the chain's
-        // 157 -- ONE call stays on the chain there, the table build below does not); the kernel publishes no flag
-        PinCall pc(c);
-        const size_t x_ = pc.in(x, n, 1, n), L_ = pc.out(L, n, n, ldl), dL_ = pc.out(dLdl, n, n, lddl);
-        if ((rc = pc.pack())) return rc;
-        double *stage;
-        if ((rc = scratch_buf(c, (size_t)n * sizeof(double), &stage))) return rc;
-        if ((rc = reserve_ws_small(c, n, 3))) return rc;
-        launch_rbf_cov_chol_small(s, pc.dev(x_), n, &l, 1, c->W, pc.dev(L_), pc.dev(dL_), 0, (size_t)n, pc.info(), c->d_info, stage);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        pc.unpack();
-        return pc.host_info();
+    int rc;
+    // small n: ONE launch of one workgroup; x in, L / dL/dl / info out through the pinned, device-mapped buffer
+    // (tools/interp_small_bench.py: n = 50 144 -> 84 us; at n = 100 one workgroup takes 170 us against the chain's
+    // 157 -- ONE call stays on the chain there, the table build below does not); the kernel publishes no flag.
+    // The chain leaves L and dL/dl in buffers of its own at its own leading dimension: no slots, they are copied down from there
+    const bool small = n <= 64;
+    HostCall hc(c);
+    const size_t x_ = hc.in(x, n, 1, n), L_ = small ? hc.out(L, n, n, ldl) : 0, dL_ = small ? hc.out(dLdl, n, n, lddl) : 0;
+    if ((rc = hc.begin(small ? HOST_PINNED : HOST_STAGED, (size_t)n))) return rc;
+    if (small) {
+        if ((rc = rbf_cov_chol_wg(c, hc.dev(x_), n, &l, 1, hc.dev(L_), hc.dev(dL_), 0, (size_t)n, hc.info(), c->d_info, hc.scratch()))) return rc;
+        return hc.finish();
     }
-    if ((rc = stage_buf(c, 0, (size_t)n * sizeof(double), &dx))) return rc;
-    if ((rc = h2d_matrix(c, x, n, 1, n, dx))) return rc;
-    if ((rc = rbf_cov_chol_core(c, dx, n, l, &Lc, &S, &ldd))) return rc;
+    int ldd;
+    double *Lc, *S;
+    if ((rc = rbf_cov_chol_core(c, hc.dev(x_), n, l, &Lc, &S, &ldd, hc.info()))) return rc;
     if ((rc = d2h_matrix(c, Lc, (size_t)ldd, n, n, L, ldl))) return rc;
     if ((rc = d2h_matrix(c, S, (size_t)ldd, n, n, dLdl, lddl))) return rc;
-    return staged_finish(c, c->d_info);
+    return hc.finish();
 }
 
 // ---- Cholesky-factor interpolation over the length-scale ---------------------------
@@ -1607,13 +1593,13 @@ static int interp_factors(gpmi_ctx *c, const double *x, int n, const double *lp,
         hipStream_t s = c->stream;
         HIPCHK(hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
         const int per = P < 64 ? P : 64;
-        if ((rc = reserve_ws_small(c, n, 3 * per))) return rc;
         if ((rc = reserve_small_par(c, per))) return rc;
         const size_t msz = ld * (size_t)n;
-        for (int p0 = 0; p0 < P; p0 += per) {
+        for (int p0 = 0; p0 < P; p0 += per) {   // (the first launch is the widest: it sizes the workspace)
             const int pc = (P - p0 < per) ? P - p0 : per;
-            launch_rbf_cov_chol_small(s, dx, n, lp + p0, pc, c->W, Lt + (size_t)p0 * msz, dLt + (size_t)p0 * msz, msz,
-                                      ld, dinfo + p0, c->d_sinfo, nullptr);
+            if ((rc = rbf_cov_chol_wg(c, dx, n, lp + p0, pc, Lt + (size_t)p0 * msz, dLt + (size_t)p0 * msz, msz, ld, dinfo + p0, c->d_sinfo,
+                                      nullptr)))
+                return rc;
         }
         std::vector<int> info(P, 0);
         HIPCHK(hipMemcpyAsync(info.data(), dinfo, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1634,7 +1620,7 @@ static int interp_factors(gpmi_ctx *c, const double *x, int n, const double *lp,
     rc = fan.run(P, [&](int p, gpmi_ctx *lc) {
         double *Lc, *S;
         int ldd;
-        int rp = rbf_cov_chol_core(lc, dx, n, lp[p], &Lc, &S, &ldd);
+        int rp = rbf_cov_chol_core(lc, dx, n, lp[p], &Lc, &S, &ldd, lc->d_info);
         if (rp) return rp;
         hipStream_t s = lc->stream;
         launch_copy_matrix(s, Lc, (size_t)ldd, Lt + (size_t)p * ld * n, ld, n, n, 0);
@@ -1745,30 +1731,19 @@ static int approx_Lz_host(gpmi_ctx *c, double l, const double *z, double *f, dou
     if (!z || !f) return gpmi_fail(GPMI_EARG, "bad argument");
     const int n = c->itp_n;
     int rc;
-    double *dz;
-    if ((rc = stage_buf(c, 0, 3 * (size_t)n * sizeof(double), &dz))) return rc;
-    if (n <= 4096) {
-        // the per-iteration call of the interpolated model at the reference's size (N = 100, test_interpolate.R:5): z goes in
-        // and f (dfdl) come back through the pinned, device-mapped buffer -- three small launches, no copy call
-        PinCall pc(c);
-        const size_t z_ = pc.in(z, n, 1, n), f_ = pc.out(f, n, 1, n), g_ = pc.out(dfdl, n, 1, n);
-        if ((rc = pc.pack())) return rc;
-        const double *zsrc = pc.dev(z_);
-        if (n > GPMI_HMV_SMALL_N) {   // the chunked kernels read z once per row block: staged in device memory first
-            launch_copy_matrix(c->stream, zsrc, (size_t)n, dz, (size_t)n, n, 1, 0);
-            zsrc = dz;
-        }
-        if ((rc = approx_Lz_core(c, l, zsrc, pc.dev(f_), dfdl ? pc.dev(g_) : nullptr))) return rc;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        pc.unpack();
-        return 0;
+    // n <= 4096: the per-iteration call of the interpolated model at the reference's size (N = 100, test_interpolate.R:5): z goes
+    // in and f (dfdl) come back through the pinned, device-mapped buffer -- three small launches that publish no flag, no copy call
+    const bool pinned = n <= 4096, chunked = n > GPMI_HMV_SMALL_N;
+    HostCall hc(c);
+    const size_t z_ = hc.in(z, n, 1, n), f_ = hc.out(f, n, 1, n), g_ = hc.out(dfdl, n, 1, n);
+    if ((rc = hc.begin(pinned ? HOST_PINNED : HOST_STAGED, pinned && chunked ? (size_t)n : 0))) return rc;
+    const double *zsrc = hc.dev(z_);
+    if (pinned && chunked) {   // the chunked kernels read z once per row block: staged in device memory first
+        launch_copy_matrix(c->stream, zsrc, (size_t)n, hc.scratch(), (size_t)n, n, 1, 0);
+        zsrc = hc.scratch();
     }
-    if ((rc = h2d_matrix(c, z, n, 1, n, dz))) return rc;
-    if ((rc = approx_Lz_core(c, l, dz, dz + n, dfdl ? dz + 2 * (size_t)n : nullptr))) return rc;
-    if ((rc = d2h_matrix(c, dz + n, (size_t)n, n, 1, f, n))) return rc;
-    if (dfdl && (rc = d2h_matrix(c, dz + 2 * (size_t)n, (size_t)n, n, 1, dfdl, n))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    if ((rc = approx_Lz_core(c, l, zsrc, hc.dev(f_), dfdl ? hc.dev(g_) : nullptr))) return rc;
+    return hc.finish(false);
 }
 
 extern "C" int gpmi_approx_Lz(gpmi_ctx *c, double l, const double *z, double *f)
@@ -1836,25 +1811,21 @@ static int tri_host(gpmi_ctx *c, int model, double l, const double *Z, int k, in
     int rc;
     if ((rc = tri_check(c, model, l, Z, k, ldz, Fb, ldfb, F, ldf, Zb, ldzb, lbar, vjp))) return rc;
     const int n = model == TRI_GP ? c->igp_n : c->itp_n;
-    // F, Zbar and lbar lie side by side: the staged path brings them down with ONE copy into the pinned buffer (a null
-    // Fbar, F, Zbar or lbar keeps its slot and is not copied)
-    PinCall pc(c);
-    const size_t Z_ = pc.in(Z, n, k, ldz), Fb_ = pc.in(Fb, n, k, ldfb), F_ = pc.out(F, n, k, ldf), Zb_ = pc.out(Zb, n, k, ldzb),
-                 lb_ = pc.out(lbar, 1, 1, 1);
-    StageCall sc(c);
-    static_cast<HbCall &>(sc) = pc;   // the same slots in device memory
+    HostCall hc(c);
+    const size_t Z_ = hc.in(Z, n, k, ldz), Fb_ = hc.in(Fb, n, k, ldfb), F_ = hc.out(F, n, k, ldf), Zb_ = hc.out(Zb, n, k, ldzb),
+                 lb_ = hc.out(lbar, 1, 1, 1);
     const bool pinned = tri_vjp_one_launch(n, k);
-    if ((rc = pinned ? pc.pack() : sc.begin())) return rc;
-    double *d = pinned ? c->h_pin_dev : sc.d;
-    if ((rc = tri_core(c, model, l, d + Z_, k, n, vjp ? d + Fb_ : nullptr, n, F ? d + F_ : nullptr, n, vjp ? d + Zb_ : nullptr, n,
-                       vjp ? d + lb_ : nullptr)))
+    if ((rc = hc.begin(pinned ? HOST_PINNED : HOST_STAGED))) return rc;
+    if ((rc = tri_core(c, model, l, hc.dev(Z_), k, n, vjp ? hc.dev(Fb_) : nullptr, n, F ? hc.dev(F_) : nullptr, n,
+                       vjp ? hc.dev(Zb_) : nullptr, n, vjp ? hc.dev(lb_) : nullptr)))
         return rc;
-    if (!pinned) {
-        if ((rc = pin_reserve(c, pc.used * sizeof(double)))) return rc;
-        HIPCHK(hipMemcpyAsync(pc.host(F_), sc.dev(F_), (lb_ + 1 - F_) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
+    if (pinned) return hc.finish(false);
+    // F, Zbar and lbar lie side by side: the staged route brings them down with ONE copy into the pinned buffer instead of
+    // finish()'s copy per slot, and the CPU unpacks them (a null Fbar, F, Zbar or lbar keeps its slot and is not copied)
+    if ((rc = pin_reserve(c, hc.used * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(hc.host(F_), hc.dev(F_), (lb_ + 1 - F_) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    pc.unpack();
+    hc.unpack();
     return 0;
 }
 
@@ -2517,6 +2488,25 @@ static int logml_grad_core(gpmi_ctx *c, const double *dX, int n, int ldx, const 
     return grad_chain_core(c, SeGradModel{dX, n, ldx, dy, p, diag_add, d_res + 3}, d_res, d_info, many);
 }
 
+// one workgroup (k_logml_grad_small) up to n <= tune.small_ng1: the sizes the reference's fits run at
+static bool small_grad(const gpmi_ctx *c, int n, int D) { return c->tune.small_ng1 > 0 && n <= c->tune.small_ng1 && D <= GPMI_MAXD; }
+// doubles of the result record the route of (n, D) writes: the value triple, then the contraction sums
+static int grad_res_len(const gpmi_ctx *c, int n, int D) { return small_grad(c, n, D) ? GPMI_SMALL_GRAD_RES : GRAD_RES; }
+
+// One value + gradient evaluation on its route, ONE launch of one workgroup or the chain: the record to d_res (grad_res_len
+// doubles), the status to *d_info.  hl: the pinned transport of a host caller on the one-workgroup route, else null
+static int logml_grad_run(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
+                          double *d_res, int *d_info, const HostLink *hl)
+{
+    if (!small_grad(c, n, p.D)) return logml_grad_core(c, dX, n, ldx, dy, p, diag_add, d_res, d_info);
+    int rc;
+    if ((rc = reserve_ws_small(c, n, 2))) return rc;
+    const HostLink t = link_or_none(hl);
+    launch_logml_grad_small(c->stream, dX, n, ldx, dy, p, diag_add, c->W, d_res, d_info, c->d_info, t.scratch, t.flag, t.seq);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // host part: (d/dalpha, d/dell..., d/dsigma) from the contraction sums
 static void logml_grad_finish(const double *hs, int D, double alpha, const double *ell, int n_ell, double sigma, double *grad)
 {
@@ -2545,26 +2535,14 @@ extern "C" int gpmi_logml_grad(gpmi_ctx *c, const double *X, int n, int ldx, int
     SeParams p;
     int rc;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    if (c->tune.small_ng1 > 0 && n <= c->tune.small_ng1 && D <= GPMI_MAXD) {
-        // the sizes the reference's fits run at: ONE launch of one workgroup; X, y go in and the 13 results come back
-        // through a pinned, device-mapped buffer (no copy call), as in gpmi_logml
-        PinCall pc(c);
-        const size_t res_ = pc.mat(GPMI_SMALL_GRAD_RES), X_ = pc.in(X, n, D, ldx), y_ = pc.in(y, n, 1, n);
-        if ((rc = pc.begin((size_t)n * (D + 1), n, 2))) return rc;
-        launch_logml_grad_small(c->stream, pc.dev(X_), n, n, pc.dev(y_), p, sigma * sigma + jitter, c->W, pc.dev(res_), pc.info(),
-                                c->d_info, pc.stage, pc.flag(), pc.seq);
-        const int info = pc.finish();
-        if (info >= 0) logml_grad_unpack(pc.host(res_), info, D, alpha, ell, n_ell, sigma, out3, grad);
-        return info;
-    }
-    double *dX, *dy, *dres;
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = logml_grad_reserve(c, n, D))) return rc;
-    dres = c->d_fin + 4096;  // second half of the finalize scratch (64 KiB): GRAD_RES doubles
-    if ((rc = logml_grad_core(c, dX, n, n, dy, p, sigma * sigma + jitter, dres, c->d_info + 1))) return rc;
+    // the record comes back as one slot (on the one-workgroup route its 13 doubles, no copy call, as in gpmi_logml)
     double hr[GRAD_RES];
-    if ((rc = d2h_matrix(c, dres, GRAD_RES, GRAD_RES, 1, hr, GRAD_RES))) return rc;
-    const int info = staged_finish(c, c->d_info + 1);
+    const int len = grad_res_len(c, n, D);
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n), res_ = hc.out(hr, len, 1, len);
+    if ((rc = hc.begin(small_grad(c, n, D) ? HOST_PINNED : HOST_STAGED, (size_t)n * (D + 1)))) return rc;
+    if ((rc = logml_grad_run(c, hc.dev(X_), n, n, hc.dev(y_), p, sigma * sigma + jitter, hc.dev(res_), hc.info(), hc.link()))) return rc;
+    const int info = hc.finish();
     if (info >= 0) logml_grad_unpack(hr, info, D, alpha, ell, n_ell, sigma, out3, grad);
     return info;
 }
@@ -2693,16 +2671,35 @@ static int exact_gp_vjp_reserve(gpmi_ctx *c, int n, int D, int k)
     return scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &b);
 }
 
-// The chain, enqueued on c->stream: device X (ldx), Z (ldz), Fbar (ldfb); F (nullable, ldf), Zbar (ldzb), grad (1 + n_ell)
-// and *d_info written.  F is formed exactly as gpmi_exact_gp_f's blocked path forms it (same factorisation, same mat-vec).
+// one workgroup (k_exact_gp_vjp_small) up to n <= tune.small_vjp
+static bool small_vjp(const gpmi_ctx *c, int n, int D, int k)
+{
+    return c->tune.small_vjp > 0 && n <= c->tune.small_vjp && n <= 256 && D <= GPMI_MAXD && k <= GPMI_VJP_KMAX;
+}
+
+// Enqueued on c->stream, ONE launch of one workgroup (small_vjp) or the chain: device X (ldx), Z (ldz), Fbar (ldfb); F (nullable,
+// ldf), Zbar (ldzb), grad (1 + n_ell) and *d_info written.  F is formed exactly as gpmi_exact_gp_f's blocked path forms it (same
+// factorisation, same mat-vec).  hl: the pinned transport of a host caller on the one-workgroup route, else null.
 // head != nullptr (gpmi_latent_gp_lp_grad): Fbar is not read but produced, by the likelihood head on F, into dFbOut (nullable:
 // a workspace slice) and d_out[0..1] = (lik, d lik / d sigma); the launches of the plain call are the same with head == nullptr.
 static int exact_gp_vjp_core(gpmi_ctx *c, const double *dX, int n, int ldx, const SeParams &p, double alpha, const double *ell,
                              int n_ell, double jitter, const double *dZ, int k, int ldz, const double *dFb, int ldfb, double *dF,
-                             int ldf, double *dZb, int ldzb, double *d_grad, int *d_info, const LatentHead *head = nullptr,
-                             double *dFbOut = nullptr, double *d_out = nullptr)
+                             int ldf, double *dZb, int ldzb, double *d_grad, int *d_info, const HostLink *hl,
+                             const LatentHead *head = nullptr, double *dFbOut = nullptr, double *d_out = nullptr)
 {
     int rc;
+    if (small_vjp(c, n, p.D, k)) {
+        if ((rc = reserve_ws_small(c, n, 4))) return rc;
+        const HostLink t = link_or_none(hl);
+        if (head)
+            launch_latent_gp_small(c->stream, dX, n, ldx, p, jitter, dZ, k, ldz, *head, d_out, dFbOut, ldfb, dF, ldf, dZb, ldzb, c->W, alpha,
+                                   ell, n_ell, d_grad, d_info, c->d_info, t.scratch, t.flag, t.seq);
+        else
+            launch_exact_gp_vjp_small(c->stream, dX, n, ldx, p, jitter, dZ, k, ldz, dFb, ldfb, dF, ldf, dZb, ldzb, c->W, alpha, ell, n_ell,
+                                      d_grad, d_info, c->d_info, t.scratch, t.flag, t.seq);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if ((rc = exact_gp_vjp_reserve(c, n, p.D, k))) return rc;
     const size_t ld = (size_t)c->ld, ldu = (size_t)(((n + 15) / 16) * 16 + 16);
     const int nsch = (n + VJP_SCOLS - 1) / VJP_SCOLS, ns = grad_ns(p.D);
@@ -2765,12 +2762,6 @@ static int exact_gp_vjp_check(int n, int ldx, int D, double alpha, int k, int ld
     return 0;
 }
 
-// one workgroup (k_exact_gp_vjp_small) up to n <= tune.small_vjp
-static bool small_vjp(const gpmi_ctx *c, int n, int D, int k)
-{
-    return c->tune.small_vjp > 0 && n <= c->tune.small_vjp && n <= 256 && D <= GPMI_MAXD && k <= GPMI_VJP_KMAX;
-}
-
 extern "C" int gpmi_exact_gp_f_vjp_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
                                        double jitter, const double *dZ, int k, int ldz, const double *dFbar, int ldfb, double *dF, int ldf,
                                        double *dZbar, int ldzb, double *d_grad, int *d_info)
@@ -2781,14 +2772,8 @@ extern "C" int gpmi_exact_gp_f_vjp_dev(gpmi_ctx *c, const double *dX, int n, int
     if (!dX || !dZ || !dFbar || !dZbar || !d_grad || !d_info) return gpmi_fail(GPMI_EARG, "NULL pointer");
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    if (small_vjp(c, n, D, k)) {
-        if ((rc = reserve_ws_small(c, n, 4))) return rc;
-        launch_exact_gp_vjp_small(c->stream, dX, n, ldx, p, jitter, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, c->W, alpha, ell,
-                                  n_ell, d_grad, d_info, c->d_info, nullptr);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    return exact_gp_vjp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_grad, d_info);
+    return exact_gp_vjp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dZ, k, ldz, dFbar, ldfb, dF, ldf, dZbar, ldzb, d_grad, d_info,
+                             nullptr);
 }
 
 extern "C" int gpmi_exact_gp_f_vjp(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
@@ -2801,25 +2786,14 @@ extern "C" int gpmi_exact_gp_f_vjp(gpmi_ctx *c, const double *X, int n, int ldx,
     if (!X || !Z || !Fbar || !Zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    if (small_vjp(c, n, D, k)) {
-        // one launch of one workgroup; inputs in and results out through the pinned, device-mapped buffer
-        PinCall pc(c);
-        const size_t g_ = pc.out(grad, 1 + n_ell, 1, 1 + n_ell), F_ = pc.out(F, n, k, ldf), Zb_ = pc.out(Zbar, n, k, ldzb),
-                     X_ = pc.in(X, n, D, ldx), Z_ = pc.in(Z, n, k, ldz), Fb_ = pc.in(Fbar, n, k, ldfb);
-        if ((rc = pc.begin((size_t)n * (D + 2 * k), n, 4))) return rc;
-        launch_exact_gp_vjp_small(c->stream, pc.dev(X_), n, n, p, jitter, pc.dev(Z_), k, n, pc.dev(Fb_), n, F ? pc.dev(F_) : nullptr, n,
-                                  pc.dev(Zb_), n, c->W, alpha, ell, n_ell, pc.dev(g_), pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    // blocked chain, staged in device memory
-    StageCall sc(c);
-    const size_t X_ = sc.in(X, n, D, ldx), Z_ = sc.in(Z, n, k, ldz), Fb_ = sc.in(Fbar, n, k, ldfb), F_ = sc.out(F, n, k, ldf),
-                 Zb_ = sc.out(Zbar, n, k, ldzb), g_ = sc.out(grad, 1 + n_ell, 1, 1 + n_ell);
-    if ((rc = sc.begin())) return rc;
-    if ((rc = exact_gp_vjp_core(c, sc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, sc.dev(Z_), k, n, sc.dev(Fb_), n,
-                                F ? sc.dev(F_) : nullptr, n, sc.dev(Zb_), n, sc.dev(g_), sc.info())))
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), Z_ = hc.in(Z, n, k, ldz), Fb_ = hc.in(Fbar, n, k, ldfb), F_ = hc.out(F, n, k, ldf),
+                 Zb_ = hc.out(Zbar, n, k, ldzb), g_ = hc.out(grad, 1 + n_ell, 1, 1 + n_ell);
+    if ((rc = hc.begin(small_vjp(c, n, D, k) ? HOST_PINNED : HOST_STAGED, (size_t)n * (D + 2 * k)))) return rc;
+    if ((rc = exact_gp_vjp_core(c, hc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, hc.dev(Z_), k, n, hc.dev(Fb_), n,
+                                F ? hc.dev(F_) : nullptr, n, hc.dev(Zb_), n, hc.dev(g_), hc.info(), hc.link())))
         return rc;
-    return sc.finish(sc.info());
+    return hc.finish();
 }
 
 // ---- latent GP: forward product, likelihood head, its adjoint and the reverse sweep with ONE factorisation -------------------
@@ -2867,15 +2841,8 @@ extern "C" int gpmi_latent_gp_lp_grad_dev(gpmi_ctx *c, const double *dX, int n, 
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
     const LatentHead lh{family, dY, m, ldy, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-    if (small_vjp(c, n, D, k)) {
-        if ((rc = reserve_ws_small(c, n, 4))) return rc;
-        launch_latent_gp_small(c->stream, dX, n, ldx, p, jitter, dZ, k, ldz, lh, d_out, dFbar, ldfb, dF, ldf, dZbar, ldzb, c->W, alpha, ell,
-                               n_ell, d_grad, d_info, c->d_info, nullptr);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
     return exact_gp_vjp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dZ, k, ldz, nullptr, ldfb, dF, ldf, dZbar, ldzb, d_grad, d_info,
-                             &lh, dFbar, d_out);
+                             nullptr, &lh, dFbar, d_out);
 }
 
 extern "C" int gpmi_latent_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
@@ -2890,31 +2857,16 @@ extern "C" int gpmi_latent_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int l
     if (family == GPMI_LIK_BERNOULLI_LOGIT && (rc = bernoulli_y_check(Y, n, m, ldy))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    const double log_sigma = family == GPMI_LIK_NORMAL ? log(sigma) : 0.0;
-    if (small_vjp(c, n, D, k)) {
-        // one launch of one workgroup through the pinned, device-mapped buffer
-        PinCall pc(c);
-        const size_t out_ = pc.out(out, 2, 1, 2), g_ = pc.out(grad, 1 + n_ell, 1, 1 + n_ell), F_ = pc.out(F, n, k, ldf),
-                     Fb_ = pc.out(Fbar, n, k, ldfb), Zb_ = pc.out(Zbar, n, k, ldzb), X_ = pc.in(X, n, D, ldx), Z_ = pc.in(Z, n, k, ldz),
-                     Y_ = pc.in(Y, n, m, ldy);
-        if ((rc = pc.begin((size_t)n * (D + k + m), n, 4))) return rc;
-        const LatentHead lh{family, pc.dev(Y_), m, n, sigma, log_sigma};
-        launch_latent_gp_small(c->stream, pc.dev(X_), n, n, p, jitter, pc.dev(Z_), k, n, lh, pc.dev(out_), Fbar ? pc.dev(Fb_) : nullptr, n,
-                               F ? pc.dev(F_) : nullptr, n, pc.dev(Zb_), n, c->W, alpha, ell, n_ell, pc.dev(g_), pc.info(), c->d_info,
-                               pc.stage, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    // blocked chain, staged in device memory
-    StageCall sc(c);
-    const size_t X_ = sc.in(X, n, D, ldx), Z_ = sc.in(Z, n, k, ldz), Y_ = sc.in(Y, n, m, ldy), F_ = sc.out(F, n, k, ldf),
-                 Fb_ = sc.out(Fbar, n, k, ldfb), Zb_ = sc.out(Zbar, n, k, ldzb), g_ = sc.out(grad, 1 + n_ell, 1, 1 + n_ell),
-                 out_ = sc.out(out, 2, 1, 2);
-    if ((rc = sc.begin())) return rc;
-    const LatentHead lh{family, sc.dev(Y_), m, n, sigma, log_sigma};
-    if ((rc = exact_gp_vjp_core(c, sc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, sc.dev(Z_), k, n, nullptr, n, F ? sc.dev(F_) : nullptr,
-                                n, sc.dev(Zb_), n, sc.dev(g_), sc.info(), &lh, sc.dev(Fb_), sc.dev(out_))))
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), Z_ = hc.in(Z, n, k, ldz), Y_ = hc.in(Y, n, m, ldy), F_ = hc.out(F, n, k, ldf),
+                 Fb_ = hc.out(Fbar, n, k, ldfb), Zb_ = hc.out(Zbar, n, k, ldzb), g_ = hc.out(grad, 1 + n_ell, 1, 1 + n_ell),
+                 out_ = hc.out(out, 2, 1, 2);
+    if ((rc = hc.begin(small_vjp(c, n, D, k) ? HOST_PINNED : HOST_STAGED, (size_t)n * (D + k + m)))) return rc;
+    const LatentHead lh{family, hc.dev(Y_), m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if ((rc = exact_gp_vjp_core(c, hc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, hc.dev(Z_), k, n, nullptr, n, F ? hc.dev(F_) : nullptr,
+                                n, hc.dev(Zb_), n, hc.dev(g_), hc.info(), hc.link(), &lh, Fbar ? hc.dev(Fb_) : nullptr, hc.dev(out_))))
         return rc;
-    return sc.finish(sc.info());
+    return hc.finish();
 }
 
 // ---- centred latent GP: the k latent columns are parameters, the GP their prior (models/heteroscedastic_centered.stan:24-34) ----
@@ -3008,12 +2960,27 @@ static int centered_gp_reserve(gpmi_ctx *c, int n, int D, int k)
     return scratch_buf(c, (size_t)npan * GPMI_FPACK * sizeof(double), &b);
 }
 
-// The chain, enqueued on c->stream: device X (ldx), F (ldf), the head's Y; d_out (4), dFg (ldfg), d_grad (1 + n_ell), *d_info written
+// one workgroup (k_centered_gp_small) up to n <= tune.small_cen
+static bool small_cen(const gpmi_ctx *c, int n, int D, int k)
+{
+    return c->tune.small_cen > 0 && n <= c->tune.small_cen && n <= 256 && D <= GPMI_MAXD && k <= GPMI_CEN_KMAX;
+}
+
+// Enqueued on c->stream, ONE launch of one workgroup (small_cen) or the chain: device X (ldx), F (ldf), the head's Y; d_out (4),
+// dFg (ldfg), d_grad (1 + n_ell), *d_info written.  hl: the pinned transport of a host caller on the one-workgroup route, else null
 static int centered_gp_core(gpmi_ctx *c, const double *dX, int n, int ldx, const SeParams &p, double alpha, const double *ell, int n_ell,
                             double jitter, const double *dF, int k, int ldf, const LatentHead &lh, double *d_out, double *dFg, int ldfg,
-                            double *d_grad, int *d_info)
+                            double *d_grad, int *d_info, const HostLink *hl)
 {
     int rc;
+    if (small_cen(c, n, p.D, k)) {
+        if ((rc = reserve_ws_small(c, n + k - 1, 2))) return rc;
+        const HostLink t = link_or_none(hl);
+        launch_centered_gp_small(c->stream, dX, n, ldx, p, jitter, dF, k, ldf, lh, d_out, dFg, ldfg, c->W, alpha, ell, n_ell, d_grad, d_info,
+                                 c->d_info, t.scratch, t.flag, t.seq);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if ((rc = centered_gp_reserve(c, n, p.D, k))) return rc;
     const size_t ld = (size_t)c->ld, ldu = (size_t)(((n + 15) / 16) * 16 + 16);
     const int nchunk = (n + UMV_COLS - 1) / UMV_COLS, nslice = (n + 255) / 256, ns = grad_ns(p.D);
@@ -3062,12 +3029,6 @@ static int centered_check(int n, int ldx, int D, double alpha, int k, int ldf, i
     return lik_head_check(family, k, m, ldy, n, sigma, true);
 }
 
-// one workgroup (k_centered_gp_small) up to n <= tune.small_cen
-static bool small_cen(const gpmi_ctx *c, int n, int D, int k)
-{
-    return c->tune.small_cen > 0 && n <= c->tune.small_cen && n <= 256 && D <= GPMI_MAXD && k <= GPMI_CEN_KMAX;
-}
-
 extern "C" int gpmi_centered_gp_lp_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx, int D, double alpha, const double *ell,
                                             int n_ell, double jitter, const double *dF, int k, int ldf, int family, const double *dY, int m,
                                             int ldy, double sigma, double *d_out, double *dFgrad, int ldfg, double *d_grad, int *d_info)
@@ -3080,14 +3041,7 @@ extern "C" int gpmi_centered_gp_lp_grad_dev(gpmi_ctx *c, const double *dX, int n
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
     const LatentHead lh{family, head ? dY : nullptr, head ? m : 0, head ? ldy : 0, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-    if (small_cen(c, n, D, k)) {
-        if ((rc = reserve_ws_small(c, n + k - 1, 2))) return rc;
-        launch_centered_gp_small(c->stream, dX, n, ldx, p, jitter, dF, k, ldf, lh, d_out, dFgrad, ldfg, c->W, alpha, ell, n_ell, d_grad,
-                                 d_info, c->d_info, nullptr);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    return centered_gp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dF, k, ldf, lh, d_out, dFgrad, ldfg, d_grad, d_info);
+    return centered_gp_core(c, dX, n, ldx, p, alpha, ell, n_ell, jitter, dF, k, ldf, lh, d_out, dFgrad, ldfg, d_grad, d_info, nullptr);
 }
 
 extern "C" int gpmi_centered_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int ldx, int D, double alpha, const double *ell, int n_ell,
@@ -3103,28 +3057,15 @@ extern "C" int gpmi_centered_gp_lp_grad(gpmi_ctx *c, const double *X, int n, int
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
     if (!head) m = 0;
-    const double log_sigma = family == GPMI_LIK_NORMAL ? log(sigma) : 0.0;
-    if (small_cen(c, n, D, k)) {
-        // one launch of one workgroup through the pinned, device-mapped buffer
-        PinCall pc(c);
-        const size_t out_ = pc.out(out, 4, 1, 4), g_ = pc.out(grad, 1 + n_ell, 1, 1 + n_ell), Fg_ = pc.out(Fgrad, n, k, ldfg),
-                     X_ = pc.in(X, n, D, ldx), F_ = pc.in(F, n, k, ldf), Y_ = pc.in(Y, n, m, ldy);
-        if ((rc = pc.begin((size_t)n * (D + k + m), n + k - 1, 2))) return rc;
-        const LatentHead lh{family, head ? pc.dev(Y_) : nullptr, m, n, sigma, log_sigma};
-        launch_centered_gp_small(c->stream, pc.dev(X_), n, n, p, jitter, pc.dev(F_), k, n, lh, pc.dev(out_), pc.dev(Fg_), n, c->W, alpha,
-                                 ell, n_ell, pc.dev(g_), pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    // blocked chain, staged in device memory
-    StageCall sc(c);
-    const size_t X_ = sc.in(X, n, D, ldx), F_ = sc.in(F, n, k, ldf), Y_ = sc.in(Y, n, m, ldy), Fg_ = sc.out(Fgrad, n, k, ldfg),
-                 g_ = sc.out(grad, 1 + n_ell, 1, 1 + n_ell), out_ = sc.out(out, 4, 1, 4);
-    if ((rc = sc.begin())) return rc;
-    const LatentHead lh{family, head ? sc.dev(Y_) : nullptr, m, n, sigma, log_sigma};
-    if ((rc = centered_gp_core(c, sc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, sc.dev(F_), k, n, lh, sc.dev(out_), sc.dev(Fg_), n,
-                               sc.dev(g_), sc.info())))
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), F_ = hc.in(F, n, k, ldf), Y_ = hc.in(Y, n, m, ldy), Fg_ = hc.out(Fgrad, n, k, ldfg),
+                 g_ = hc.out(grad, 1 + n_ell, 1, 1 + n_ell), out_ = hc.out(out, 4, 1, 4);
+    if ((rc = hc.begin(small_cen(c, n, D, k) ? HOST_PINNED : HOST_STAGED, (size_t)n * (D + k + m)))) return rc;
+    const LatentHead lh{family, head ? hc.dev(Y_) : nullptr, m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if ((rc = centered_gp_core(c, hc.dev(X_), n, n, p, alpha, ell, n_ell, jitter, hc.dev(F_), k, n, lh, hc.dev(out_), hc.dev(Fg_), n,
+                               hc.dev(g_), hc.info(), hc.link())))
         return rc;
-    return sc.finish(sc.info());
+    return hc.finish();
 }
 
 // the G result records (stride doubles apart) and info words of a value + gradient grid -> out3 and grad, 3 per point
@@ -3166,15 +3107,17 @@ extern "C" int gpmi_logml_grad_grid(gpmi_ctx *c, const double *X, int n, int ldx
     if (D <= GPMI_MAXD && n <= (G >= 2 ? c->tune.small_ng : c->tune.small_ng1) && G <= 8) {
         // a sampler's handful of chains: ONE launch, X, y in and the results out through the pinned, device-mapped buffer
         // (no copy call, no stream synchronisation); one info word per point in a slot of their own
-        PinCall pc(c);
-        const size_t res_ = pc.mat(GPMI_SMALL_GRAD_RES, G), info_ = pc.mat((G + 1) / 2), X_ = pc.in(X, n, D, ldx), y_ = pc.in(y, n, 1, n);
-        if ((rc = pc.begin((size_t)G * n * (D + 1), n, 2 * G))) return rc;
+        HostCall hc(c);
+        const size_t res_ = hc.mat(GPMI_SMALL_GRAD_RES, G), info_ = hc.mat((G + 1) / 2), X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n);
+        if ((rc = hc.begin(HOST_PINNED, (size_t)G * n * (D + 1)))) return rc;
+        if ((rc = reserve_ws_small(c, n, 2 * G))) return rc;
         if ((rc = reserve_small_par(c, G))) return rc;
-        launch_logml_grad_small_batch(c->stream, pc.dev(X_), n, n, D, pc.dev(y_), alpha, rho, sigma, G, jitter, c->W, pc.dev(res_),
-                                      (int *)pc.dev(info_), c->d_sinfo, pc.stage, pc.flag(), pc.seq, c->d_ctr + 40);
-        if ((rc = pc.wait())) return rc;
-        memcpy(info, pc.host(info_), (size_t)G * sizeof(int));
-        grad_grid_unpack(pc.host(res_), GPMI_SMALL_GRAD_RES, info, G, D, alpha, rho, sigma, out3, grad);
+        const HostLink t = *hc.link();
+        launch_logml_grad_small_batch(c->stream, hc.dev(X_), n, n, D, hc.dev(y_), alpha, rho, sigma, G, jitter, c->W, hc.dev(res_),
+                                      (int *)hc.dev(info_), c->d_sinfo, t.scratch, t.flag, t.seq, c->d_ctr + 40);
+        if ((rc = hc.finish(false))) return rc;
+        memcpy(info, hc.host(info_), (size_t)G * sizeof(int));
+        grad_grid_unpack(hc.host(res_), GPMI_SMALL_GRAD_RES, info, G, D, alpha, rho, sigma, out3, grad);
         return 0;
     }
     if (D <= GPMI_MAXD && n <= (G >= 2 ? c->tune.small_ng : c->tune.small_ng1)) {
@@ -3234,16 +3177,9 @@ extern "C" int gpmi_logml_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx
     SeParams p;
     int rc;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    double *dres = c->d_fin + 4096;  // second half of the finalize scratch, as in gpmi_logml_grad
-    if (c->tune.small_ng1 > 0 && n <= c->tune.small_ng1 && D <= GPMI_MAXD) {
-        if ((rc = reserve_ws_small(c, n, 2))) return rc;
-        launch_logml_grad_small(c->stream, dX, n, ldx, dy, p, sigma * sigma + jitter, c->W, dres, d_info, c->d_info, nullptr);
-        launch_logml_grad_finish(c->stream, dres, GPMI_SMALL_GRAD_RES, d_info, 1, D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if ((rc = logml_grad_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dres, d_info))) return rc;
-    launch_logml_grad_finish(c->stream, dres, GRAD_RES, d_info, 1, D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
+    double *dres = c->d_fin + 4096;  // second half of the finalize scratch: GRAD_RES doubles
+    if ((rc = logml_grad_run(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dres, d_info, nullptr))) return rc;
+    launch_logml_grad_finish(c->stream, dres, grad_res_len(c, n, D), d_info, 1, D, n_ell, alpha, ell, sigma, nullptr, d_out3, d_grad);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -3261,8 +3197,8 @@ extern "C" int gpmi_logml_grad_dev(gpmi_ctx *c, const double *dX, int n, int ldx
 // and M are done; the augmented route has M in the top-left n x n block of W (L, no longer needed) and C in the rows n + 1 ..
 // of the columns 0 .. n - 1 (L^-T).  The vectors live behind the tile slots (and behind the mat-vec partials of the
 // three-chain route): a, b (2 n: the two columns of the contraction), u, sqrt v (n each), the tile partials of b
-// (loo_bpart_doubles), then mu, var, lpd of the host form (3 n).  Everything is written before it is read.
-static size_t loo_extra_doubles(int n) { return 7 * (size_t)n + loo_bpart_doubles(n); }
+// (loo_bpart_doubles).  Everything is written before it is read.
+static size_t loo_extra_doubles(int n) { return 4 * (size_t)n + loo_bpart_doubles(n); }
 static size_t loo_extra_offset(int n, size_t slots, bool aug)   // from the first tile slot
 {
     return slots + (aug ? 0 : (size_t)((n + UMV_COLS - 1) / UMV_COLS) * n);
@@ -3313,15 +3249,6 @@ static int logml_loo_reserve(gpmi_ctx *c, int n, int D, bool many = false)
     return grad_chain_reserve(c, n, grad_ns(D), T * (T + 1) / 2, many, loo_extra_doubles(n));
 }
 
-// the host form's mu, var, lpd (3 n doubles) once logml_loo_reserve has run
-static double *logml_loo_host_vectors(const gpmi_ctx *c, int n, int D, bool many = false)
-{
-    const bool aug = grad_augmented(c, n, many);
-    const size_t T = (size_t)((n + 63) / 64);
-    double *part = c->stage[3] + (aug ? 0 : 2 * (size_t)n) + GRAD_NS_MAX;
-    return part + loo_extra_offset(n, T * (T + 1) / 2 * grad_ns(D), aug) + 4 * (size_t)n + loo_bpart_doubles(n);
-}
-
 static int logml_loo_check(int n, int ldx, int D, double alpha, double sigma, bool ptrs)
 {
     if (n < 1 || ldx < n || D < 1 || D > GPMI_MAXD_BIG || !ptrs) return gpmi_fail(GPMI_EARG, "bad argument");
@@ -3370,27 +3297,23 @@ extern "C" int gpmi_logml_loo(gpmi_ctx *c, const double *X, int n, int ldx, int 
     if ((rc = logml_loo_check(n, ldx, D, alpha, sigma, X && y && out3 && loo))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    double *dX, *dy;
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = logml_loo_reserve(c, n, D))) return rc;
-    // the record: out3, the contraction sums, loo, grad
-    constexpr int LOO_RES = GRAD_RES + 1 + GRAD_NS_MAX;
-    double *dres = c->d_fin + 4096, *dv = logml_loo_host_vectors(c, n, D);
-    double *dmu = mu ? dv : nullptr, *dvar = var ? dv + n : nullptr, *dlpd = lpd ? dv + 2 * (size_t)n : nullptr;
-    if ((rc = logml_loo_core(c, dX, n, n, dy, p, alpha, ell, n_ell, sigma, jitter, dres, dres + GRAD_RES, dmu, dvar, dlpd,
-                             grad ? dres + GRAD_RES + 1 : nullptr, c->d_info + 1)))
+    // out3, loo and grad come down as ONE record; mu, var, lpd as slots of their own (null: none)
+    double hr[4 + GRAD_NS_MAX];
+    const int len = 4 + 2 + n_ell;
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n), rec_ = hc.out(hr, len, 1, len), mu_ = hc.out(mu, n, 1, n),
+                 var_ = hc.out(var, n, 1, n), lpd_ = hc.out(lpd, n, 1, n);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    double *rec = hc.dev(rec_);
+    if ((rc = logml_loo_core(c, hc.dev(X_), n, n, hc.dev(y_), p, alpha, ell, n_ell, sigma, jitter, rec, rec + 3, mu ? hc.dev(mu_) : nullptr,
+                             var ? hc.dev(var_) : nullptr, lpd ? hc.dev(lpd_) : nullptr, grad ? rec + 4 : nullptr, hc.info())))
         return rc;
-    double hr[LOO_RES];
-    if ((rc = d2h_matrix(c, dres, LOO_RES, LOO_RES, 1, hr, LOO_RES))) return rc;
-    if (mu && (rc = d2h_matrix(c, dmu, n, n, 1, mu, n))) return rc;
-    if (var && (rc = d2h_matrix(c, dvar, n, n, 1, var, n))) return rc;
-    if (lpd && (rc = d2h_matrix(c, dlpd, n, n, 1, lpd, n))) return rc;
-    const int info = staged_finish(c, c->d_info + 1);
+    const int info = hc.finish();
     if (info < 0) return info;
     for (int k = 0; k < 3; ++k) out3[k] = hr[k];
-    *loo = hr[GRAD_RES];
+    *loo = hr[3];
     if (grad)
-        for (int k = 0; k < 2 + n_ell; ++k) grad[k] = hr[GRAD_RES + 1 + k];
+        for (int k = 0; k < 2 + n_ell; ++k) grad[k] = hr[4 + k];
     return info;
 }
 
@@ -3404,16 +3327,7 @@ extern "C" int gpmi_logml_loo(gpmi_ctx *c, const double *X, int n, int ldx, int 
 static int hess_buf_reserve(gpmi_ctx *c, int n, int n_ell)
 {
     const size_t bytes = (hess_buf_doubles(n, n_ell) + 4096) * sizeof(double);   // slack for tile over-reads
-    if (bytes > c->hess_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->hess_buf) HIPCHK(hipFree(c->hess_buf));
-        c->hess_buf = nullptr;
-        c->hess_bytes = 0;
-        if (hipMalloc((void **)&c->hess_buf, bytes) != hipSuccess)
-            return gpmi_fail(GPMI_ENOMEM, "cannot allocate %zu bytes for the Hessian's matrices", bytes);
-        c->hess_bytes = bytes;
-    }
-    return 0;
+    return grow_dev(c, &c->hess_buf, &c->hess_bytes, bytes, "for the Hessian's matrices");
 }
 
 struct SeHessModel {
@@ -3496,18 +3410,17 @@ extern "C" int gpmi_logml_hess(gpmi_ctx *c, const double *X, int n, int ldx, int
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
     if ((rc = logml_hess_check_ell(n_ell, ldh))) return rc;
-    double *dX, *dy;
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = logml_hess_reserve(c, n, D, n_ell))) return rc;
-    // the record: out3, grad, hess (packed)
+    // out3, grad and hess (packed) come down as ONE record
     constexpr int QMAX = 2 + GPMI_MAXD;
     const int q = 2 + n_ell, len = 3 + q + q * q;
-    double *rec = hess_record(c->hess_buf, n, n_ell);
-    if ((rc = logml_hess_core(c, dX, n, n, dy, p, alpha, ell, n_ell, sigma, jitter, rec, rec + 3, rec + 3 + q, q, c->d_info + 1)))
-        return rc;
     double hr[3 + QMAX + QMAX * QMAX];
-    if ((rc = d2h_matrix(c, rec, len, len, 1, hr, len))) return rc;
-    const int info = staged_finish(c, c->d_info + 1);
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n), rec_ = hc.out(hr, len, 1, len);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    double *rec = hc.dev(rec_);
+    if ((rc = logml_hess_core(c, hc.dev(X_), n, n, hc.dev(y_), p, alpha, ell, n_ell, sigma, jitter, rec, rec + 3, rec + 3 + q, q, hc.info())))
+        return rc;
+    const int info = hc.finish();
     if (info < 0) return info;
     for (int k = 0; k < 3; ++k) out3[k] = hr[k];
     if (grad)
@@ -3724,14 +3637,13 @@ extern "C" int gpmi_joint_logml_grad(gpmi_ctx *c, const double *t, int n, const 
     int rc;
     if ((rc = joint_grad_check(n, alpha, l))) return rc;
     if (!t || !yy || !out3 || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
-    double *dt, *dyy;
-    if ((rc = upload_joint(c, t, n, yy, &dt, &dyy))) return rc;
-    if ((rc = joint_logml_grad_reserve(c, n))) return rc;
-    double *dres = c->d_fin + 4096;  // second half of the finalize scratch: out3, then the gradient
-    if ((rc = joint_logml_grad_core(c, dt, n, dyy, alpha, l, sigma, jitter, dres, dres + 3, c->d_info + 1))) return rc;
-    double hr[6];
-    if ((rc = d2h_matrix(c, dres, 6, 6, 1, hr, 6))) return rc;
-    const int info = staged_finish(c, c->d_info + 1);
+    double hr[6];   // out3, then the gradient: ONE record
+    HostCall hc(c);
+    const size_t t_ = hc.in(t, n, 1, n), yy_ = hc.in(yy, 2 * n, 1, 2 * n), res_ = hc.out(hr, 6, 1, 6);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    if ((rc = joint_logml_grad_core(c, hc.dev(t_), n, hc.dev(yy_), alpha, l, sigma, jitter, hc.dev(res_), hc.dev(res_) + 3, hc.info())))
+        return rc;
+    const int info = hc.finish();
     if (info >= 0) {
         for (int k = 0; k < 3; ++k) out3[k] = hr[k], grad[k] = hr[3 + k];
     }
@@ -3774,6 +3686,44 @@ extern "C" int gpmi_joint_logml_grad_grid(gpmi_ctx *c, const double *t, int n, c
 }
 
 // ---- GP posterior ---------------------------------------------------------------
+// one workgroup (k_gp_condition_small) up to n + m + 1 <= tune.small_gc: the sizes of R/tests.R
+static bool small_condition(const gpmi_ctx *c, int n, int m) { return c->tune.small_gc > 0 && n + m + 1 <= c->tune.small_gc; }
+
+// device (one workgroup: or host-mapped) t, ts, y; mn (m), Kn (m x m, packed) and *d_info written; enqueues on c->stream
+static int gp_condition_run(gpmi_ctx *c, const double *dt, int n, const double *dts, int m, const double *dy, double a2, double l,
+                            double s2, double jitter, int kindK, int kindS, int kindSS, int compat, double *d_mn, double *dKn, int *d_info,
+                            const HostLink *hl)
+{
+    int rc;
+    hipStream_t s = c->stream;
+    const int nt = n + m, M = nt + 1;
+    if (small_condition(c, n, m)) {   // ONE launch of one workgroup
+        if ((rc = reserve_ws_small(c, nt, 1))) return rc;
+        const HostLink t = link_or_none(hl);
+        launch_gp_condition_small(s, dt, n, dts, m, dy, kindK, kindS, kindSS, compat, a2, l * l, s2, jitter, c->W, dKn, (size_t)m, d_mn,
+                                  d_info, c->d_info, t.scratch, t.flag, t.seq);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    if ((rc = reserve_ws(c, M, nt))) return rc;
+    const size_t ld = (size_t)c->ld;
+    HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int), s));
+    // [[K + s2 I, .], [Ks, Kss]] lower-stored, then the row [y^T, 0]
+    launch_deriv_cov(s, kindK, dt, n, dt, n, a2, l, compat, 1, c->W, ld);
+    launch_add_diag(s, c->W, ld, n, s2);
+    launch_deriv_cov(s, kindS, dts, m, dt, n, a2, l, compat, 0, c->W + n, ld);
+    launch_deriv_cov(s, kindSS, dts, m, dts, m, a2, l, compat, 1, c->W + n + (size_t)n * ld, ld);
+    launch_set_row(s, c->W, ld, nt, dy, n, nt);
+    // factor the first n columns: rows n.. become Ks L^-T, the trailing block the Schur
+    // complement Kss - Ks (K+s2 I)^-1 Ks^T, the last row [z^T, -mn^T]
+    if ((rc = launch_potrf_partial(c, c->W, ld, M, nt, n, d_info, nullptr))) return rc;
+    launch_copy_matrix(s, c->W + n + (size_t)n * ld, ld, dKn, (size_t)m, m, m, 2);
+    launch_add_diag(s, dKn, (size_t)m, m, jitter);
+    launch_get_row(s, c->W, ld, nt, n, m, -1.0, d_mn);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int gpmi_gp_condition(gpmi_ctx *c, const double *t, int n, const double *ts, int m,
                                  const double *y, double alpha, double l, double s2, double jitter,
                                  int kindK, int kindS, int kindSS, int flags, double *mn, double *Kn, int ldkn)
@@ -3784,51 +3734,14 @@ extern "C" int gpmi_gp_condition(gpmi_ctx *c, const double *t, int n, const doub
     if (kindK < 0 || kindK > GPMI_TT || kindS < 0 || kindS > GPMI_TT || kindSS < 0 || kindSS > GPMI_TT)
         return gpmi_fail(GPMI_EARG, "bad kernel kind");
     int rc;
-    const int nt = n + m, M = nt + 1;
-    if (c->tune.small_gc > 0 && M <= c->tune.small_gc) {
-        // R/tests.R sizes: ONE launch of one workgroup; t, ts, y go in and mn, Kn, info come back through the pinned,
-        // device-mapped buffer (no copy call)
-        PinCall pc(c);
-        const size_t mn_ = pc.out(mn, m, 1, m), Kn_ = pc.out(Kn, m, m, ldkn), t_ = pc.in(t, n, 1, n), ts_ = pc.in(ts, m, 1, m),
-                     y_ = pc.in(y, n, 1, n);
-        if ((rc = pc.begin(2 * (size_t)n + m, nt, 1))) return rc;
-        launch_gp_condition_small(c->stream, pc.dev(t_), n, pc.dev(ts_), m, pc.dev(y_), kindK, kindS, kindSS,
-                                  (flags & GPMI_COMPAT_RR) ? 1 : 0, alpha * alpha, l * l, s2, jitter, c->W, pc.dev(Kn_), (size_t)m,
-                                  pc.dev(mn_), pc.info(), c->d_info, pc.stage, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    if ((rc = reserve_ws(c, M, nt))) return rc;
-    const size_t ld = (size_t)c->ld;
-    double *dt, *dts, *dy, *dKn;
-    if ((rc = stage_buf(c, 0, (size_t)(n + m) * sizeof(double), &dt))) return rc;
-    dts = dt + n;
-    if ((rc = stage_buf(c, 1, (size_t)n * sizeof(double), &dy))) return rc;
-    const int ldo = (m + 1) & ~1;
-    if ((rc = stage_buf(c, 2, (size_t)ldo * (m + 1) * sizeof(double), &dKn))) return rc;
-    hipStream_t s = c->stream;
-    if ((rc = h2d_matrix(c, t, n, 1, n, dt))) return rc;
-    if ((rc = h2d_matrix(c, ts, m, 1, m, dts))) return rc;
-    if ((rc = h2d_matrix(c, y, n, 1, n, dy))) return rc;
-    HIPCHK(hipMemsetAsync(c->d_info, 0, sizeof(int), s));
-    const double a2 = alpha * alpha;
-    const int compat = (flags & GPMI_COMPAT_RR) ? 1 : 0;
-    // [[K + s2 I, .], [Ks, Kss]] lower-stored, then the row [y^T, 0]
-    launch_deriv_cov(s, kindK, dt, n, dt, n, a2, l, compat, 1, c->W, ld);
-    launch_add_diag(s, c->W, ld, n, s2);
-    launch_deriv_cov(s, kindS, dts, m, dt, n, a2, l, compat, 0, c->W + n, ld);
-    launch_deriv_cov(s, kindSS, dts, m, dts, m, a2, l, compat, 1, c->W + n + (size_t)n * ld, ld);
-    launch_set_row(s, c->W, ld, nt, dy, n, nt);
-    // factor the first n columns: rows n.. become Ks L^-T, the trailing block the Schur
-    // complement Kss - Ks (K+s2 I)^-1 Ks^T, the last row [z^T, -mn^T]
-    if ((rc = launch_potrf_partial(c, c->W, ld, M, nt, n, c->d_info, nullptr))) return rc;
-    launch_copy_matrix(s, c->W + n + (size_t)n * ld, ld, dKn, (size_t)ldo, m, m, 2);
-    launch_add_diag(s, dKn, (size_t)ldo, m, jitter);
-    double *dmn = dKn + (size_t)ldo * m;  // spare column of the output staging
-    launch_get_row(s, c->W, ld, nt, n, m, -1.0, dmn);
-    HIPCHK(hipGetLastError());
-    if ((rc = d2h_matrix(c, dKn, (size_t)ldo, m, m, Kn, ldkn))) return rc;
-    if ((rc = d2h_matrix(c, dmn, (size_t)m, m, 1, mn, m))) return rc;
-    return staged_finish(c, c->d_info);
+    HostCall hc(c);
+    const size_t t_ = hc.in(t, n, 1, n), ts_ = hc.in(ts, m, 1, m), y_ = hc.in(y, n, 1, n), mn_ = hc.out(mn, m, 1, m),
+                 Kn_ = hc.out(Kn, m, m, ldkn);
+    if ((rc = hc.begin(small_condition(c, n, m) ? HOST_PINNED : HOST_STAGED, 2 * (size_t)n + m))) return rc;
+    if ((rc = gp_condition_run(c, hc.dev(t_), n, hc.dev(ts_), m, hc.dev(y_), alpha * alpha, l, s2, jitter, kindK, kindS, kindSS,
+                               (flags & GPMI_COMPAT_RR) ? 1 : 0, hc.dev(mn_), hc.dev(Kn_), hc.info(), hc.link())))
+        return rc;
+    return hc.finish();
 }
 
 // ---- GP posterior at new D-dimensional inputs: pointwise mean and variance ---------------------------
@@ -3863,14 +3776,16 @@ static int predict_check(int n, int ldx, int D, double alpha, double sigma, int 
     return 0;
 }
 
+// hl: the pinned transport of a host caller on the one-workgroup route (each input is read once: its scratch is not used), else null
 static int predict_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
-                        const double *dXs, int m, int ldxs, double *d_mean, double *d_var, int *d_info)
+                        const double *dXs, int m, int ldxs, double *d_mean, double *d_var, int *d_info, const HostLink *hl)
 {
     int rc;
     hipStream_t s = c->stream;
     if (small_predict(c, n, m, p.D)) {
         if ((rc = reserve_ws_small(c, n + m, 1))) return rc;
-        launch_gp_predict_small(s, dX, n, ldx, dXs, m, ldxs, dy, p, diag_add, c->W, d_mean, d_var, d_info, c->d_info);
+        const HostLink t = link_or_none(hl);
+        launch_gp_predict_small(s, dX, n, ldx, dXs, m, ldxs, dy, p, diag_add, c->W, d_mean, d_var, d_info, c->d_info, t.flag, t.seq);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -3915,7 +3830,7 @@ extern "C" int gpmi_gp_predict_dev(gpmi_ctx *c, const double *dX, int n, int ldx
     if ((rc = predict_check(n, ldx, D, alpha, sigma, m, ldxs))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    return predict_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dXs, m, ldxs, d_mean, d_var, d_info);
+    return predict_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dXs, m, ldxs, d_mean, d_var, d_info, nullptr);
 }
 
 extern "C" int gpmi_gp_predict(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double alpha, const double *ell,
@@ -3927,27 +3842,15 @@ extern "C" int gpmi_gp_predict(gpmi_ctx *c, const double *X, int n, int ldx, int
     if ((rc = predict_check(n, ldx, D, alpha, sigma, m, ldxs))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    const double diag_add = sigma * sigma + jitter;
-    if (small_predict(c, n, m, D)) {
-        // the reference's sizes: ONE launch; X, Xs, y go in and mean, var, info come back through the pinned, device-mapped
-        // buffer (no copy call; each input is read once: no staging scratch)
-        PinCall pc(c);
-        const size_t mean_ = pc.out(mean, m, 1, m), var_ = pc.out(var, m, 1, m), X_ = pc.in(X, n, D, ldx), Xs_ = pc.in(Xs, m, D, ldxs),
-                     y_ = pc.in(y, n, 1, n);
-        if ((rc = pc.begin(0, n + m, 1))) return rc;
-        launch_gp_predict_small(c->stream, pc.dev(X_), n, n, pc.dev(Xs_), m, m, pc.dev(y_), p, diag_add, c->W, pc.dev(mean_),
-                                var ? pc.dev(var_) : nullptr, pc.info(), c->d_info, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    // the chain: Xs, mean and var in staging buffer 3 (X and y in 0 and 1, the core's own in 2)
-    StageCall sc(c);
-    const size_t Xs_ = sc.in(Xs, m, D, ldxs), mean_ = sc.out(mean, m, 1, m), var_ = sc.out(var, m, 1, m);
-    double *dX, *dy;
-    if ((rc = sc.begin(3))) return rc;
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = predict_core(c, dX, n, n, dy, p, diag_add, sc.dev(Xs_), m, m, sc.dev(mean_), var ? sc.dev(var_) : nullptr, c->d_info + 1)))
+    // (the one-workgroup kernel reads each input once: no staging scratch)
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n), Xs_ = hc.in(Xs, m, D, ldxs), mean_ = hc.out(mean, m, 1, m),
+                 var_ = hc.out(var, m, 1, m);
+    if ((rc = hc.begin(small_predict(c, n, m, D) ? HOST_PINNED : HOST_STAGED))) return rc;
+    if ((rc = predict_core(c, hc.dev(X_), n, n, hc.dev(y_), p, sigma * sigma + jitter, hc.dev(Xs_), m, m, hc.dev(mean_),
+                           var ? hc.dev(var_) : nullptr, hc.info(), hc.link())))
         return rc;
-    return sc.finish(c->d_info + 1);
+    return hc.finish();
 }
 
 // ---- sample_derivs: one draw of the derivative process, fused on the device --------------------
@@ -4046,19 +3949,19 @@ extern "C" int gpmi_sample_derivs(gpmi_ctx *c, const double *t, int n, const dou
     if (n <= 0 || m <= 0 || !t || !ts || !y || !z || !draw || !(l > 0.0)) return gpmi_fail(GPMI_EARG, "bad argument");
     int rc;
     if ((rc = sample_derivs_reserve(c, n, m))) return rc;
-    StageCall sc(c);
-    const size_t t_ = sc.in(t, n, 1, n), y_ = sc.in(y, n, 1, n), ts_ = sc.in(ts, m, 1, m), z_ = sc.in(z, m, 1, m),
-                 draw_ = sc.out(draw, m, 1, m), mu_ = sc.out(mu, m, 1, m);
-    if ((rc = sc.begin())) return rc;
+    HostCall hc(c);
+    const size_t t_ = hc.in(t, n, 1, n), y_ = hc.in(y, n, 1, n), ts_ = hc.in(ts, m, 1, m), z_ = hc.in(z, m, 1, m),
+                 draw_ = hc.out(draw, m, 1, m), mu_ = hc.out(mu, m, 1, m);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
     if (small_sample_derivs(c, n, m, 1)) {   // small enough that one workgroup beats the launch chain even for ONE draw
         const double par[3] = {l, a, sy};
-        if ((rc = sample_derivs_small(c, sc.dev(t_), n, sc.dev(ts_), m, sc.dev(y_), par, 1, jitter, sc.dev(z_), sc.dev(draw_), sc.dev(mu_),
-                                      sc.info())))
+        if ((rc = sample_derivs_small(c, hc.dev(t_), n, hc.dev(ts_), m, hc.dev(y_), par, 1, jitter, hc.dev(z_), hc.dev(draw_), hc.dev(mu_),
+                                      hc.info())))
             return rc;
-    } else if ((rc = sample_derivs_core(c, sc.dev(t_), n, sc.dev(ts_), m, sc.dev(y_), a, l, sy * sy, jitter, sc.dev(z_), sc.dev(draw_),
-                                        sc.dev(mu_), sc.info())))
+    } else if ((rc = sample_derivs_core(c, hc.dev(t_), n, hc.dev(ts_), m, hc.dev(y_), a, l, sy * sy, jitter, hc.dev(z_), hc.dev(draw_),
+                                        hc.dev(mu_), hc.info())))
         return rc;
-    return sc.finish(sc.info());
+    return hc.finish();
 }
 
 // B independent draws, draw b from (params[3 b .. 3 b + 2] = (l, a, sy), Y[:, b], Z[:, b]): the loop
@@ -4079,12 +3982,12 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
     const bool small = small_sample_derivs(c, n, m, B);
     LaneFan fan(c);
     if (!small && (rc = fan.prepare(B, false, [&](gpmi_ctx *lc) { return sample_derivs_reserve(lc, n, m); }))) return rc;
-    StageCall sc(c);
-    const size_t t_ = sc.in(t, n, 1, n), ts_ = sc.in(ts, m, 1, m), Y_ = sc.in(Y, n, B, ldy), Z_ = sc.in(Z, m, B, ldz),
-                 D_ = sc.out(draws, m, B, ldd), M_ = sc.out(mus, m, B, ldmu), st_ = sc.mat((B + 1) / 2);   // one status word per draw
-    if ((rc = sc.begin())) return rc;
-    double *dt = sc.dev(t_), *dts = sc.dev(ts_), *dY = sc.dev(Y_), *dZ = sc.dev(Z_), *dD = sc.dev(D_), *dM = sc.dev(M_);
-    int *dst = (int *)sc.dev(st_);
+    HostCall hc(c);
+    const size_t t_ = hc.in(t, n, 1, n), ts_ = hc.in(ts, m, 1, m), Y_ = hc.in(Y, n, B, ldy), Z_ = hc.in(Z, m, B, ldz),
+                 D_ = hc.out(draws, m, B, ldd), M_ = hc.out(mus, m, B, ldmu), st_ = hc.mat((B + 1) / 2);   // one status word per draw
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    double *dt = hc.dev(t_), *dts = hc.dev(ts_), *dY = hc.dev(Y_), *dZ = hc.dev(Z_), *dD = hc.dev(D_), *dM = hc.dev(M_);
+    int *dst = (int *)hc.dev(st_);
     hipStream_t const caller = c->stream;
     if (small) {
         if ((rc = sample_derivs_small(c, dt, n, dts, m, dY, params, B, jitter, dZ, dD, dM, dst))) return rc;
@@ -4097,7 +4000,7 @@ extern "C" int gpmi_sample_derivs_batch(gpmi_ctx *c, const double *t, int n, con
         if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(info, dst, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, caller));
-    if ((rc = sc.finish(nullptr))) return rc;   // (one status word per draw, copied above)
+    if ((rc = hc.finish(false))) return rc;   // (one status word per draw, copied above)
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -4134,17 +4037,19 @@ static int predict_joint_reserve(gpmi_ctx *c, int n, int m, int D)
     return reserve_ws(c, n + m + 1, n + m);
 }
 
-// all pointers device; d_cov nullable; dZ / d_draws unused when B == 0; enqueues on c->stream, no synchronisation
+// all pointers device; d_cov nullable; dZ / d_draws unused when B == 0; enqueues on c->stream, no synchronisation.  hl: the pinned
+// transport of a host caller on the one-workgroup route (every pointer host-mapped, each input read once), else null
 static int predict_joint_core(gpmi_ctx *c, const double *dX, int n, int ldx, const double *dy, const SeParams &p, double diag_add,
                               const double *dXs, int m, int ldxs, double post_jitter, double *d_mean, double *d_cov, int ldc,
-                              const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info)
+                              const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info, const HostLink *hl)
 {
     int rc;
     hipStream_t s = c->stream;
     if ((rc = predict_joint_reserve(c, n, m, p.D))) return rc;
     if (small_predict_joint(c, n, m, p.D)) {
+        const HostLink t = link_or_none(hl);
         launch_gp_predict_joint_wg(s, dX, n, ldx, dXs, m, ldxs, dy, p, diag_add, post_jitter, c->W, d_mean, d_cov, (size_t)ldc, dZ, B,
-                                   (size_t)ldz, d_draws, (size_t)ldd, d_info, c->d_info + 2);
+                                   (size_t)ldz, d_draws, (size_t)ldd, d_info, c->d_info + 2, t.flag, t.seq);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -4180,7 +4085,7 @@ extern "C" int gpmi_gp_predict_joint_dev(gpmi_ctx *c, const double *dX, int n, i
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
     return predict_joint_core(c, dX, n, ldx, dy, p, sigma * sigma + jitter, dXs, m, ldxs, post_jitter, d_mean, d_cov, ldc, dZ, B, ldz,
-                              d_draws, ldd, d_info);
+                              d_draws, ldd, d_info, nullptr);
 }
 
 extern "C" int gpmi_gp_predict_joint(gpmi_ctx *c, const double *X, int n, int ldx, int D, const double *y, double alpha,
@@ -4194,31 +4099,16 @@ extern "C" int gpmi_gp_predict_joint(gpmi_ctx *c, const double *X, int n, int ld
     if ((rc = predict_joint_check(n, ldx, D, alpha, sigma, m, ldxs, cov != nullptr, ldc, B, ldz, ldd))) return rc;
     SeParams p;
     if ((rc = fill_params(&p, D, alpha, ell, n_ell))) return rc;
-    const double diag_add = sigma * sigma + jitter;
-    if (small_predict_joint(c, n, m, D)) {
-        // ONE launch: inputs and results travel through the pinned, device-mapped buffer (each input is read once)
-        PinCall pc(c);
-        const size_t mean_ = pc.out(mean, m, 1, m), cov_ = cov ? pc.out(cov, m, m, ldc) : 0, draws_ = B ? pc.out(draws, m, B, ldd) : 0,
-                     X_ = pc.in(X, n, D, ldx), Xs_ = pc.in(Xs, m, D, ldxs), y_ = pc.in(y, n, 1, n), Z_ = B ? pc.in(Z, m, B, ldz) : 0;
-        if ((rc = pc.begin(0, n + m, 1))) return rc;
-        launch_gp_predict_joint_wg(c->stream, pc.dev(X_), n, n, pc.dev(Xs_), m, m, pc.dev(y_), p, diag_add, post_jitter, c->W,
-                                   pc.dev(mean_), cov ? pc.dev(cov_) : nullptr, (size_t)m, B ? pc.dev(Z_) : nullptr, B, (size_t)m,
-                                   B ? pc.dev(draws_) : nullptr, (size_t)m, pc.info(), c->d_info + 2, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    // the chain: Xs, Z and the results in staging buffer 3 (X and y in 0 and 1); cov == NULL: no m x m staging either
-    if ((rc = predict_joint_reserve(c, n, m, D))) return rc;
-    StageCall sc(c);
-    const size_t Xs_ = sc.in(Xs, m, D, ldxs), Z_ = B ? sc.in(Z, m, B, ldz) : 0, mean_ = sc.out(mean, m, 1, m),
-                 cov_ = cov ? sc.out(cov, m, m, ldc) : 0, draws_ = B ? sc.out(draws, m, B, ldd) : 0;
-    double *dX, *dy;
-    if ((rc = sc.begin(3))) return rc;
-    if ((rc = upload_xy(c, X, n, ldx, D, y, &dX, &dy))) return rc;
-    if ((rc = predict_joint_core(c, dX, n, n, dy, p, diag_add, sc.dev(Xs_), m, m, post_jitter, sc.dev(mean_),
-                                 cov ? sc.dev(cov_) : nullptr, m, B ? sc.dev(Z_) : nullptr, B, m, B ? sc.dev(draws_) : nullptr, m,
-                                 c->d_info + 1)))
+    // cov == NULL or B == 0: no m x m or m x B slot either
+    HostCall hc(c);
+    const size_t X_ = hc.in(X, n, D, ldx), y_ = hc.in(y, n, 1, n), Xs_ = hc.in(Xs, m, D, ldxs), Z_ = B ? hc.in(Z, m, B, ldz) : 0,
+                 mean_ = hc.out(mean, m, 1, m), cov_ = cov ? hc.out(cov, m, m, ldc) : 0, draws_ = B ? hc.out(draws, m, B, ldd) : 0;
+    if ((rc = hc.begin(small_predict_joint(c, n, m, D) ? HOST_PINNED : HOST_STAGED))) return rc;
+    if ((rc = predict_joint_core(c, hc.dev(X_), n, n, hc.dev(y_), p, sigma * sigma + jitter, hc.dev(Xs_), m, m, post_jitter, hc.dev(mean_),
+                                 cov ? hc.dev(cov_) : nullptr, m, B ? hc.dev(Z_) : nullptr, B, m, B ? hc.dev(draws_) : nullptr, m,
+                                 hc.info(), hc.link())))
         return rc;
-    return sc.finish(c->d_info + 1);
+    return hc.finish();
 }
 
 // ---- prediction for the joint [y; y'] model: f, f', f'' at new times given both series ---------------------------------
@@ -4258,18 +4148,21 @@ static int joint_predict_reserve(gpmi_ctx *c, int n, int m, int p)
     return reserve_ws(c, 2 * n + p * m + 1, 2 * n + p * m);
 }
 
-// all pointers device but post_jitter (host, p values); d_cov nullable; dZ / d_draws unused when B == 0; enqueues on c->stream
+// all pointers device but post_jitter (host, p values); d_cov nullable; dZ / d_draws unused when B == 0; enqueues on c->stream.
+// hl: as in predict_joint_core
 static int joint_predict_core(gpmi_ctx *c, const double *dt, int n, const double *dyy, double alpha, double l, double sigma,
                               double jitter, const double *dts, int m, int orders, const double *post_jitter, double *d_mean,
-                              double *d_cov, int ldc, const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info)
+                              double *d_cov, int ldc, const double *dZ, int B, int ldz, double *d_draws, int ldd, int *d_info,
+                              const HostLink *hl)
 {
     int rc;
     hipStream_t s = c->stream;
     const int p = __builtin_popcount(orders), n2 = 2 * n, pm = p * m;
     if ((rc = joint_predict_reserve(c, n, m, p))) return rc;
     if (small_joint_predict(c, n, m, p)) {
+        const HostLink t = link_or_none(hl);
         launch_joint_predict_wg(s, dt, n, dts, m, dyy, alpha * alpha, l, sigma * sigma, jitter, orders, post_jitter, c->W, d_mean, d_cov,
-                                (size_t)ldc, dZ, B, (size_t)ldz, d_draws, (size_t)ldd, d_info, c->d_info + 2);
+                                (size_t)ldc, dZ, B, (size_t)ldz, d_draws, (size_t)ldd, d_info, c->d_info + 2, t.flag, t.seq);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -4301,7 +4194,7 @@ extern "C" int gpmi_joint_predict_dev(gpmi_ctx *c, const double *dt, int n, cons
     int rc;
     if ((rc = joint_predict_check(n, alpha, l, sigma, m, orders, post_jitter, d_cov != nullptr, ldc, B, ldz, ldd))) return rc;
     return joint_predict_core(c, dt, n, dyy, alpha, l, sigma, jitter, dts, m, orders, post_jitter, d_mean, d_cov, ldc, dZ, B, ldz,
-                              d_draws, ldd, d_info);
+                              d_draws, ldd, d_info, nullptr);
 }
 
 extern "C" int gpmi_joint_predict(gpmi_ctx *c, const double *t, int n, const double *yy, double alpha, double l, double sigma,
@@ -4313,28 +4206,16 @@ extern "C" int gpmi_joint_predict(gpmi_ctx *c, const double *t, int n, const dou
     int rc;
     if ((rc = joint_predict_check(n, alpha, l, sigma, m, orders, post_jitter, cov != nullptr, ldc, B, ldz, ldd))) return rc;
     const int p = __builtin_popcount(orders), pm = p * m;
-    if (small_joint_predict(c, n, m, p)) {
-        // ONE launch: inputs and results travel through the pinned, device-mapped buffer (each input is read once)
-        PinCall pc(c);
-        const size_t mean_ = pc.out(mean, pm, 1, pm), cov_ = cov ? pc.out(cov, pm, pm, ldc) : 0, draws_ = B ? pc.out(draws, pm, B, ldd) : 0,
-                     t_ = pc.in(t, n, 1, n), ts_ = pc.in(ts, m, 1, m), yy_ = pc.in(yy, 2 * n, 1, 2 * n), Z_ = B ? pc.in(Z, pm, B, ldz) : 0;
-        if ((rc = pc.begin(0, 2 * n + pm, 1))) return rc;
-        launch_joint_predict_wg(c->stream, pc.dev(t_), n, pc.dev(ts_), m, pc.dev(yy_), alpha * alpha, l, sigma * sigma, jitter, orders,
-                                post_jitter, c->W, pc.dev(mean_), cov ? pc.dev(cov_) : nullptr, (size_t)pm, B ? pc.dev(Z_) : nullptr, B,
-                                (size_t)pm, B ? pc.dev(draws_) : nullptr, (size_t)pm, pc.info(), c->d_info + 2, pc.flag(), pc.seq);
-        return pc.finish();
-    }
-    // the chain: inputs and results in staging buffer 0; cov == NULL: no p m x p m staging either
-    if ((rc = joint_predict_reserve(c, n, m, p))) return rc;
-    StageCall sc(c);
-    const size_t t_ = sc.in(t, n, 1, n), ts_ = sc.in(ts, m, 1, m), yy_ = sc.in(yy, 2 * n, 1, 2 * n), Z_ = B ? sc.in(Z, pm, B, ldz) : 0,
-                 mean_ = sc.out(mean, pm, 1, pm), cov_ = cov ? sc.out(cov, pm, pm, ldc) : 0, draws_ = B ? sc.out(draws, pm, B, ldd) : 0;
-    if ((rc = sc.begin())) return rc;
-    if ((rc = joint_predict_core(c, sc.dev(t_), n, sc.dev(yy_), alpha, l, sigma, jitter, sc.dev(ts_), m, orders, post_jitter,
-                                 sc.dev(mean_), cov ? sc.dev(cov_) : nullptr, pm, B ? sc.dev(Z_) : nullptr, B, pm,
-                                 B ? sc.dev(draws_) : nullptr, pm, c->d_info + 1)))
+    // cov == NULL or B == 0: no p m x p m or p m x B slot either
+    HostCall hc(c);
+    const size_t t_ = hc.in(t, n, 1, n), ts_ = hc.in(ts, m, 1, m), yy_ = hc.in(yy, 2 * n, 1, 2 * n), Z_ = B ? hc.in(Z, pm, B, ldz) : 0,
+                 mean_ = hc.out(mean, pm, 1, pm), cov_ = cov ? hc.out(cov, pm, pm, ldc) : 0, draws_ = B ? hc.out(draws, pm, B, ldd) : 0;
+    if ((rc = hc.begin(small_joint_predict(c, n, m, p) ? HOST_PINNED : HOST_STAGED))) return rc;
+    if ((rc = joint_predict_core(c, hc.dev(t_), n, hc.dev(yy_), alpha, l, sigma, jitter, hc.dev(ts_), m, orders, post_jitter,
+                                 hc.dev(mean_), cov ? hc.dev(cov_) : nullptr, pm, B ? hc.dev(Z_) : nullptr, B, pm,
+                                 B ? hc.dev(draws_) : nullptr, pm, hc.info(), hc.link())))
         return rc;
-    return sc.finish(c->d_info + 1);
+    return hc.finish();
 }
 
 // ---- sequential conditional sampler -------------------------------------
@@ -4745,12 +4626,12 @@ extern "C" int gpmi_hermite_basis(gpmi_ctx *c, const double *x, int n, int M, do
     if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
     if (ldp < n || (dPhi_dl && lddp < n)) return gpmi_fail(GPMI_EARG, "leading dimension below n");
     if (!x || !Phi) return gpmi_fail(GPMI_EARG, "NULL pointer");
-    StageCall sc(c);
-    const size_t x_ = sc.in(x, n, 1, n), P_ = sc.out(Phi, n, M, ldp), D_ = sc.out(dPhi_dl, n, M, lddp);
-    if ((rc = sc.begin())) return rc;
-    launch_lr_basis(c->stream, sc.dev(x_), n, M, lr_params(scale, amp, l), sc.dev(P_), (size_t)n, dPhi_dl ? sc.dev(D_) : nullptr, (size_t)n);
+    HostCall hc(c);
+    const size_t x_ = hc.in(x, n, 1, n), P_ = hc.out(Phi, n, M, ldp), D_ = hc.out(dPhi_dl, n, M, lddp);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    launch_lr_basis(c->stream, hc.dev(x_), n, M, lr_params(scale, amp, l), hc.dev(P_), (size_t)n, dPhi_dl ? hc.dev(D_) : nullptr, (size_t)n);
     HIPCHK(hipGetLastError());
-    return sc.finish(nullptr);
+    return hc.finish(false);
 }
 
 static int lowrank_logml_core(gpmi_ctx *c, const double *dx, int n, const double *dy, int M, double scale, double amp, double l,
@@ -4783,12 +4664,12 @@ extern "C" int gpmi_lowrank_logml_grad(gpmi_ctx *c, const double *x, int n, cons
     if ((rc = lowrank_check(n, M, scale, amp, l))) return rc;
     if (!pos_finite(sigma)) return gpmi_fail(GPMI_EARG, "sigma must be positive and finite");
     if (!x || !y || !out3) return gpmi_fail(GPMI_EARG, "NULL pointer");
-    StageCall sc(c);
-    const size_t x_ = sc.in(x, n, 1, n), y_ = sc.in(y, n, 1, n), o_ = sc.out(out3, 3, 1, 3), g_ = sc.out(grad, 3, 1, 3);
-    if ((rc = sc.begin())) return rc;
-    if ((rc = lowrank_logml_core(c, sc.dev(x_), n, sc.dev(y_), M, scale, amp, l, sigma, sc.dev(o_), grad ? sc.dev(g_) : nullptr, sc.info())))
+    HostCall hc(c);
+    const size_t x_ = hc.in(x, n, 1, n), y_ = hc.in(y, n, 1, n), o_ = hc.out(out3, 3, 1, 3), g_ = hc.out(grad, 3, 1, 3);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    if ((rc = lowrank_logml_core(c, hc.dev(x_), n, hc.dev(y_), M, scale, amp, l, sigma, hc.dev(o_), grad ? hc.dev(g_) : nullptr, hc.info())))
         return rc;
-    return sc.finish(sc.info());
+    return hc.finish();
 }
 
 static int lowrank_latent_check(int n, int M, double scale, double amp, double l, int family, int m, int ldy, double sigma)
@@ -4832,15 +4713,15 @@ extern "C" int gpmi_lowrank_latent_lp_grad(gpmi_ctx *c, const double *x, int n, 
     if ((rc = lowrank_latent_check(n, M, scale, amp, l, family, m, ldy, sigma))) return rc;
     if (!x || !z || !Y || !out || !zbar || !grad) return gpmi_fail(GPMI_EARG, "NULL pointer");
     if (family == GPMI_LIK_BERNOULLI_LOGIT && (rc = bernoulli_y_check(Y, n, m, ldy))) return rc;
-    StageCall sc(c);
-    const size_t x_ = sc.in(x, n, 1, n), z_ = sc.in(z, M, 1, M), Y_ = sc.in(Y, n, m, ldy), o_ = sc.out(out, 2, 1, 2),
-                 q_ = sc.out(q, n, 1, n), qb_ = sc.out(qbar, n, 1, n), zb_ = sc.out(zbar, M, 1, M), g_ = sc.out(grad, 2, 1, 2);
-    if ((rc = sc.begin())) return rc;
-    const LatentHead lh{family, sc.dev(Y_), m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
-    if ((rc = lowrank_latent_core(c, sc.dev(x_), n, M, scale, amp, l, sc.dev(z_), lh, sc.dev(o_), q ? sc.dev(q_) : nullptr,
-                                  qbar ? sc.dev(qb_) : nullptr, sc.dev(zb_), sc.dev(g_))))
+    HostCall hc(c);
+    const size_t x_ = hc.in(x, n, 1, n), z_ = hc.in(z, M, 1, M), Y_ = hc.in(Y, n, m, ldy), o_ = hc.out(out, 2, 1, 2),
+                 q_ = hc.out(q, n, 1, n), qb_ = hc.out(qbar, n, 1, n), zb_ = hc.out(zbar, M, 1, M), g_ = hc.out(grad, 2, 1, 2);
+    if ((rc = hc.begin(HOST_STAGED))) return rc;
+    const LatentHead lh{family, hc.dev(Y_), m, n, sigma, family == GPMI_LIK_NORMAL ? log(sigma) : 0.0};
+    if ((rc = lowrank_latent_core(c, hc.dev(x_), n, M, scale, amp, l, hc.dev(z_), lh, hc.dev(o_), q ? hc.dev(q_) : nullptr,
+                                  qbar ? hc.dev(qb_) : nullptr, hc.dev(zb_), hc.dev(g_))))
         return rc;
-    return sc.finish(nullptr);
+    return hc.finish(false);
 }
 
 // ---- diagnostics ---------------------------------------------------------------

@@ -459,6 +459,91 @@ def seq_marginals(n=21, m=41):
     return fn
 
 
+def logml_loo(want_all):
+    """gpmi_logml_loo at n = 37; want_all=False: the nullable mu, var, lpd and grad all NULL."""
+    def fn(lib, h, B):
+        _, X, y = _data(N)
+        pX, ldx = B.mat(X)
+        out = np.full(3, SENTINEL); loo = np.full(1, SENTINEL); g = np.full(2 + D, SENTINEL)
+        mu, var, lpd = np.full(N, SENTINEL), np.full(N, SENTINEL), np.full(N, SENTINEL)
+        opt = (mu, var, lpd, g) if want_all else (None,) * 4
+        rc = lib.gpmi_logml_loo(h, pX, N, ldx, D, B.vec(y), _d(ALPHA), B.vec(ELL), D, _d(SIGMA), _d(JIT), _p(out), _p(loo), *map(_p, opt))
+        res = {"rc": rc, "out": out, "loo": loo}
+        if want_all:
+            res.update(mu=mu, var=var, lpd=lpd, grad=g)
+        return res
+    return fn
+
+
+def logml_hess(n_ell, want_grad=True):
+    """gpmi_logml_hess at n = 37 with one length-scale or one per dimension: the Hessian is (2 + n_ell) x (2 + n_ell)."""
+    def fn(lib, h, B):
+        _, X, y = _data(N)
+        pX, ldx = B.mat(X)
+        q = 2 + n_ell
+        out = np.full(3, SENTINEL); g = np.full(q, SENTINEL)
+        H, pH, ldh = B.out(q, q)
+        rc = lib.gpmi_logml_hess(h, pX, N, ldx, D, B.vec(y), _d(ALPHA), B.vec(ELL[:n_ell]), n_ell, _d(SIGMA), _d(JIT), _p(out),
+                                 _p(g) if want_grad else None, pH, ldh)
+        res = {"rc": rc, "out": out, "hess": H}
+        if want_grad:
+            res["grad"] = g
+        return res
+    return fn
+
+
+LR_M, LR_SCALE, LR_AMP, LR_L = 8, 0.25, 1.3, 0.3
+
+
+def _lowrank_data(seed=23):
+    """x sorted in [-0.5, 0.5] (the basis is scaled for that interval), y, the M coefficients z and replicate columns Y."""
+    rng = np.random.default_rng(seed)
+    x = np.sort(rng.uniform(-0.5, 0.5, N))
+    return x, np.sin(3.0 * x) + 0.3 * rng.standard_normal(N), rng.standard_normal(LR_M), rng.standard_normal((N, M))
+
+
+def hermite_basis(want_dl):
+    def fn(lib, h, B):
+        x = _lowrank_data()[0]
+        P, pP, ldp = B.out(N, LR_M)
+        dP, pdP, lddp = B.out(N, LR_M, want_dl)
+        rc = lib.gpmi_hermite_basis(h, B.vec(x), N, LR_M, _d(LR_SCALE), _d(LR_AMP), _d(LR_L), pP, ldp, pdP, lddp)
+        res = {"rc": rc, "Phi": P}
+        if want_dl:
+            res["dPhi_dl"] = dP
+        return res
+    return fn
+
+
+def lowrank_logml_grad(want_grad):
+    def fn(lib, h, B):
+        x, y, _, _ = _lowrank_data()
+        out = np.full(3, SENTINEL); g = np.full(3, SENTINEL)
+        rc = lib.gpmi_lowrank_logml_grad(h, B.vec(x), N, B.vec(y), LR_M, _d(LR_SCALE), _d(LR_AMP), _d(LR_L), _d(SIGMA), _p(out),
+                                         _p(g) if want_grad else None)
+        res = {"rc": rc, "out": out}
+        if want_grad:
+            res["grad"] = g
+        return res
+    return fn
+
+
+def lowrank_latent_lp_grad(want_q):
+    """The NORMAL head on M replicate columns; want_q=False: the nullable q and qbar NULL."""
+    def fn(lib, h, B):
+        x, _, z, Y = _lowrank_data()
+        pY, ldy = B.mat(Y)
+        out = np.full(2, SENTINEL); zb = np.full(LR_M, SENTINEL); g = np.full(2, SENTINEL)
+        q, qb = np.full(N, SENTINEL), np.full(N, SENTINEL)
+        rc = lib.gpmi_lowrank_latent_lp_grad(h, B.vec(x), N, LR_M, _d(LR_SCALE), _d(LR_AMP), _d(LR_L), B.vec(z), NORMAL, pY, M, ldy,
+                                             _d(0.7), _p(out), _p(q) if want_q else None, _p(qb) if want_q else None, _p(zb), _p(g))
+        res = {"rc": rc, "out": out, "zbar": zb, "grad": g}
+        if want_q:
+            res.update(q=q, qbar=qb)
+        return res
+    return fn
+
+
 ONE, CHAIN = "one workgroup", "chain"
 # (id, {option: value} of the context, call)
 CASES = [
@@ -532,6 +617,18 @@ CASES = [
     ("seq_marginals-n21-m41-chunks", {"predict_mb": 16}, seq_marginals()),
     ("interp_build-approx_Lz_grad-n37", {}, interp_build_Lz_grad(N)),
     ("interp_build-approx_Lz_grad-n300", {}, interp_build_Lz_grad(300)),
+    # leave-one-out and the Hessian (one route each: the chain), the low-rank model (one launch chain whatever the size)
+    ("logml_loo", {}, logml_loo(True)),
+    ("logml_loo-nulls", {}, logml_loo(False)),
+    ("logml_hess-nell1", {}, logml_hess(1)),
+    ("logml_hess-nell2", {}, logml_hess(2)),
+    ("logml_hess-nell2-nograd", {}, logml_hess(2, False)),
+    ("hermite_basis", {}, hermite_basis(True)),
+    ("hermite_basis-nodl", {}, hermite_basis(False)),
+    ("lowrank_logml_grad", {}, lowrank_logml_grad(True)),
+    ("lowrank_logml_grad-nograd", {}, lowrank_logml_grad(False)),
+    ("lowrank_latent-normal", {}, lowrank_latent_lp_grad(True)),
+    ("lowrank_latent-normal-noq", {}, lowrank_latent_lp_grad(False)),
 ]
 
 # Every option that sends a call to the blocked factorisation and the launch chains, whatever its size

@@ -8,7 +8,8 @@ bit for bit -- outputs, gradient and return code -- and every padding row of eve
 
 The bit-for-bit comparison rests on each packed call repeating itself bit for bit at its shape: every reduction of the
 library has a fixed order, and the parent of the commit that added this file was checked to repeat itself on every case below
-(no exception was found, so no case falls back to a tolerance).
+(no exception was found, so no case falls back to a tolerance).  The cases added since (leave-one-out, the Hessian, the
+low-rank model) were checked the same way at the parent of the commit that added them.
 
 A path is forced the way the neighbouring tests do it: a fresh Context with the relevant small_* option at 0 takes the chain,
 the default takes one workgroup; the three hard-coded switches (gpmi_exact_gp_f at n <= 256, gpmi_rbf_cov_chol at n <= 64, the
